@@ -2,8 +2,16 @@
 """bench.py -- TomatoEnv env-steps/sec on MI355X (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scheme ls5|rk4|rk3|rk2] [--n-sub S] [--window W] [--dtype f32|f64]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up (W steps), times the K steps and prints the line: `value`, `ms_per_step` and the figures taken from
+those same K steps (kernel time, roofline from the recorded counters, integrator events).  `--full` adds everything that takes runs of
+its own after the timed steps: the `sustained` continuation, the other scheme (`other_scheme`), the accuracy legs on the 10-day and
+hold-out fixtures (`parity`), the PARITY configuration (`parity_config`) and the CPU baselines; the `--no-*` options switch single
+legs of a --full run off.  `--dump-outputs DIR` writes what the K-th timed step handed its caller (observations, rewards, dones,
+infos, terminal observations) and the state it left, for a fixed sample of environments, as DIR/<name>.npy (see dump_outputs).
 
 A "step" is one batched TomatoEnv.step(): crop-noise-free control update, fused ODE step kernel
 (fourth-order Runge-Kutta sub-steps, reward / violation / info epilogue) and the observation-assembly kernel, for B
@@ -204,12 +212,49 @@ def parity_leg(args, dev, layout, n_sub=None, window=None, occupancy=0, fixture=
     return float(np.max(np.abs(X - XR) / scale)), float(failed), "%s, %d steps" % (fixture, len(acts))
 
 
+DUMP_ENVS = 16384          # environments --dump-outputs writes (all of them in a smaller batch): about 38 MB at obs dim 263
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, env, rank, world):
+    """--dump-outputs: what the LAST timed step handed its caller (TomatoVecEnv.step_tensor's obs / reward / done / info, and the
+    auto-reset's terminal observation of the environments that finished in it, zero elsewhere) and the state / controls it left, for a
+    fixed sample of environments (sorted, seed 0: the same rows in every run of the same batch), one float32 / float64 file per array.
+    `env_index` holds the sampled environments' indices.  With more than one rank every rank writes its own files (<name>_rank<r>.npy),
+    each sampling its share of DUMP_ENVS."""
+    import numpy as np
+    import torch
+    B = env.B
+    n = min(B, max(1, DUMP_ENVS // world))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    it = torch.as_tensor(idx, device=env.obs_t.device)
+    done = env.done_t[it].cpu().numpy().astype(np.float32)
+    arrays = {
+        "env_index": idx.astype(np.float64),
+        "obs": env.obs_t[it].cpu().numpy(),
+        "reward": env.reward_t[it].cpu().numpy(),
+        "done": done,
+        "info": env.info_T[:, it].t().cpu().numpy(),
+        "terminal_obs": np.where(done[:, None] > 0, env.term_obs_t[it].cpu().numpy(), np.float32(0)),
+        "state": env.x_T[:, it].t().cpu().numpy(),
+        "control": env.u_T[:, it].t().cpu().numpy(),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total * world <= DUMP_MAX_BYTES, f"--dump-outputs: {total * world} bytes exceed {DUMP_MAX_BYTES}"
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(out / f"{name}{sfx}.npy", np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    # Defaults measure SUSTAINED throughput: 2 000 steps = 1.3 s timed after 0.13 s of warm-up; the whole default run takes about
-    # 40 s (most of it the CPU-baseline legs).  A short region reads a little high: the driver's `--steps 20 --warmup 5` (12.6 ms
+    # Defaults measure SUSTAINED throughput: 2 000 steps = 1.3 s timed after 0.13 s of warm-up; the whole default run with --full
+    # takes about 40 s (most of it the CPU-baseline legs).  A short region reads a little high: the driver's `--steps 20 --warmup 5` (12.6 ms
     # timed) gave 1.042e8 in round 5 against 1.02e8 over 2 000 steps, +2 % (not the +25 % this comment claimed in rounds 1-5, which
-    # was the round-1 kernel's boost-clock burst).  Whatever K is, the line also carries a `sustained` block: the same loop
+    # was the round-1 kernel's boost-clock burst).  Whatever K is, a --full line also carries a `sustained` block: the same loop
     # continued until >= 1 s has been timed (below), so a short driver run records the sustained figure itself.
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
@@ -233,7 +278,16 @@ def main():
     ap.add_argument("--vecnorm", action="store_true", help="also run the on-device VecNormalize (obs + reward) each step")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node: one rank per GPU; without a launcher bench.py starts "
                                                         "torch.distributed.run itself")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs of their own: sustained continuation, other scheme, accuracy legs "
+                         "(parity, hold-out), parity configuration, CPU baselines (each can be switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (sampled environments) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:           # a plain run: set up, warm up, the K timed steps, the line
+        args.no_sustained = args.no_alt_scheme = args.no_parity = args.no_parity_config = args.no_cpu_baseline = True
 
     # ---- N > 1 without a launcher: become the launcher.  Nothing in THIS process has touched the GPU yet (no HIP call, no
     # torch.cuda.is_available(); device_count() does not initialise the runtime on this image), the ranks are fresh child
@@ -347,6 +401,8 @@ def main():
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:           # before any later leg steps the env again
+        dump_outputs(args.dump_outputs, env, rank, world)
 
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in (warm_events if replay is not None else events)]))
     m = env.metrics()

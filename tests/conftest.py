@@ -39,7 +39,7 @@ def _launch(job, nproc, extra_env, extra_args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", str(nproc), "--steps", "6", "--warmup", "2",
-           "--batch", "4096", "--no-cpu-baseline", "--no-alt-scheme"] + extra_args
+           "--batch", "4096", "--full", "--no-cpu-baseline", "--no-alt-scheme"] + extra_args
     job["proc"] = subprocess.Popen(cmd, stdout=log, stderr=subprocess.STDOUT, env=env, cwd=str(ROOT))
     job["log"] = log.name
 
@@ -77,9 +77,30 @@ def pytest_sessionfinish(session, exitstatus):
         job["proc"] = job["log"] = None
 
 
+class _SplitFixture:
+    """A fixture stored as NAME.npz + NAME_part2.npz (every committed file stays under 1 MiB), read as one: `.files` and `[key]`
+    over the arrays of both parts, like the NpzFile of a single file."""
+
+    def __init__(self, *paths):
+        self._parts = [np.load(p, allow_pickle=False) for p in paths]
+        self.files = [k for part in self._parts for k in part.files]
+
+    def __getitem__(self, key):
+        for part in self._parts:
+            if key in part.files:
+                return part[key]
+        raise KeyError(key)
+
+    def __contains__(self, key):
+        return key in self.files
+
+
 @pytest.fixture(scope="session")
 def golden():
     def load(name):
+        part2 = GOLDEN / f"{name}_part2.npz"
+        if part2.exists():
+            return _SplitFixture(GOLDEN / f"{name}.npz", part2)
         return np.load(GOLDEN / f"{name}.npz", allow_pickle=False)
     return load
 

@@ -840,7 +840,30 @@ def g_holdout_noisy():
     rel = np.abs(P / p0[128:162] - 1)
     print("holdout_gl2010_noisy: tOut %.1f..%.1f, iGlob max %.0f; crop entries off their defaults by up to %.3f; BDF-1e-6 band: one-step %.2e, "
           "free-running %.2e" % (w[:961, 1].min(), w[:961, 1].max(), w[:961, 0].max(), np.nanmax(rel), one.max(), free.max()))
-    np.savez_compressed(HERE / "holdout_gl2010_noisy.npz", actions=acts, weather=w[:1012], X=X, U=U, P_crop=P, p=p0, bdf_one_step=one, bdf_free=free)
+    # two files, each under the 1 MiB limit of a committed file; tests/conftest.py's `golden` loader reads them as one
+    np.savez_compressed(HERE / "holdout_gl2010_noisy.npz", actions=acts, weather=w[:1012], X=X, p=p0, bdf_one_step=one, bdf_free=free)
+    np.savez_compressed(HERE / "holdout_gl2010_noisy_part2.npz", U=U, P_crop=P)
+
+
+def g_weather_csv():
+    """The lines of the reference's two Bleiswijk weather files that a loader reads for start day 60 of GL2009 with refenv_day60's horizon
+    (2 days + 49 days of prediction at 300 s rows): GL2009 from row 60 x 288 to its end, and the head of GL2010 that the table runs into,
+    verbatim; of the GL2009 rows before day 60 only the count and the clock (first time stamp, step) are kept -- a loader uses no other
+    column of them.  tests/test_holdout_fixture.py writes the two files back and checks the package's loader against refenv_day60."""
+    import pandas as pd
+    src = {y: open(f"{WEATHER_DIR}/Bleiswijk/GL{y}.csv", "rb").read().splitlines(keepends=True) for y in (2009, 2010)}
+    t = pd.read_csv(f"{WEATHER_DIR}/Bleiswijk/GL2009.csv")["time"].values
+    dt = float(t[1] - t[0])
+    assert np.all(np.diff(t) == dt) and np.all(t == np.round(t))          # a uniform integer clock: filler rows can restate it exactly
+    rows09 = len(src[2009]) - 1
+    first = 60 * 86400 // int(dt)                                          # the loader's n0 for start day 60
+    n_tot = 2 * 86400 // int(dt) + 49 * 86400 // int(dt) + 1
+    need10 = first + n_tot - rows09
+    assert 0 < need10 < len(src[2010]) - 1
+    b = lambda lines: np.frombuffer(b"".join(lines), dtype=np.uint8)        # noqa: E731
+    np.savez_compressed(HERE / "weather_csv_gl2009_day60.npz", gl2009_header=b(src[2009][:1]), gl2009_rows=rows09, gl2009_t0=float(t[0]),
+                        gl2009_dt=dt, gl2009_first=first, gl2009_tail=b(src[2009][1 + first:]), gl2010_head=b(src[2010][:1 + need10]))
+    print("weather_csv_gl2009_day60: GL2009 rows %d.. of %d, GL2010 rows ..%d" % (first, rows09, need10))
 
 
 def g_refenv_day60():
@@ -873,7 +896,7 @@ def g_refenv_day60():
                         ra_actions=acts[:k], N=env.N, Np=env.Np, start_day=float(base["start_train_day"]), **out)
 
 
-ALL = dict(refenv_day60=g_refenv_day60, holdout_noisy=g_holdout_noisy, holdout_random=g_holdout_random, holdout_rulebased=g_holdout_rulebased, holdout_runtime=g_holdout_runtime,
+ALL = dict(weather_csv=g_weather_csv, refenv_day60=g_refenv_day60, holdout_noisy=g_holdout_noisy, holdout_random=g_holdout_random, holdout_rulebased=g_holdout_rulebased, holdout_runtime=g_holdout_runtime,
            holdout_season=g_holdout_season, jump=g_jump, refobs=g_refobs, refenv=g_refenv, storm=g_storm, helpers2=g_helpers2, pipe=g_pipe, rollout_summer=g_rollout_summer, params=g_params, weather=g_weather, rhs=g_rhs, step=g_step, reward=g_reward, noise=g_noise,
            controller=g_controller, env=g_env, rollout=g_rollout)
 

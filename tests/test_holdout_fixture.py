@@ -92,16 +92,28 @@ def test_product_arithmetic_on_the_noisy_parameter_holdout(golden, hostmath):
             assert plain < band
 
 
-REF_WEATHER = "/root/reference/gl_gym/environments/weather"
+def _write_weather_csv(golden, root):
+    """The reference's two Bleiswijk weather files as far as a loader reads them for start day 60 of GL2009 (weather_csv_gl2009_day60.npz,
+    make_golden.py g_weather_csv): the lines from day 60 on and the head of GL2010 verbatim, the GL2009 rows before day 60 with their own
+    clock and zeros in the columns no loader reads for this start day."""
+    g = golden("weather_csv_gl2009_day60")
+    d = root / "Bleiswijk"
+    d.mkdir()
+    t0, dt, n_cols = float(g["gl2009_t0"]), float(g["gl2009_dt"]), g["gl2009_header"].tobytes().count(b",") + 1
+    filler = "".join("%r%s\n" % (t0 + k * dt, ",0.0" * (n_cols - 1)) for k in range(int(g["gl2009_first"])))
+    (d / "GL2009.csv").write_bytes(g["gl2009_header"].tobytes() + filler.encode() + g["gl2009_tail"].tobytes())
+    (d / "GL2010.csv").write_bytes(g["gl2010_head"].tobytes())
+    assert (d / "GL2009.csv").read_bytes().count(b"\n") == 1 + int(g["gl2009_rows"])
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REF_WEATHER), reason="the reference's weather files are only in the build container")
-def test_host_weather_loader_follows_the_reference_past_the_end_of_a_file(golden):
+def test_host_weather_loader_follows_the_reference_past_the_end_of_a_file(golden, tmp_path):
     """refenv_day60.npz holds the table the REFERENCE's loader produced for start day 60 of GL2009 with the 49 days of horizon its env asks
     for (tomato_env.py:250-260): it runs past the end of the file and appends GL2010 (utils.py expandWeatherData).  The package's host
-    loader reads the same two files (data, not code) and must reproduce the table bit for bit."""
+    loader reads the same two files (data, not code; the lines it reads are stored in weather_csv_gl2009_day60.npz) and must reproduce
+    the table bit for bit."""
     from gl_gym_amd.utils import load_weather_data
     g = golden("refenv_day60")
-    w = load_weather_data(REF_WEATHER, "Bleiswijk", "GL", 2009, 60, 2, int(g["Np"]) + 1, 900, 10)
+    _write_weather_csv(golden, tmp_path)
+    w = load_weather_data(str(tmp_path), "Bleiswijk", "GL", 2009, 60, 2, int(g["Np"]) + 1, 900, 10)
     assert w.shape == g["weather"].shape == (4896, 10)
     np.testing.assert_array_equal(w, g["weather"])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 4: bench lines of the other configurations (BASELINE configs[1], [4], large and small batches), default step counts shortened.
 OUT=gpurun_out/r04_var; mkdir -p $OUT
-run() { name=$1; shift; python3 bench.py --no-cpu-baseline --no-alt-scheme "$@" > $OUT/r04_variant_${name}_bench_line.json 2> $OUT/$name.err; python3 -c "
+run() { name=$1; shift; python3 bench.py --full --no-cpu-baseline --no-alt-scheme "$@" > $OUT/r04_variant_${name}_bench_line.json 2> $OUT/$name.err; python3 -c "
 import json,sys; d=json.load(open('$OUT/r04_variant_${name}_bench_line.json')); print('$name', '%.4g env-steps/s' % d['value'], '%.4f ms/step' % d['ms_per_step'], 'kernel %.4f ms' % d['roofline']['kernel_ms'], 'frac', d['roofline']['frac'], 'parity', (d.get('parity') or {}).get('max_scaled_err_10day'))"; }
 run config2_f64_b4096 --dtype f64 --batch 4096 --steps 300 --warmup 30
 run f64_b65536 --dtype f64 --steps 100 --warmup 10
