@@ -21,6 +21,7 @@
 #include "glgym.h"
 #include "gl_model.hpp"
 #include "gl_model_quad.hpp"
+#include "glgym_bdf.h"
 
 using namespace glm;
 
@@ -1281,6 +1282,14 @@ struct glgym_handle_s {
     int obs_modules[6] = {0, 1, 2, 3, 4, 5};   // observation modules in output order (glgym_set_obs_modules)
     int n_obs_modules = 6;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // glgym_evalF's integrator (glgym_set_integrator / glgym_set_tolerances) and the per-row statistics of its last BDF call
+    int integrator = GLGYM_INTEGRATOR_EXPLICIT;
+    double rtol = 1e-6, atol = 1e-6;
+    int max_steps = 10000;
+    int32_t* stats_dev = nullptr;
+    int stats_cap = 0;
+    std::vector<int32_t> stats;         // [stats_rows][GLGYM_NSOLVER_STAT]
+    int stats_rows = 0;
     // scratch for the host-pointer entry points
     double* scratch = nullptr;
     size_t scratch_elems = 0;
@@ -1326,7 +1335,13 @@ struct DeviceGuard {
 
 extern "C" {
 
-const char* glgym_version(void) { return "glgym 0.5 (gfx950; ABI 5; stability-controlled, step-doubling-verified sub-steppers in delta form: five-stage fourth-order 2N scheme / RK4 / RK3 / midpoint)"; }
+#define GLGYM_STR_(v) #v
+#define GLGYM_STR(v) GLGYM_STR_(v)
+const char* glgym_version(void)
+{
+    return "glgym 0.7 (gfx950; ABI " GLGYM_STR(GLGYM_ABI_VERSION) "; stability-controlled, step-doubling-verified sub-steppers in delta form: "
+           "five-stage fourth-order 2N scheme / RK4 / RK3 / midpoint; adaptive variable-order BDF for glgym_evalF)";
+}
 int glgym_abi_version(void) { return GLGYM_ABI_VERSION; }
 const char* glgym_last_error(void) { return g_err.c_str(); }
 
@@ -1388,6 +1403,7 @@ int glgym_destroy(glgym_handle h)
     if (h->p0_crop_dev) (void)hipFree(h->p0_crop_dev);
     if (h->fail_dev) (void)hipFree(h->fail_dev);
     if (h->scratch) (void)hipFree(h->scratch);
+    if (h->stats_dev) (void)hipFree(h->stats_dev);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     delete h;
@@ -1472,6 +1488,36 @@ int glgym_set_control_limits(glgym_handle h, const double* u_min, const double* 
         if (!(u_min[j] <= u_max[j])) { g_err = "glgym_set_control_limits: u_min > u_max"; return GLGYM_EINVAL; }
     for (int j = 0; j < NU; ++j) { h->u_min[j] = (float)u_min[j]; h->u_max[j] = (float)u_max[j]; }    // float32 arrays,
     h->du = (float)delta_u_max;                                                                       // base_env.py:72-74
+    return GLGYM_OK;
+}
+
+int glgym_set_integrator(glgym_handle h, int integrator)
+{
+    if (!h || (integrator != GLGYM_INTEGRATOR_EXPLICIT && integrator != GLGYM_INTEGRATOR_BDF)) {
+        g_err = "glgym_set_integrator: GLGYM_INTEGRATOR_EXPLICIT or GLGYM_INTEGRATOR_BDF";
+        return GLGYM_EINVAL;
+    }
+    h->integrator = integrator;
+    return GLGYM_OK;
+}
+
+int glgym_set_tolerances(glgym_handle h, double rtol, double atol, int max_steps)
+{
+    if (!h || !(rtol > 0.0) || !(atol > 0.0) || !std::isfinite(rtol) || !std::isfinite(atol) || max_steps < 1) {
+        g_err = "glgym_set_tolerances: rtol > 0, atol > 0 (finite), max_steps >= 1";
+        return GLGYM_EINVAL;
+    }
+    h->rtol = rtol; h->atol = atol; h->max_steps = max_steps;
+    return GLGYM_OK;
+}
+
+int glgym_get_solver_stats(glgym_handle h, int B, int32_t* stats)
+{
+    if (!h || !stats || B < 1 || B != h->stats_rows) {
+        g_err = "glgym_get_solver_stats: B must be the batch size of the last glgym_evalF with GLGYM_INTEGRATOR_BDF";
+        return GLGYM_EINVAL;
+    }
+    std::memcpy(stats, h->stats.data(), (size_t)B * GLGYM_NSOLVER_STAT * sizeof(int32_t));
     return GLGYM_OK;
 }
 
@@ -1601,6 +1647,11 @@ static int evalf_impl(glgym_handle h, const double* x, const double* u, const do
         return GLGYM_EINVAL;
     }
     HIPCHK(hipSetDevice(h->device));
+    const bool bdf = !rhs_only && h->integrator == GLGYM_INTEGRATOR_BDF;
+    if (bdf && h->variant == GLGYM_ODE_PIPE) {
+        g_err = "glgym_evalF: GLGYM_INTEGRATOR_BDF does not support GLGYM_ODE_PIPE";
+        return GLGYM_EINVAL;
+    }
     const double* p_used = p ? p : h->p;
     // per-row parameter blocks may differ only inside the crop block p[128..161] (what noise.py perturbs);
     // anything else is handled one row at a time.
@@ -1609,11 +1660,15 @@ static int evalf_impl(glgym_handle h, const double* x, const double* u, const do
         for (int b = 1; b < B && per_row; ++b)
             for (int i = 0; i < NP; ++i)
                 if ((i < CROP0 || i >= CROP0 + NCROP) && p[(size_t)b * NP + i] != p[i]) {
+                    std::vector<int32_t> st(bdf ? (size_t)B * GLGYM_NSOLVER_STAT : 0);
                     for (int r = 0; r < B; ++r) {
                         const int rc = evalf_impl(h, x + (size_t)r * NX, u + (size_t)r * NU, d + (size_t)r * h->nd,
                                                   p + (size_t)r * NP, 1, 1, out + (size_t)r * NX, rhs_only);
+                        if (bdf && h->stats_rows == 1)
+                            std::memcpy(&st[(size_t)r * GLGYM_NSOLVER_STAT], h->stats.data(), sizeof(int32_t) * GLGYM_NSOLVER_STAT);
                         if (rc != GLGYM_OK) return rc;
                     }
+                    if (bdf) { h->stats = st; h->stats_rows = B; }
                     return GLGYM_OK;
                 }
     }
@@ -1634,7 +1689,23 @@ static int evalf_impl(glgym_handle h, const double* x, const double* u, const do
     }
     HIPCHK(hipMemset(h->fail_dev, 0, sizeof(int)));
     HIPCHK(hipMemset(dout, 0xFF, (size_t)B * NX * sizeof(double)));      // a row no lane writes reads back as NaN, not as the previous call's
-    if (h->dtype == GLGYM_F32) {
+    if (bdf) {
+        // fp64 for either handle dtype (every handle carries the fp64 constants)
+        if (h->stats_cap < B) {
+            if (h->stats_dev) (void)hipFree(h->stats_dev);
+            h->stats_dev = nullptr; h->stats_cap = 0;
+            HIPCHK(hipMalloc(&h->stats_dev, (size_t)B * GLGYM_NSOLVER_STAT * sizeof(int32_t)));
+            h->stats_cap = B;
+        }
+        h->stats_rows = 0;
+        ModelConst<double> m = h->md;
+        if (p) make_model_const<double>(p_used, m);
+        HIPCHK(bdf_launch(dx, du, dd, dcrop, B, h->nd, h->dt, h->rtol, h->atol, h->max_steps, m, p_used[39], p_used[162], dout,
+                          h->stats_dev, h->fail_dev));
+        h->stats.resize((size_t)B * GLGYM_NSOLVER_STAT);
+        HIPCHK(hipMemcpy(h->stats.data(), h->stats_dev, h->stats.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        h->stats_rows = B;
+    } else if (h->dtype == GLGYM_F32) {
         ModelConst<float> m = h->mf;
         if (p) make_model_const<float>(p_used, m);
         rc = run_evalf<float>(h, m, p_used, dx, du, dd, dcrop, B, dout, rhs_only);
@@ -1649,7 +1720,8 @@ static int evalf_impl(glgym_handle h, const double* x, const double* u, const do
     HIPCHK(hipMemcpy(&n_failed, h->fail_dev, sizeof(int), hipMemcpyDeviceToHost));
     if (n_failed > 0) {
         g_err = "glgym_evalF: the integration failed for " + std::to_string(n_failed) + " of " + std::to_string(B) +
-                " rows (no two consecutive attempts of the n_sub, 2x, 4x, 8x ladder agreed); their rows of x_next are NaN";
+                (bdf ? " rows (BDF: step limit, right-hand-side limit, step-size underflow or a non-finite value)"
+                     : " rows (no two consecutive attempts of the n_sub, 2x, 4x, 8x ladder agreed)") + "; their rows of x_next are NaN";
         return GLGYM_EODE;
     }
     // Every row of a call that reports no failure has been written by exactly one lane group; the buffer was NaN-filled before the
@@ -1805,6 +1877,10 @@ extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream
     if (a->B < 1 || a->ld < a->B || !a->x || !a->u || !a->weather || !a->w_off || !a->timestep ||
         !a->reward || !a->done || (!a->action) == (!a->control) || a->weather_rows < 1) {
         g_err = "glgym_step: bad arguments (exactly one of action/control, ld >= B, non-null state/outputs)";
+        return GLGYM_EINVAL;
+    }
+    if (h->integrator != GLGYM_INTEGRATOR_EXPLICIT) {
+        g_err = "glgym_step: GLGYM_INTEGRATOR_BDF is available to glgym_evalF only; set GLGYM_INTEGRATOR_EXPLICIT for env-steps";
         return GLGYM_EINVAL;
     }
     DeviceGuard dev_guard(h);

@@ -1,0 +1,178 @@
+// glgym_bdf.hip -- the BDF integrator of glgym_evalF (GLGYM_INTEGRATOR_BDF): gl_bdf.hpp on a team of one wavefront per row.
+//
+// Layout: one 64-lane workgroup integrates one row.  The handle's ModelConst, the row's CropConst and StepCoef, the difference
+// array, the Jacobian and the LU factors live in LDS; lane i < 28 owns state i in the vector work.  A trajectory evaluation of the
+// right-hand side runs in lane 0; the 28 finite-difference columns of a Jacobian (and the base point of a re-evaluated one) run in
+// lanes 0..28 side by side from the same call site, so a Jacobian costs one right-hand-side latency.  fp64 throughout, for either
+// handle dtype.  No MFMA, no scalar-memory stores.
+#include "glgym_bdf.h"
+
+#include "gl_bdf.hpp"
+
+using namespace glm;
+
+namespace {
+
+constexpr int WAVE = 64;
+
+__device__ __forceinline__ double bdf_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    return v;
+}
+
+// v of lane k (k compile-time after unrolling): two v_readlane, no LDS round trip
+__device__ __forceinline__ double bdf_lane(double v, int k)
+{
+    const long long bits = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, k);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), k);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+struct WaveTeam {
+    static constexpr int width = WAVE;
+    int ln;
+    const ModelConst<double>& m;
+    const CropConst<double>& cr;
+    const StepCoef<double>& s;
+    __device__ int lane() const { return ln; }
+    __device__ double sum(double v) const { return bdf_wave_sum(v); }
+    __device__ void sync() const { __syncthreads(); }
+    // butterfly over (value, index): the largest value, the smallest index among equal values, in every lane
+    __device__ void argmax(double& v, int& i) const
+    {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(v, o, WAVE);
+            const int oi = __shfl_xor(i, o, WAVE);
+            if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+        }
+    }
+    // (I - c J) w = b: lane i holds w_i in a register; forward sweep in the serial order, back substitution as a column sweep
+    // (w_k = w_k / U_kk final, then lanes i < k take U_ik w_k off).  Rows of lanes >= 28 mirror row 27 and are never stored.
+    __device__ void lu_solve(glbdf::BdfScratch& sh, double* b) const
+    {
+        const int ii = ln < NX ? ln : NX - 1;
+        double w = b[sh.perm[ii]];
+#pragma unroll
+        for (int k = 0; k < NX - 1; ++k) {
+            const double lik = sh.LU[ii * NX + k], wk = bdf_lane(w, k);
+            if (ln > k) w -= lik * wk;
+        }
+#pragma unroll
+        for (int k = NX - 1; k >= 0; --k) {
+            const double uik = sh.LU[ii * NX + k], wk = bdf_lane(w, k) / sh.LU[k * NX + k];
+            if (ln == k) w = wk;
+            else if (ln < k) w -= uik * wk;
+        }
+        if (ln < NX) b[ln] = w;
+        __syncthreads();
+    }
+    __device__ void eval1(const double* x, double* f) const
+    {
+        if (ln == 0) {
+            double xs[NX], k[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) xs[i] = x[i];
+            rhs<double, true, false>(xs, s, m, cr, k);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) f[i] = k[i];
+        }
+        __syncthreads();
+    }
+    // lane j < 28: column j at x + dx_j e_j; lane 28 (need_f0): f0 = rhs(x) -- one call site, one right-hand-side latency
+    __device__ void jac(const double* x, double* f0, bool need_f0, double* J) const
+    {
+        double k[NX], dxj = 1.0;
+        if (ln < NX + (need_f0 ? 1 : 0)) {
+            double xs[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+                const double xi = x[i];
+                if (i == ln) { dxj = 1.4901161193847656e-8 * ::fmax(::fabs(xi), 1.0); xs[i] = xi + dxj; }
+                else xs[i] = xi;
+            }
+            rhs<double, true, false>(xs, s, m, cr, k);
+        }
+        if (need_f0 && ln == NX) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) f0[i] = k[i];
+        }
+        __syncthreads();
+        if (ln < NX) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) J[i * NX + ln] = (k[i] - f0[i]) / dxj;
+        }
+        __syncthreads();
+    }
+};
+
+__global__ __launch_bounds__(WAVE) void bdf_row_kernel(const double* __restrict__ x, const double* __restrict__ u,
+                                                       const double* __restrict__ d, const double* __restrict__ crop, int nd, double dt,
+                                                       double rtol, double atol, int max_steps, ModelConst<double> m_arg, double gasR,
+                                                       double tCanMin, double* __restrict__ out, int32_t* __restrict__ stats,
+                                                       int* __restrict__ n_failed)
+{
+    __shared__ glbdf::BdfScratch sh;
+    __shared__ ModelConst<double> sh_m[1];
+    __shared__ CropConst<double> sh_cr[1];
+    __shared__ StepCoef<double> sh_s[1];
+    const int b = blockIdx.x, ln = threadIdx.x;
+    {
+        // the parameter block in LDS (broadcast reads; as a kernel argument its ~180 doubles would not fit the SGPRs)
+        static_assert(sizeof(ModelConst<double>) % 4 == 0, "word copy");
+        const unsigned* src = reinterpret_cast<const unsigned*>(&m_arg);
+        unsigned* dst = reinterpret_cast<unsigned*>(&sh_m[0]);
+        for (int i = ln; i < (int)(sizeof(ModelConst<double>) / 4); i += WAVE) dst[i] = src[i];
+    }
+    __syncthreads();
+    if (ln == 0) {
+        CropConst<double> cr;
+        if (crop) make_crop_const<double, double>(crop + (size_t)b * NCROP, gasR, tCanMin, cr);
+        else cr = m_arg.crop;
+        sh_cr[0] = cr;
+    }
+    __syncthreads();
+    if (ln == 0) {
+        double uu[NU], dd[7];
+        for (int i = 0; i < NU; ++i) uu[i] = u[(size_t)b * NU + i];
+        for (int i = 0; i < 7; ++i) dd[i] = d[(size_t)b * nd + i];
+        StepCoef<double> s;
+        precompute(uu, dd, sh_m[0], sh_cr[0], s);
+        sh_s[0] = s;
+    }
+    double bad = 0.0;
+    if (ln < NX) {
+        const double v = x[(size_t)b * NX + ln];
+        sh.D[0][ln] = v;
+        if (!__builtin_isfinite(v)) bad = 1.0;
+    }
+    if (ln < NU && !__builtin_isfinite(u[(size_t)b * NU + ln])) bad = 1.0;
+    if (ln < 7 && !__builtin_isfinite(d[(size_t)b * nd + ln])) bad = 1.0;
+    __syncthreads();
+    const WaveTeam tm{ln, sh_m[0], sh_cr[0], sh_s[0]};
+    int32_t st[glbdf::NSTAT] = {0, 0, 0, 0, 0};
+    int rc = glbdf::BDF_FAIL_NONFINITE;
+    if (bdf_wave_sum(bad) == 0.0) rc = glbdf::bdf_step(tm, sh, dt, rtol, atol, max_steps, st);
+    if (ln < NX) out[(size_t)b * NX + ln] = rc == glbdf::BDF_OK ? sh.D[0][ln] : __builtin_nan("");
+    if (ln < glbdf::NSTAT) {
+        int32_t v = st[0];
+#pragma unroll
+        for (int i = 1; i < glbdf::NSTAT; ++i) v = ln == i ? st[i] : v;
+        stats[(size_t)b * glbdf::NSTAT + ln] = v;
+    }
+    if (ln == 0 && rc != glbdf::BDF_OK) atomicAdd(n_failed, 1);
+}
+
+}  // namespace
+
+hipError_t bdf_launch(const double* x, const double* u, const double* d, const double* crop, int B, int nd, double dt, double rtol,
+                      double atol, int max_steps, const ModelConst<double>& m, double gasR, double tCanMin, double* out,
+                      int32_t* stats, int* n_failed)
+{
+    hipLaunchKernelGGL(bdf_row_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)0, x, u, d, crop, nd, dt, rtol, atol, max_steps, m, gasR,
+                       tCanMin, out, stats, n_failed);
+    return hipGetLastError();
+}

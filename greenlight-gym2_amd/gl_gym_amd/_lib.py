@@ -17,7 +17,11 @@ SCHEME_RK4, SCHEME_RK2 = 0, 1
 SCHEME_RK3 = 2
 SCHEME_LS5 = 3
 SCHEMES = {"rk4": SCHEME_RK4, "rk2": SCHEME_RK2, "rk3": SCHEME_RK3, "ls5": SCHEME_LS5}
-ABI_VERSION = 6                                           # include/glgym.h GLGYM_ABI_VERSION
+ABI_VERSION = 7                                           # include/glgym.h GLGYM_ABI_VERSION
+# integrator of glgym_evalF (include/glgym.h glgym_integrator): the explicit sub-steppers (default) or the adaptive variable-order BDF
+INTEGRATORS = {"explicit": 0, "bdf": 1}
+NSOLVER_STAT = 5                                          # glgym_get_solver_stats: steps, rhs evals, Jacobians, factorisations, order
+SOLVER_STAT_KEYS = ("steps", "rhs_evals", "jacobians", "factorisations", "order")
 LAYOUTS = {"auto": 0, "one": 1, "quad": 2}                # glgym_layout
 # NOMINAL sub-steps per 900 s env-step.  RK4 (round 4): the conduction between the two faces of the cover glass -- the 0.65 1/s
 # mode that kept every explicit scheme at >= 224 sub-steps -- is integrated exactly (gl_model.hpp rk_delta, COVEXP), so the nominal
@@ -179,6 +183,9 @@ PROTOTYPES = {
     "glgym_get_reward_scale": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
     "glgym_evalF": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP, C.c_int, C.c_int, _DP]),
     "glgym_rhs": (C.c_int, [C.c_void_p, _DP, _DP, _DP, C.c_int, _DP]),
+    "glgym_set_integrator": (C.c_int, [C.c_void_p, C.c_int]),
+    "glgym_set_tolerances": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "glgym_get_solver_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
     "glgym_step": (C.c_int, [C.c_void_p, C.POINTER(StepArgs), C.c_void_p]),
     "glgym_obs": (C.c_int, [C.c_void_p, C.POINTER(ObsArgs), C.c_void_p]),
     "glgym_set_obs_modules": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),

@@ -145,8 +145,9 @@ typedef struct {
     double co2_min, co2_max, temp_min, temp_max, rh_min, rh_max;
 } glgym_reward_cfg;
 
-/* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5) */
-#define GLGYM_ABI_VERSION 6
+/* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
+ * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats */
+#define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
 typedef struct {
@@ -271,6 +272,25 @@ int glgym_get_reward_scale(glgym_handle h, double* max_profit, double* min_profi
 int glgym_evalF(glgym_handle h, const double* x, const double* u, const double* d, const double* p, int p_rows,
                 int B, double* x_next);
 int glgym_rhs(glgym_handle h, const double* x, const double* u, const double* d, int B, double* dx);
+
+/* Integrator of glgym_evalF (ABI 7).  GLGYM_INTEGRATOR_EXPLICIT (default): the sub-stepping scheme above (glgym_set_scheme,
+ * glgym_set_n_sub, glgym_set_window, glgym_set_verify).  GLGYM_INTEGRATOR_BDF: the algorithm family of the reference's CVODES
+ * call (greenlight_model.cpp:46-63) -- adaptive, error-controlled, variable-order (1-5) BDF / NDF with modified Newton iterations
+ * and a reused finite-difference Jacobian (Shampine & Reichelt 1997, the formulation of scipy.integrate.BDF), fp64 arithmetic for
+ * either handle dtype, one wavefront per row; the scheme, n_sub, window and verify settings do not apply to it.  Per-row parameter
+ * blocks are supported as for the explicit integrator.  A row that needs more than max_steps steps or 100 000 right-hand sides,
+ * whose step size underflows (below 1e-12 dt) or that meets a non-finite value is a failed row: NaN, GLGYM_EODE.
+ * With BDF set, glgym_step returns GLGYM_EINVAL (the env-step kernels integrate explicitly), as does glgym_evalF with
+ * GLGYM_ODE_PIPE.  glgym_rhs is unaffected. */
+typedef enum { GLGYM_INTEGRATOR_EXPLICIT = 0, GLGYM_INTEGRATOR_BDF = 1 } glgym_integrator;
+int glgym_set_integrator(glgym_handle h, int integrator);
+/* Tolerances of GLGYM_INTEGRATOR_BDF: rtol > 0, atol > 0 (the weighted RMS norm of the local error, weights atol + rtol |x_i|),
+ * max_steps >= 1 steps per row and call.  Default 1e-6, 1e-6 (the reference's abstol = reltol), 10 000. */
+int glgym_set_tolerances(glgym_handle h, double rtol, double atol, int max_steps);
+/* Solver statistics of the last glgym_evalF with GLGYM_INTEGRATOR_BDF, per row: stats[B][GLGYM_NSOLVER_STAT] = steps, right-hand
+ * side evaluations, Jacobians, LU factorisations, final order.  B must be the batch size of that call. */
+#define GLGYM_NSOLVER_STAT 5
+int glgym_get_solver_stats(glgym_handle h, int B, int32_t* stats);
 
 /* Observation modules (gl_gym/environments/observations.py:59-182), concatenated per row in the order of
  * TomatoEnv's `observation_modules` list (tomato_env.py:77-81, 193-198).  Default: all six in configs/envs/TomatoEnv.yml
