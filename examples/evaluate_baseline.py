@@ -3,6 +3,7 @@
 gl_gym/experiments/evaluate_baseline.py:12-37 (`evaluate_controller`) on this repo's API.
 
     python examples/evaluate_baseline.py --n-envs 1024 --season 10 [--uncertainty 0.2] [--weather-csv-dir DIR ...]
+                                         [--integrator bdf --rtol 1e-6 --atol 1e-6]
 
 Per step the reference records obs[:23], reward and 8 info keys for ONE env; here the same 32 columns are recorded
 for env 0 and, in addition, batch means over all envs (each env starts at a different day of the weather tensor).
@@ -35,6 +36,10 @@ def main():
     ap.add_argument("--location", default="Bleiswijk")
     ap.add_argument("--source", default="GL")
     ap.add_argument("--year", type=int, default=2009)
+    ap.add_argument("--integrator", choices=("explicit", "bdf"), default="explicit",
+                    help="bdf: error-controlled BDF env-steps at --rtol / --atol (the reference's CVODES family)")
+    ap.add_argument("--rtol", type=float, default=1e-6)
+    ap.add_argument("--atol", type=float, default=1e-6)
     args = ap.parse_args()
 
     if args.weather_csv_dir:
@@ -45,7 +50,8 @@ def main():
         starts = list(range(0, 35040 - int(args.season * 96) - 60, 96))
         days = [s / 96.0 for s in starts]
     env = TomatoVecEnv(args.n_envs, weather=w, dtype=args.dtype, season_length=args.season, start_rows=starts,
-                       start_days=days, uncertainty_scale=args.uncertainty, seed=666, auto_reset=False)
+                       start_days=days, uncertainty_scale=args.uncertainty, seed=666, auto_reset=False,
+                       integrator=args.integrator, rtol=args.rtol, atol=args.atol)
     ctrl = RuleBasedController()
     N1 = env.N + 1
     rec0 = np.zeros((N1, 23 + 1 + len(COLS)))

@@ -21,6 +21,7 @@
 #include "glgym.h"
 #include "gl_model.hpp"
 #include "gl_model_quad.hpp"
+#include "gl_reward.hpp"
 #include "glgym_bdf.h"
 
 using namespace glm;
@@ -63,38 +64,9 @@ template <> __device__ __forceinline__ const ModelConst<float>& device_default<f
 template <> __device__ __forceinline__ const ModelConst<double>& device_default<double>() { return g_default_f64; }
 
 // ---------------------------------------------------------------------------------------------------
-// reward constants (rewards.py:96-124,156-231; TomatoEnv.yml:38-67)
+// reward constants (gl_reward.hpp, shared with the BDF env-step of glgym_bdf.hip)
 // ---------------------------------------------------------------------------------------------------
-template <class T> struct RewardConst {
-    T heatK, elecK, co2K;       // cost per unit of u0 / u4 / u1 per env-step
-    T gainK;                    // EUR per mg m-2 of fruit dry matter
-    T minProfit, invRange;      // scale_reward(profit, min, max)
-    T fixedCosts;
-    T lo[3], hi[3], invMaxViol[3];
-    T kPpm;
-};
-
-template <class T> void make_reward_const(const double* p, double dt, const glgym_reward_cfg& c, RewardConst<T>& r,
-                                          double* max_profit, double* min_profit, double* fixed_costs)
-{
-    const double heat = p[108] / p[46] * dt / 3600 * 1e-3 * c.heating_price;
-    const double elec = p[172] * dt / 3600 * 1e-3 * c.elec_price;
-    const double co2 = p[109] / p[46] * dt * 1e-6 * c.co2_price;
-    const double maxP = p[154] * dt * 1e-6 / c.dmfm * c.fruit_price;
-    const double minP = -(heat + elec + co2);
-    const double yearly = c.fixed_greenhouse_cost + c.fixed_co2_cost + c.fixed_lamp_cost * 116 + c.fixed_screen_cost;
-    const double fixed = yearly / 365 / (double)(86400 / (long)dt);       // rewards.py:155 uses floor division
-    r.heatK = T(heat); r.elecK = T(elec); r.co2K = T(co2);
-    r.gainK = T(1e-6 / c.dmfm * c.fruit_price);
-    r.minProfit = T(minP); r.invRange = T(1.0 / (maxP - minP)); r.fixedCosts = T(fixed);
-    r.lo[0] = T(c.co2_min); r.lo[1] = T(c.temp_min); r.lo[2] = T(c.rh_min);
-    r.hi[0] = T(c.co2_max); r.hi[1] = T(c.temp_max); r.hi[2] = T(c.rh_max);
-    r.invMaxViol[0] = T(1.0 / 2500.0); r.invMaxViol[1] = T(1.0 / 15.0); r.invMaxViol[2] = T(1.0 / 15.0);   // :89-93
-    r.kPpm = T(8.3144598 / (101325.0 * 44.01e-3));
-    if (max_profit) *max_profit = maxP;
-    if (min_profit) *min_profit = minP;
-    if (fixed_costs) *fixed_costs = fixed;
-}
+template <class T> struct RewardConst : RewardConstBase<T> {};
 
 template <class T> struct StepArgsT {
     int B, ld;
@@ -119,11 +91,6 @@ template <class T> __device__ __forceinline__ T wave_sum(T v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
     return v;
-}
-
-template <class T> __device__ __forceinline__ T sat_vp_exact(T t)
-{
-    return T(610.78) * Math<T>::exp(T(17.2694) * t / (t + T(238.3)));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1284,6 +1251,7 @@ struct glgym_handle_s {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // glgym_evalF's integrator (glgym_set_integrator / glgym_set_tolerances) and the per-row statistics of its last BDF call
     int integrator = GLGYM_INTEGRATOR_EXPLICIT;
+    int step_integrator = GLGYM_INTEGRATOR_EXPLICIT;     // glgym_step's (glgym_set_step_integrator); the tolerances are shared
     double rtol = 1e-6, atol = 1e-6;
     int max_steps = 10000;
     int32_t* stats_dev = nullptr;
@@ -1498,6 +1466,16 @@ int glgym_set_integrator(glgym_handle h, int integrator)
         return GLGYM_EINVAL;
     }
     h->integrator = integrator;
+    return GLGYM_OK;
+}
+
+int glgym_set_step_integrator(glgym_handle h, int integrator)
+{
+    if (!h || (integrator != GLGYM_INTEGRATOR_EXPLICIT && integrator != GLGYM_INTEGRATOR_BDF)) {
+        g_err = "glgym_set_step_integrator: GLGYM_INTEGRATOR_EXPLICIT or GLGYM_INTEGRATOR_BDF";
+        return GLGYM_EINVAL;
+    }
+    h->step_integrator = integrator;
     return GLGYM_OK;
 }
 
@@ -1866,6 +1844,28 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
     }
 }
 
+// glgym_set_step_integrator(h, GLGYM_INTEGRATOR_BDF): one wavefront per environment in glgym_bdf.hip, fp64 integration for either dtype
+template <class T>
+static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const RewardConst<T>& rw, hipStream_t st)
+{
+    if (h->variant == GLGYM_ODE_PIPE) {
+        g_err = "glgym_step: GLGYM_INTEGRATOR_BDF does not support GLGYM_ODE_PIPE";
+        return GLGYM_EINVAL;
+    }
+    glbdf::BdfEnvArgs<T> k;
+    k.ld = a->ld;
+    k.x = (T*)a->x; k.u = (T*)a->u; k.action = a->action; k.control = (const T*)a->control;
+    k.weather = (const T*)a->weather; k.weather_rows = a->weather_rows; k.nd = h->nd;
+    k.w_off = a->w_off; k.timestep = a->timestep; k.crop_p = (const T*)a->crop_p; k.N = a->N;
+    k.reward = (T*)a->reward; k.info = (T*)a->info; k.done = a->done; k.step_flags = a->step_flags;
+    k.dt = h->dt; k.rtol = h->rtol; k.atol = h->atol; k.max_steps = h->max_steps;
+    k.gasR = h->p[39]; k.tCanMin = h->p[162];
+    k.du = h->du;
+    for (int j = 0; j < NU; ++j) { k.u_min[j] = h->u_min[j]; k.u_max[j] = h->u_max[j]; }
+    HIPCHK(bdf_env_launch<T>(k, a->B, h->md, rw, a->metrics, st));
+    return GLGYM_OK;
+}
+
 extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream)
 {
     if (!h || !a) { g_err = "glgym_step: null handle / arguments"; return GLGYM_EINVAL; }
@@ -1878,6 +1878,11 @@ extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream
         !a->reward || !a->done || (!a->action) == (!a->control) || a->weather_rows < 1) {
         g_err = "glgym_step: bad arguments (exactly one of action/control, ld >= B, non-null state/outputs)";
         return GLGYM_EINVAL;
+    }
+    if (h->step_integrator == GLGYM_INTEGRATOR_BDF) {
+        DeviceGuard dev_guard(h);
+        return h->dtype == GLGYM_F32 ? launch_step_bdf<float>(h, a, h->rf, (hipStream_t)stream)
+                                     : launch_step_bdf<double>(h, a, h->rd, (hipStream_t)stream);
     }
     if (h->integrator != GLGYM_INTEGRATOR_EXPLICIT) {
         g_err = "glgym_step: GLGYM_INTEGRATOR_BDF is available to glgym_evalF only; set GLGYM_INTEGRATOR_EXPLICIT for env-steps";

@@ -113,6 +113,10 @@ def make_step_args(*args, **kw):
 
 # step_flags bits (include/glgym.h GLGYM_SF_*)
 SF_FIRST_MASK, SF_ACCEPT_AGREE_FLAGGED, SF_ACCEPT_LAST_ALONE, SF_FAILED = 31, 32, 64, 128
+SF_BDF = 2048                    # the env-step ran the BDF integrator; its steps are in bits 16..30
+# metric slots of BDF env-steps (glgym.h GLGYM_METRIC_BDF): sums of steps, rhs evals, Jacobians, factorisations
+METRIC_BDF = 14
+BDF_METRIC_KEYS = ("bdf_steps", "bdf_rhs_evals", "bdf_jacobians", "bdf_factorisations")
 
 
 class ObsArgs(C.Structure):
@@ -186,6 +190,7 @@ PROTOTYPES = {
     "glgym_set_integrator": (C.c_int, [C.c_void_p, C.c_int]),
     "glgym_set_tolerances": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
     "glgym_get_solver_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "glgym_set_step_integrator": (C.c_int, [C.c_void_p, C.c_int]),
     "glgym_step": (C.c_int, [C.c_void_p, C.POINTER(StepArgs), C.c_void_p]),
     "glgym_obs": (C.c_int, [C.c_void_p, C.POINTER(ObsArgs), C.c_void_p]),
     "glgym_set_obs_modules": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),

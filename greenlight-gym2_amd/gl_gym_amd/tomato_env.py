@@ -30,6 +30,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from .greenlight_model import _check_integrator, _check_tolerances
 from .parameters import init_default_params
 from .utils import synthetic_weather
 
@@ -164,7 +165,8 @@ class TomatoVecEnv:
                  model_variant: str = "ode", scheme: Optional[str] = None, window: Optional[int] = None,
                  preset: Optional[str] = None,
                  observation_modules: Optional[Sequence[str]] = None, u_min: Optional[Sequence[float]] = None,
-                 u_max: Optional[Sequence[float]] = None, delta_u_max: float = 0.1, integration_info: bool = True):
+                 u_max: Optional[Sequence[float]] = None, delta_u_max: float = 0.1, integration_info: bool = True,
+                 integrator: str = "explicit", rtol: float = 1e-6, atol: float = 1e-6, max_steps: int = 10000):
         """u_min / u_max / delta_u_max: action_to_control's bounds (base_env.py:72-74; default [0, 1] and 0.1).
         observation_modules: names of the reference's modules in output order (default: the six of TomatoEnv.yml).
         scheme / n_sub / window: "ls5" (default; model_variant "ode_pipe" defaults to "rk4" and accepts no other: five-stage fourth-order 2N-storage scheme, n_sub 128, two sub-steps per tier-2b window), "rk4" (classical RK4, 240),
@@ -174,7 +176,13 @@ class TomatoVecEnv:
         integration_info: put the per-env GLGYM_SF_* word of each step into infos[i]["integration"] (one more B x 4-byte D2H copy
         per host-side step; False: not copied, key absent -- the device tensor `step_flags_t` is always written);
         weather: [rows, nd] with nd = 10, or 14 when the rows carry the measured pipe columns
-        (experiments/gl_predefined_controls.py:95, 107).  model_variant = "ode" | "ode_pipe" (ode.hpp:126-263, nd >= 14)."""
+        (experiments/gl_predefined_controls.py:95, 107).  model_variant = "ode" | "ode_pipe" (ode.hpp:126-263, nd >= 14).
+        integrator: "explicit" (default: the scheme / n_sub / window above) or "bdf" -- every env-step integrated by the adaptive,
+        error-controlled variable-order BDF in fp64 at rtol / atol, at most max_steps steps per env-step (include/glgym.h
+        glgym_set_step_integrator; the algorithm family of the reference's CVODES call); scheme, n_sub, window and preset stay stored and
+        apply again after set_integrator("explicit").  "bdf" does not combine with model_variant "ode_pipe"."""
+        _check_integrator(integrator, model_variant)
+        _check_tolerances(rtol, atol, max_steps)
         torch = _torch()
         if not torch.cuda.is_available():
             raise L.GlgymError("TomatoVecEnv needs a HIP device (torch.cuda.is_available() is False); "
@@ -232,6 +240,8 @@ class TomatoVecEnv:
             L.check(self._lib.glgym_set_model_variant(self._h, L.ODE_PIPE), "glgym_set_model_variant")
         L.check(self._lib.glgym_set_scheme(self._h, L.SCHEMES[scheme]), "glgym_set_scheme")
         L.check(self._lib.glgym_set_window(self._h, self.window), "glgym_set_window")
+        self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
+        self.set_integrator(integrator)
         self.u_min = np.asarray([0.0] * L.NU if u_min is None else u_min, dtype=np.float32)            # base_env.py:72-74
         self.u_max = np.asarray([1.0] * L.NU if u_max is None else u_max, dtype=np.float32)
         self.delta_u_max = np.ones(L.NU, dtype=np.float32) * np.float32(delta_u_max)
@@ -671,6 +681,27 @@ class TomatoVecEnv:
         self.set_n_sub(n_def if n_sub is None else n_sub)
         self.set_window((w_def if n_sub is None else 0) if window is None else window)
 
+    def set_integrator(self, name: str, rtol: Optional[float] = None, atol: Optional[float] = None,
+                       max_steps: Optional[int] = None):
+        """Integrator of the env-steps: "explicit" (the stored scheme / n_sub / window / preset) or "bdf" (adaptive, error-controlled
+        variable-order BDF in fp64, include/glgym.h glgym_set_step_integrator).  Tolerances not given keep their current values."""
+        rtol = self.rtol if rtol is None else rtol
+        atol = self.atol if atol is None else atol
+        max_steps = self.max_steps if max_steps is None else max_steps
+        _check_integrator(name, self.model_variant)
+        _check_tolerances(rtol, atol, max_steps)
+        L.check(self._lib.glgym_set_tolerances(self._h, float(rtol), float(atol), int(max_steps)), "glgym_set_tolerances")
+        L.check(self._lib.glgym_set_step_integrator(self._h, L.INTEGRATORS[name]), "glgym_set_step_integrator")
+        self.integrator, self.rtol, self.atol, self.max_steps = name, float(rtol), float(atol), int(max_steps)
+
+    def solver_metrics(self) -> Dict[str, float]:
+        """Totals of the BDF env-steps since the metrics were last zeroed (metric slots GLGYM_METRIC_BDF..+3): steps, right-hand-side
+        evaluations, Jacobians, LU factorisations.  The per-env step count of the last step is in bits 16..30 of step_flags_t."""
+        if self.metrics_t is None:
+            return {}
+        v = self.metrics_t.double().sum(dim=0)[L.METRIC_BDF:L.METRIC_BDF + len(L.BDF_METRIC_KEYS)].cpu().numpy()
+        return {k: float(v[i]) for i, k in enumerate(L.BDF_METRIC_KEYS)}
+
     def set_window(self, window: int):
         """Nominal sub-steps per tier-2b / harvest window (glgym_set_window): 0 = the scheme's own."""
         self.window = int(window)
@@ -726,9 +757,12 @@ class TomatoEnv:
     def __init__(self, weather=None, params=None, dt=900.0, season_length=60, pred_horizon=0.5, dtype="float64",
                  n_sub=None, device="cuda:0", uncertainty_scale=0.0, start_day=0.0, growth_year=2010,
                  reward_params=None, constraints=None, location="synthetic", training=True, model_variant="ode",
-                 scheme="rk4", observation_modules=None, u_min=None, u_max=None, delta_u_max=0.1):
+                 scheme="rk4", observation_modules=None, u_min=None, u_max=None, delta_u_max=0.1, integrator="explicit", rtol=1e-6,
+                 atol=1e-6, max_steps=10000):
+        """integrator / rtol / atol / max_steps: as TomatoVecEnv ("bdf": error-controlled BDF env-steps)."""
         self.vec = TomatoVecEnv(1, model_variant=model_variant, scheme=scheme, observation_modules=observation_modules,
-                                u_min=u_min, u_max=u_max, delta_u_max=delta_u_max,
+                                u_min=u_min, u_max=u_max, delta_u_max=delta_u_max, integrator=integrator, rtol=rtol, atol=atol,
+                                max_steps=max_steps,
                                 weather=weather, params=params, dt=dt, season_length=season_length,
                                 pred_horizon=pred_horizon, dtype=dtype, n_sub=n_sub, device=device,
                                 uncertainty_scale=uncertainty_scale, start_rows=[0], start_days=[start_day],

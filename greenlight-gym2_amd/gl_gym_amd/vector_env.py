@@ -42,6 +42,7 @@ class TomatoVectorEnv(_Base):
     metadata = {"autoreset_mode": "same_step", "render_modes": []}
 
     def __init__(self, num_envs: int, **kwargs):
+        """kwargs: TomatoVecEnv's, e.g. integrator="bdf", rtol=1e-6, atol=1e-6, max_steps=10000 for error-controlled BDF env-steps."""
         kwargs.setdefault("auto_reset", True)
         if not kwargs["auto_reset"]:
             raise ValueError("the VectorEnv facade autoresets (same-step); use TomatoVecEnv for manual resets")

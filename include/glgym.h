@@ -52,6 +52,9 @@ extern "C" {
                                stability control inserted: storms, wet screens pinned to the air temperature), then why
                                first attempts were unverified: n error-estimate flags, n branch-invariant flags, n cap /
                                non-finite flags, n heavy (>= 3x the nominal sub-steps) */
+#define GLGYM_METRIC_BDF 14 /* env-steps with GLGYM_INTEGRATOR_BDF (glgym_set_step_integrator) add slots 0..7 as above, leave slots 8..13
+                               at 0 and add to slots 14..17 = sum BDF steps, right-hand-side evaluations, Jacobians, LU factorisations.
+                               GLGYM_NMETRIC stays the count of the explicit kernels' slots. */
 #define GLGYM_METRIC_REPLICAS 64   /* accumulator blocks, one 128-byte line each (atomics onto a single line serialise) */
 #define GLGYM_METRIC_STRIDE 32     /* floats per replica */
 
@@ -146,7 +149,8 @@ typedef struct {
 } glgym_reward_cfg;
 
 /* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
- * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats */
+ * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
+ * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -184,6 +188,10 @@ typedef struct {
 #define GLGYM_SF_ACCEPT_LAST_ALONE 64      /* the finest attempt (8x n_sub), unflagged, taken as it stood although it did not agree
                                               with the attempt before it -- in verified mode as well */
 #define GLGYM_SF_FAILED 128                /* failed integration: done = 1, state unchanged */
+/* With GLGYM_INTEGRATOR_BDF (glgym_set_step_integrator) the word is GLGYM_SF_BDF | (GLGYM_SF_FAILED on failure) | BDF steps taken << 16
+ * (bits 16..30, saturating at 32 767); bits 0..6 and 8..10 are 0.  The totals of steps, right-hand sides, Jacobians and LU
+ * factorisations go to metric slots GLGYM_METRIC_BDF..+3. */
+#define GLGYM_SF_BDF 2048                  /* the env-step was integrated by the BDF integrator */
 
 /* Device-pointer arguments of observation assembly (row-major output, what SB3 / Gymnasium consume). */
 typedef struct {
@@ -280,15 +288,29 @@ int glgym_rhs(glgym_handle h, const double* x, const double* u, const double* d,
  * either handle dtype, one wavefront per row; the scheme, n_sub, window and verify settings do not apply to it.  Per-row parameter
  * blocks are supported as for the explicit integrator.  A row that needs more than max_steps steps or 100 000 right-hand sides,
  * whose step size underflows (below 1e-12 dt) or that meets a non-finite value is a failed row: NaN, GLGYM_EODE.
- * With BDF set, glgym_step returns GLGYM_EINVAL (the env-step kernels integrate explicitly), as does glgym_evalF with
- * GLGYM_ODE_PIPE.  glgym_rhs is unaffected. */
+ * glgym_evalF with GLGYM_ODE_PIPE returns GLGYM_EINVAL under BDF.  This setting governs glgym_evalF only: env-steps take theirs from
+ * glgym_set_step_integrator, and a handle whose glgym_evalF integrator is BDF while its env-step integrator is explicit gets
+ * GLGYM_EINVAL from glgym_step (a guard for callers that expected BDF env-steps).  glgym_rhs is unaffected. */
 typedef enum { GLGYM_INTEGRATOR_EXPLICIT = 0, GLGYM_INTEGRATOR_BDF = 1 } glgym_integrator;
 int glgym_set_integrator(glgym_handle h, int integrator);
-/* Tolerances of GLGYM_INTEGRATOR_BDF: rtol > 0, atol > 0 (the weighted RMS norm of the local error, weights atol + rtol |x_i|),
- * max_steps >= 1 steps per row and call.  Default 1e-6, 1e-6 (the reference's abstol = reltol), 10 000. */
+/* Integrator of glgym_step.  GLGYM_INTEGRATOR_EXPLICIT (default): the sub-stepping kernels below.  GLGYM_INTEGRATOR_BDF: the same
+ * row integrator as glgym_evalF's BDF (one 64-lane workgroup per environment, fp64 for either dtype) inside the env-step: controls
+ * (action path clipped in T, raw controls unclipped) stored to u first, the weather row and the (shared or per-env) crop block in
+ * double, the BDF step over dt at the glgym_set_tolerances settings, then the new state, reward, info and terminal test in T as the
+ * explicit kernels compute them (x27 from the step counter).  On the same double inputs the state equals glgym_evalF's BDF bit for
+ * bit.  A failed integration (step limit, the right-hand-side cap, step-size underflow, a singular matrix, a non-finite input)
+ * leaves the state unchanged with done = 1, no gains and GLGYM_OK, as the explicit kernels do; no other environment is affected.
+ * Scheme, n_sub, window, verify, layout, occupancy and ladder settings do not apply; GLGYM_ODE_PIPE gives GLGYM_EINVAL.  Launched on
+ * the caller's stream without host copies or synchronisation (capturable).  Per-env step counts: step_flags; totals: metric slots
+ * GLGYM_METRIC_BDF..+3. */
+int glgym_set_step_integrator(glgym_handle h, int integrator);
+/* Tolerances of GLGYM_INTEGRATOR_BDF, for glgym_evalF and glgym_step alike: rtol > 0, atol > 0 (the weighted RMS norm of the local
+ * error, weights atol + rtol |x_i|), max_steps >= 1 steps per row (environment) and call.  Default 1e-6, 1e-6 (the reference's
+ * abstol = reltol), 10 000. */
 int glgym_set_tolerances(glgym_handle h, double rtol, double atol, int max_steps);
 /* Solver statistics of the last glgym_evalF with GLGYM_INTEGRATOR_BDF, per row: stats[B][GLGYM_NSOLVER_STAT] = steps, right-hand
- * side evaluations, Jacobians, LU factorisations, final order.  B must be the batch size of that call. */
+ * side evaluations, Jacobians, LU factorisations, final order.  B must be the batch size of that call.  (glgym_step does not
+ * record them here: its per-env steps are in step_flags, its totals in metric slots GLGYM_METRIC_BDF..+3.) */
 #define GLGYM_NSOLVER_STAT 5
 int glgym_get_solver_stats(glgym_handle h, int B, int32_t* stats);
 
