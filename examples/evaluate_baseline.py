@@ -3,7 +3,7 @@
 gl_gym/experiments/evaluate_baseline.py:12-37 (`evaluate_controller`) on this repo's API.
 
     python examples/evaluate_baseline.py --n-envs 1024 --season 10 [--uncertainty 0.2] [--weather-csv-dir DIR ...]
-                                         [--integrator bdf --rtol 1e-6 --atol 1e-6]
+                                         [--integrator bdf --rtol 1e-6 --atol 1e-6] [--rng numpy]
 
 Per step the reference records obs[:23], reward and 8 info keys for ONE env; here the same 32 columns are recorded
 for env 0 and, in addition, batch means over all envs (each env starts at a different day of the weather tensor).
@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--year", type=int, default=2009)
     ap.add_argument("--integrator", choices=("explicit", "bdf"), default="explicit",
                     help="bdf: error-controlled BDF env-steps at --rtol / --atol (the reference's CVODES family)")
+    ap.add_argument("--rng", choices=("philox", "numpy"), default="philox",
+                    help="numpy: env b draws its start and its crop noise from the reference's stream np_random(seed + b)")
     ap.add_argument("--rtol", type=float, default=1e-6)
     ap.add_argument("--atol", type=float, default=1e-6)
     args = ap.parse_args()
@@ -51,7 +53,7 @@ def main():
         days = [s / 96.0 for s in starts]
     env = TomatoVecEnv(args.n_envs, weather=w, dtype=args.dtype, season_length=args.season, start_rows=starts,
                        start_days=days, uncertainty_scale=args.uncertainty, seed=666, auto_reset=False,
-                       integrator=args.integrator, rtol=args.rtol, atol=args.atol)
+                       integrator=args.integrator, rtol=args.rtol, atol=args.atol, rng=args.rng)
     ctrl = RuleBasedController()
     N1 = env.N + 1
     rec0 = np.zeros((N1, 23 + 1 + len(COLS)))

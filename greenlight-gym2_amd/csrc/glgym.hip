@@ -23,6 +23,7 @@
 #include "gl_model_quad.hpp"
 #include "gl_reward.hpp"
 #include "glgym_bdf.h"
+#include "glgym_rng.h"
 
 using namespace glm;
 
@@ -2081,6 +2082,31 @@ int glgym_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, 
         hipLaunchKernelGGL((crop_noise_kernel<double>), grid, block, 0, st, (double*)crop_p, B, ld, h->p0_crop_dev,
                            (float)scale, (unsigned long long)seed, (unsigned long long)draw_index);
     HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_rng_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t* rng_state, void* stream)
+{
+    DeviceGuard dev_guard(h);
+    if (!h || !rng_state || B < 1 || ld < B || !(scale >= 0.0)) {
+        g_err = "glgym_rng_crop_noise: bad arguments (null handle or stream buffer, ld < B, or a negative scale)";
+        return GLGYM_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (h->dtype == GLGYM_F32) HIPCHK(rng_crop_noise_launch<float>((float*)crop_p, B, ld, h->p0_crop_dev, scale, rng_state, st));
+    else HIPCHK(rng_crop_noise_launch<double>((double*)crop_p, B, ld, h->p0_crop_dev, scale, rng_state, st));
+    return GLGYM_OK;
+}
+
+int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
+                         const int32_t* start_rows, const float* start_days, int32_t* w_off, float* start_day, void* stream)
+{
+    DeviceGuard dev_guard(h);
+    if (!h || !rng_state || B < 1 || ld < B || n_years < 1 || n_days < 1 || !start_rows || !w_off) {
+        g_err = "glgym_rng_reset_draw: bad arguments (null pointer, ld < B, or an empty start grid)";
+        return GLGYM_EINVAL;
+    }
+    HIPCHK(rng_reset_draw_launch(B, ld, mask, rng_state, n_years, n_days, start_rows, start_days, w_off, start_day, (hipStream_t)stream));
     return GLGYM_OK;
 }
 

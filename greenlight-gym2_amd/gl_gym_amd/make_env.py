@@ -82,8 +82,10 @@ def tomato_vec_env_from_config(n_envs: int, reward_function: str, observation_mo
                                base_env_params: Optional[Dict[str, Any]] = None, uncertainty_scale: float = 0.0,
                                seed: int = 0, **device_kw):
     """``TomatoEnv(**env_specific_params, base_env_params=env_base_params)`` for n_envs environments at once.
-    device_kw: dtype, scheme, preset, n_sub, window, device, auto_reset, lazy_infos, model_variant, integrator, rtol, atol, max_steps
-    (TomatoVecEnv keyword arguments; integrator="bdf": error-controlled BDF env-steps);
+    device_kw: dtype, scheme, preset, n_sub, window, device, auto_reset, lazy_infos, model_variant, integrator, rtol, atol, max_steps, rng
+    (TomatoVecEnv keyword arguments; integrator="bdf": error-controlled BDF env-steps; rng="numpy": environment b draws its start
+    (year, day) and its crop noise from the reference's own stream Generator(PCG64(SeedSequence(seed + b))) -- the start grid
+    (len(years), len(days)) is passed along);
     weather_on_device=True builds the weather table with the device pipeline (weather_device.py)."""
     from .tomato_env import TomatoVecEnv
     base = dict(base_env_params or {})
@@ -105,6 +107,8 @@ def tomato_vec_env_from_config(n_envs: int, reward_function: str, observation_mo
                                               dt, int(base.get("nd", 10)), pipeline)
     if pipeline is not None:
         pipeline.close()
+    if device_kw.get("rng", "philox") == "numpy":
+        device_kw.setdefault("start_grid", (len(years), len(days)))
     env = TomatoVecEnv(n_envs, weather=table, dt=dt, season_length=season, pred_horizon=horizon, seed=seed,
                        start_rows=rows, start_days=sdays, reward_params=reward_params, constraints=constraints,
                        uncertainty_scale=uncertainty_scale, observation_modules=list(observation_modules),
@@ -124,11 +128,17 @@ def make_vec_env(env_id: str, env_base_params: Dict[str, Any], env_specific_para
     ``SubprocVecEnv([...] * n_envs)``, wrapped in the on-device VecNormalize when ``vec_norm_kwargs`` is given
     (evaluation envs: statistics frozen, rewards not normalised -- RL/utils.py:64-67).  The same three-layer stack as
     the reference: env -> VecMonitorGPU (episode return / length, ``infos[i]["episode"]``, optional monitor CSV) ->
-    VecNormalizeGPU."""
+    VecNormalizeGPU.
+    rng="numpy" (device_kw): as the reference's make_env does for every environment (RL/utils.py:39: `env.reset(seed + rank)` inside
+    _init), the construction ends with a seeded reset, so the reset() a caller issues next draws a second start, as
+    SubprocVecEnv.reset() does there.  Not reproduced: `env.action_space.seed(seed + rank)` and SB3's own generators, which live
+    outside the environment."""
     if env_id != "TomatoEnv":
         raise NotImplementedError(f"env_id {env_id!r}: only TomatoEnv exists (RL/utils.py:24)")
     env = tomato_vec_env_from_config(n_envs, base_env_params=env_base_params, seed=seed, **env_specific_params,
                                      **device_kw)
+    if env.rng == "numpy":
+        env.reset_tensor()           # the streams were seeded with seed + rank at construction: this is make_env's reset(seed + rank)
     from .vec_monitor import VecMonitorGPU
     if monitor_filename is not None and os.path.dirname(monitor_filename):
         os.makedirs(os.path.dirname(monitor_filename), exist_ok=True)

@@ -30,6 +30,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from . import np_stream
 from .greenlight_model import _check_integrator, _check_tolerances
 from .parameters import init_default_params
 from .utils import synthetic_weather
@@ -69,6 +70,21 @@ DEFAULT_CONSTRAINTS = dict(co2_min=300., co2_max=1600., temp_min=15., temp_max=3
 def _torch():
     import torch
     return torch
+
+
+RNGS = ("philox", "numpy")
+
+
+def _check_rng(rng, start_grid, n_starts):
+    """-> (rng, start_grid) as TomatoVecEnv stores them.  rng = "numpy" without a grid means (1, n_starts): one year, every start a day."""
+    if rng not in RNGS:
+        raise ValueError("rng must be 'philox' or 'numpy'")
+    if start_grid is None:
+        return rng, ((1, int(n_starts)) if rng == "numpy" else None)
+    grid = tuple(int(v) for v in start_grid)
+    if len(grid) != 2 or grid[0] < 1 or grid[1] < 1 or grid[0] * grid[1] != int(n_starts):
+        raise ValueError(f"start_grid must be (n_years, n_days) with n_years * n_days = len(start_rows) = {n_starts}, got {start_grid!r}")
+    return rng, grid
 
 
 def _observation_modules(Np, names):       # TomatoVecEnv.__init__ has a keyword argument of the same name as the function
@@ -166,7 +182,8 @@ class TomatoVecEnv:
                  preset: Optional[str] = None,
                  observation_modules: Optional[Sequence[str]] = None, u_min: Optional[Sequence[float]] = None,
                  u_max: Optional[Sequence[float]] = None, delta_u_max: float = 0.1, integration_info: bool = True,
-                 integrator: str = "explicit", rtol: float = 1e-6, atol: float = 1e-6, max_steps: int = 10000):
+                 integrator: str = "explicit", rtol: float = 1e-6, atol: float = 1e-6, max_steps: int = 10000,
+                 rng: str = "philox", start_grid: Optional[Sequence[int]] = None, env_index_offset: int = 0):
         """u_min / u_max / delta_u_max: action_to_control's bounds (base_env.py:72-74; default [0, 1] and 0.1).
         observation_modules: names of the reference's modules in output order (default: the six of TomatoEnv.yml).
         scheme / n_sub / window: "ls5" (default; model_variant "ode_pipe" defaults to "rk4" and accepts no other: five-stage fourth-order 2N-storage scheme, n_sub 128, two sub-steps per tier-2b window), "rk4" (classical RK4, 240),
@@ -180,9 +197,18 @@ class TomatoVecEnv:
         integrator: "explicit" (default: the scheme / n_sub / window above) or "bdf" -- every env-step integrated by the adaptive,
         error-controlled variable-order BDF in fp64 at rtol / atol, at most max_steps steps per env-step (include/glgym.h
         glgym_set_step_integrator; the algorithm family of the reference's CVODES call); scheme, n_sub, window and preset stay stored and
-        apply again after set_integrator("explicit").  "bdf" does not combine with model_variant "ode_pipe"."""
+        apply again after set_integrator("explicit").  "bdf" does not combine with model_variant "ode_pipe".
+        rng: "philox" (default: counter-based draws keyed by (seed, env, draw counter)) or "numpy": every environment owns the NumPy
+        generator the reference's TomatoEnv owns, Generator(PCG64(SeedSequence(seed + env_index_offset + b))) (RL/utils.py:39: make_env seeds
+        environment `rank` with seed + rank), kept on the device (include/glgym.h glgym_rng_*) and drawn from in the reference's order: at a
+        reset choice(years), choice(days) (tomato_env.py:236-241), at every step 34 uniforms whether or not uncertainty_scale is 0
+        (tomato_env.py:118).  Start rows, start days and crop blocks then equal the reference's bit for bit.  A reset without a seed continues
+        the streams (gymnasium.Env.reset(seed=None)); reset_tensor(seed=s) / seed(s) / set_seed(s) reseed; get_rng_state / set_rng_state.
+        start_grid: (n_years, n_days) of the year-major start table (make_env.season_table), n_years * n_days = len(start_rows); default
+        (1, len(start_rows)).  env_index_offset: global index of this shard's first environment (rng="numpy" only)."""
         _check_integrator(integrator, model_variant)
         _check_tolerances(rtol, atol, max_steps)
+        _check_rng(rng, start_grid, 1 if start_rows is None else len(start_rows))
         torch = _torch()
         if not torch.cuda.is_available():
             raise L.GlgymError("TomatoVecEnv needs a HIP device (torch.cuda.is_available() is False); "
@@ -281,6 +307,8 @@ class TomatoVecEnv:
             raise ValueError("start_rows + episode length exceeds the weather tensor")
         self.start_days = np.asarray(start_days if start_days is not None
                                      else self.start_rows * self.dt / self.c, dtype=np.float32)
+        self.rng, self.start_grid = _check_rng(rng, start_grid, len(self.start_rows))
+        self.env_index_offset = int(env_index_offset)
 
         dev, T = self.device, self.tdtype
         z = lambda *s, dtype=T: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
@@ -306,6 +334,10 @@ class TomatoVecEnv:
         self._start_days_t = torch.as_tensor(self.start_days, dtype=torch.float32, device=dev)
         self.episode_t = z(self.B, dtype=torch.int32)           # episodes started per env (keys the start draw)
         self._draw = 0
+        # rng="numpy": the PCG64 streams, SoA uint64 [5][ld] (torch has no arithmetic on uint64: carried as int64, same bits)
+        self.rng_state_t = z(np_stream.NWORD, self.ld, dtype=torch.int64) if self.rng == "numpy" else None
+        if self.rng == "numpy":
+            self._seed_streams(self.seed_value)
         self.x, self.u = self.x_T[:, :self.B].t(), self.u_T[:, :self.B].t()      # [B,28] / [B,6] views
 
         # observation space = concatenation of the modules' bounds (tomato_env.py:83-95; the reference's lower bound
@@ -335,8 +367,43 @@ class TomatoVecEnv:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    # ---- rng="numpy": the reference's per-environment NumPy streams ------------------------------
+    def _seed_streams(self, seed: int):
+        """Environment b <- PCG64(SeedSequence(seed + env_index_offset + b)), seeded on the host (np_stream.seed_states) and uploaded."""
+        first = int(seed) + self.env_index_offset
+        self.set_rng_state(np_stream.seed_states(range(first, first + self.B)))
+
+    def get_rng_state(self) -> List[dict]:
+        """The streams as NumPy `bit_generator.state` dicts, one per environment (rng="numpy"): `np.random.PCG64().state = d` continues
+        environment b's stream on the host; set_rng_state(get_rng_state()) of an earlier moment restores it (checkpoints)."""
+        if self.rng_state_t is None:
+            raise L.GlgymError("get_rng_state: this environment was built with rng='philox' (stateless, keyed by seed and counters)")
+        return np_stream.unpack_states(self.rng_state_t[:, :self.B].cpu().numpy().view(np.uint64))
+
+    def set_rng_state(self, states):
+        """states: list of B PCG64 `bit_generator.state` dicts, or the packed uint64 [5, B] array of np_stream."""
+        if self.rng_state_t is None:
+            raise L.GlgymError("set_rng_state: this environment was built with rng='philox'")
+        words = states if isinstance(states, np.ndarray) else np_stream.pack_states(states)
+        if words.shape != (np_stream.NWORD, self.B):
+            raise ValueError(f"set_rng_state: expected {self.B} states, got an array of shape {words.shape}")
+        self.rng_state_t[:, :self.B].copy_(self.torch.as_tensor(np.ascontiguousarray(words, dtype=np.uint64).view(np.int64)))
+
     def _launch_reset(self, mask_t):
-        """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode))."""
+        """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).
+        rng="numpy": glgym_rng_reset_draw takes choice(years), choice(days) from each masked environment's stream first, and
+        glgym_reset, called without a start table, initialises from the w_off it wrote."""
+        mask_ptr = mask_t.data_ptr() if mask_t is not None else None
+        if self.rng == "numpy":
+            L.check(self._lib.glgym_rng_reset_draw(self._h, self.B, self.ld, mask_ptr, self.rng_state_t.data_ptr(), self.start_grid[0],
+                                                   self.start_grid[1], self._start_rows_t.data_ptr(), self._start_days_t.data_ptr(),
+                                                   self.w_off_t.data_ptr(), self.start_day_t.data_ptr(), self._stream()),
+                    "glgym_rng_reset_draw")
+            a = L.ResetArgs(self.B, self.ld, mask_ptr, self.x_T.data_ptr(), self.u_T.data_ptr(), self.timestep_t.data_ptr(),
+                            self.weather_t.data_ptr(), self.weather_rows, self.w_off_t.data_ptr(), None, None, 0,
+                            self.start_day_t.data_ptr(), self.episode_t.data_ptr(), self.seed_value)
+            L.check(self._lib.glgym_reset(self._h, C.byref(a), self._stream()), "glgym_reset")
+            return
         a = L.ResetArgs(self.B, self.ld, mask_t.data_ptr() if mask_t is not None else None, self.x_T.data_ptr(),
                         self.u_T.data_ptr(), self.timestep_t.data_ptr(), self.weather_t.data_ptr(), self.weather_rows,
                         self.w_off_t.data_ptr(), self._start_rows_t.data_ptr(), self._start_days_t.data_ptr(),
@@ -357,7 +424,12 @@ class TomatoVecEnv:
             warnings.warn("GLGYM_LAYOUT / GLGYM_OCC / GLGYM_VERIFY changed after this TomatoVecEnv was created: they are read once, at glgym_create, "
                           "and have no effect on an existing handle -- use set_layout() / set_occupancy() / set_verify()", RuntimeWarning, stacklevel=3)
             self._env_at_create = None                     # once
-        if self.crop_T is not None and not getattr(self, "freeze_crop_noise", False):       # noise.py: a fresh draw every step
+        if self.rng == "numpy":
+            if not getattr(self, "freeze_crop_noise", False):   # tomato_env.py:118: 34 draws every step, also at scale 0 (no block: streams advance)
+                L.check(self._lib.glgym_rng_crop_noise(self._h, self.crop_T.data_ptr() if self.crop_T is not None else None, self.B, self.ld,
+                                                       self.uncertainty_scale, self.rng_state_t.data_ptr(), self._stream()),
+                        "glgym_rng_crop_noise")
+        elif self.crop_T is not None and not getattr(self, "freeze_crop_noise", False):       # noise.py: a fresh draw every step
             L.check(self._lib.glgym_crop_noise(self._h, self.crop_T.data_ptr(), self.B, self.ld,
                                                self.uncertainty_scale, self.seed_value, self._draw, self._stream()),
                     "glgym_crop_noise")
@@ -376,6 +448,8 @@ class TomatoVecEnv:
         if seed is not None:
             self.seed_value = int(seed)
             self.episode_t.zero_()
+            if self.rng == "numpy":
+                self._seed_streams(self.seed_value)
         self._launch_reset(None)
         self._launch_obs(self.obs_t)
         return self.obs_t
@@ -432,6 +506,8 @@ class TomatoVecEnv:
     def seed(self, seed: Optional[int] = None):
         if seed is not None:
             self.seed_value = int(seed)
+            if self.rng == "numpy":
+                self._seed_streams(self.seed_value)
         return [seed] * self.B
 
     def step_async(self, actions):
@@ -530,6 +606,8 @@ class TomatoVecEnv:
         that draws the episode starts."""
         self.seed_value = int(seed)
         self.episode_t.zero_()
+        if self.rng == "numpy":
+            self._seed_streams(self.seed_value)
 
     # ---- clocks and the weather row of the coming step, as device tensors (for controllers) ---------
     def current_weather(self):
@@ -562,6 +640,8 @@ class TomatoVecEnv:
         self.start_days = np.asarray(self.start_days[:1], dtype=np.float32)
         self._start_rows_t = torch.as_tensor(self.start_rows, dtype=torch.int32, device=self.device)
         self._start_days_t = torch.as_tensor(self.start_days, dtype=torch.float32, device=self.device)
+        if self.rng == "numpy":
+            self.start_grid = (1, 1)        # one start left: choice() of one-element lists draws nothing
         self.w_off_t.zero_()
 
     @property
@@ -623,8 +703,9 @@ class TomatoVecEnv:
         HIP graph.  The library's device-pointer entry points never synchronise, so they can be stream-captured; one
         graph launch then replaces five kernel launches (about 2 % at B = 65 536, more when B is small).  Returns
         ``replay(actions_t) -> (obs, reward, done, info)`` with the same device tensors ``step_tensor`` returns.
-        Per-env crop noise (uncertainty_scale > 0) advances a host-side draw counter per step and is not capturable."""
-        if self.crop_T is not None:
+        Per-env crop noise (uncertainty_scale > 0) of rng="philox" advances a host-side draw counter per step and is not capturable;
+        with rng="numpy" the streams live on the device and the noise and start-draw launches are captured with the rest."""
+        if self.crop_T is not None and self.rng != "numpy":
             raise L.GlgymError("capture_step_graph: per-step crop noise carries a host-side draw counter; use step_tensor")
         torch = self.torch
         static_a = torch.zeros(self.B, L.NU, dtype=torch.float32, device=self.device)
@@ -641,24 +722,24 @@ class TomatoVecEnv:
                     self._launch_obs(self.obs_t, self.done_t, self.term_obs_t)
 
         # warm-up on a side stream (torch's capture protocol), with the state restored afterwards
-        keep = [b.clone() for b in (self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t,
-                                    self.obs_t)]
+        state = [self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t, self.obs_t]
+        if self.rng == "numpy":             # the warm-up draws from the streams: they go back to where they were
+            state += [self.rng_state_t] + ([self.crop_T] if self.crop_T is not None else [])
+        keep = [b.clone() for b in state]
         metrics = None if self.metrics_t is None else self.metrics_t.clone()
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             seq()
         torch.cuda.current_stream(self.device).wait_stream(side)
-        for b, k in zip((self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t, self.obs_t),
-                        keep):
+        for b, k in zip(state, keep):
             b.copy_(k)
         if metrics is not None:
             self.metrics_t.copy_(metrics)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             seq()
-        for b, k in zip((self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t, self.obs_t),
-                        keep):
+        for b, k in zip(state, keep):
             b.copy_(k)                      # capture does not execute, but keep the contract explicit
         if metrics is not None:
             self.metrics_t.copy_(metrics)
@@ -758,9 +839,11 @@ class TomatoEnv:
                  n_sub=None, device="cuda:0", uncertainty_scale=0.0, start_day=0.0, growth_year=2010,
                  reward_params=None, constraints=None, location="synthetic", training=True, model_variant="ode",
                  scheme="rk4", observation_modules=None, u_min=None, u_max=None, delta_u_max=0.1, integrator="explicit", rtol=1e-6,
-                 atol=1e-6, max_steps=10000):
-        """integrator / rtol / atol / max_steps: as TomatoVecEnv ("bdf": error-controlled BDF env-steps)."""
-        self.vec = TomatoVecEnv(1, model_variant=model_variant, scheme=scheme, observation_modules=observation_modules,
+                 atol=1e-6, max_steps=10000, rng="philox"):
+        """integrator / rtol / atol / max_steps: as TomatoVecEnv ("bdf": error-controlled BDF env-steps).
+        rng: "numpy" = the reference env's own generator: reset(seed=s) seeds Generator(PCG64(SeedSequence(s))), every step draws
+        its 34 uniforms from it (also at uncertainty_scale 0), reset() without a seed continues the stream."""
+        self.vec = TomatoVecEnv(1, rng=rng, model_variant=model_variant, scheme=scheme, observation_modules=observation_modules,
                                 u_min=u_min, u_max=u_max, delta_u_max=delta_u_max, integrator=integrator, rtol=rtol, atol=atol,
                                 max_steps=max_steps,
                                 weather=weather, params=params, dt=dt, season_length=season_length,

@@ -16,6 +16,8 @@ Semantics (Gymnasium's vector API):
     object arrays with ``None`` for running envs, and ``infos["final_info"]`` (a dict of arrays for the finished envs'
     last step = the values of this very step), with their ``_final_*`` masks = ``terminations``;
   * ``reset(seed=s)`` re-seeds the episode-start draws (env b uses stream (s, b)); ``options`` is accepted and ignored.
+    With ``rng="numpy"`` env b is reseeded as ``Generator(PCG64(SeedSequence(s + b)))``, the reference's stream of rank b, and a
+    ``reset()`` without a seed continues the streams.
 
 When ``gymnasium`` is importable the class derives from ``gymnasium.vector.VectorEnv`` and its spaces are gymnasium Boxes
 (``batch_space``); otherwise it is a plain class with the same attributes.  The device-tensor interface of the wrapped env
@@ -42,7 +44,8 @@ class TomatoVectorEnv(_Base):
     metadata = {"autoreset_mode": "same_step", "render_modes": []}
 
     def __init__(self, num_envs: int, **kwargs):
-        """kwargs: TomatoVecEnv's, e.g. integrator="bdf", rtol=1e-6, atol=1e-6, max_steps=10000 for error-controlled BDF env-steps."""
+        """kwargs: TomatoVecEnv's, e.g. integrator="bdf", rtol=1e-6, atol=1e-6, max_steps=10000 for error-controlled BDF env-steps,
+        rng="numpy", start_grid=(n_years, n_days) for the reference's seeded random stream."""
         kwargs.setdefault("auto_reset", True)
         if not kwargs["auto_reset"]:
             raise ValueError("the VectorEnv facade autoresets (same-step); use TomatoVecEnv for manual resets")

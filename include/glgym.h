@@ -21,6 +21,8 @@
  *   glgym_reset    <- TomatoEnv.reset (state part)               gl_gym/environments/tomato_env.py:262-266,
  *                     init_state                                  gl_gym/environments/utils.py:13-46
  *   glgym_crop_noise <- parametric_crop_uncertainty               gl_gym/environments/noise.py:3-23
+ *   glgym_rng_crop_noise / glgym_rng_reset_draw <- the same two draws from the environment's own NumPy generator
+ *                     (gymnasium seeding: Generator(PCG64(SeedSequence(seed)))), bit for bit: tomato_env.py:118, 236-241
  *   glgym_rule_based <- RuleBasedController.predict              gl_gym/environments/baseline.py:68-227
  *                     (constants gl_gym/configs/agents/rule_based.yml; caller experiments/evaluate_baseline.py:22)
  *   glgym_weather  <- load_weather_data (array part)              gl_gym/environments/utils.py:48-125
@@ -150,7 +152,7 @@ typedef struct {
 
 /* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
- * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF */
+ * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -341,6 +343,30 @@ int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream);
  * (seed, stream_id), counter (env index, draw_index).  crop_p: SoA [34][ld] T. */
 int glgym_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t seed, uint64_t draw_index,
                      void* stream);
+
+/* ---- the reference's seeded random stream on the device (csrc/gl_pcg64.hpp, csrc/glgym_rng.hip) -------------------------
+ * The reference's TomatoEnv draws everything random from one NumPy generator per environment, np_random(seed) =
+ * Generator(PCG64(SeedSequence(seed))) (gymnasium.utils.seeding; env `rank` of make_vec_env is seeded with seed + rank,
+ * gl_gym/RL/utils.py:39).  These two entry points make the same draws from the same streams, so that a seeded run walks the
+ * reference's episodes: same start days, same perturbed crop parameters, bit for bit.  Opt-in; glgym_crop_noise and glgym_reset's own
+ * start draw (Philox) are unchanged.
+ * rng_state: caller-owned device buffer, SoA uint64 [5][ld]: PCG64 state low / high word, increment low / high word, and NumPy's
+ * 32-bit buffer as has_uint32 << 32 | uinteger -- the fields of `bit_generator.state`, filled by the caller (seeding runs on the host).
+ * Asynchronous on `stream`, no host synchronisation (capturable).
+ *
+ * glgym_rng_crop_noise <- parametric_crop_uncertainty(self.p, self.uncertainty_scale, self._np_random) (noise.py:16-22, called at
+ *   tomato_env.py:118, 150 in EVERY step, also with scale 0): noise = uniform(-scale/2, scale/2, 34), i.e. lo + (hi - lo) *
+ *   (next_uint64 >> 11) * 2^-53; crop_p[i][b] = float32(double(p_i) + noise_i * double(p_i)) for p_i = float32(p[128+i]), product and
+ *   sum rounded separately; then p144 = p141 / p142 in float32.  crop_p: SoA [34][ld] T as glgym_step_args.crop_p reads it, or NULL:
+ *   the streams only advance by the 34 draws (the step then uses the handle's parameters, as with uncertainty_scale = 0).
+ * glgym_rng_reset_draw <- growth_year = choice(years); start_day = choice(days) (tomato_env.py:236-241): for every environment with
+ *   mask[b] != 0 (mask NULL: all) iy = bounded(n_years), id = bounded(n_days) -- Generator.choice of a list of n draws nothing for
+ *   n = 1 and otherwise one buffered 32-bit word through Lemire's rejection method -- and entry j = iy * n_days + id of the year-major
+ *   start table [n_years * n_days]: w_off[b] = start_rows[j], start_day[b] = start_days[j] (start_day / start_days may be NULL).
+ *   Call glgym_reset afterwards WITHOUT a start table (start_rows NULL): it initialises from w_off[b]. */
+int glgym_rng_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t* rng_state, void* stream);
+int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
+                         const int32_t* start_rows, const float* start_days, int32_t* w_off, float* start_day, void* stream);
 
 /* ---- rule-based controller (BASELINE config 1 "fixed rule-based actions") ------------------------------
  * u[6] = RuleBasedController.predict(x, weather[w_off + timestep], env clocks) for every env of the shard, written in the
