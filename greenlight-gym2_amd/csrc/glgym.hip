@@ -24,6 +24,7 @@
 #include "gl_reward.hpp"
 #include "glgym_bdf.h"
 #include "glgym_rng.h"
+#include "glgym_plan.h"
 
 using namespace glm;
 
@@ -2107,6 +2108,95 @@ int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mas
         return GLGYM_EINVAL;
     }
     HIPCHK(rng_reset_draw_launch(B, ld, mask, rng_state, n_years, n_days, start_rows, start_days, w_off, start_day, (hipStream_t)stream));
+    return GLGYM_OK;
+}
+
+// ---- device-side planning (glgym_plan.hip): host side only -- argument checks, and glgym_plan_rollout's loop over glgym_step ----
+static bool plan_size_ok(const char* who, int32_t got, size_t want)
+{
+    if (got == (int32_t)want) return true;
+    g_err = std::string(who) + ": struct_size is " + std::to_string(got) + ", this library expects " + std::to_string(want) +
+            " (ABI " + std::to_string(GLGYM_ABI_VERSION) + "): rebuild against include/glgym.h";
+    return false;
+}
+
+int glgym_plan_fork(glgym_handle h, const glgym_plan_fork_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_fork: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_fork", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->n_children < 1 || a->n_parents < 1 || a->ld_parent < a->n_parents || a->ld_child < a->n_children ||
+        (!a->parent && (a->K < 1 || (int64_t)a->n_parents * a->K < a->n_children)) ||
+        !a->x_parent || !a->u_parent || !a->timestep_parent || !a->w_off_parent || !a->x || !a->u || !a->timestep || !a->w_off ||
+        !a->ret || !a->viol || !a->n_steps || !a->alive || !a->failed) {
+        g_err = "glgym_plan_fork: bad arguments (null pointer, ld < batch, or without a parent table K < 1 or fewer than C = P * K slots)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->dtype == GLGYM_F32) HIPCHK(plan_fork_launch<float>(*a, st));
+    else HIPCHK(plan_fork_launch<double>(*a, st));
+    return GLGYM_OK;
+}
+
+int glgym_plan_accumulate(glgym_handle h, const glgym_plan_accumulate_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_accumulate: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_accumulate", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->B < 1 || a->ld < a->B || !a->reward || !a->info || !a->done || !a->ret || !a->viol || !a->n_steps || !a->alive || !a->failed) {
+        g_err = "glgym_plan_accumulate: bad arguments (null pointer or ld < B)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->dtype == GLGYM_F32) HIPCHK(plan_accumulate_launch<float>(*a, st));
+    else HIPCHK(plan_accumulate_launch<double>(*a, st));
+    return GLGYM_OK;
+}
+
+int glgym_plan_rollout(glgym_handle h, const glgym_plan_rollout_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_rollout: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_rollout", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->H < 1 || !(a->gamma >= 0.0) || !std::isfinite(a->gamma) || (!a->actions) == (!a->controls) || a->step.B < 1 ||
+        a->step.ld < a->step.B || !a->step.reward || !a->step.info || !a->step.done || !a->ret || !a->viol || !a->n_steps ||
+        !a->alive || !a->failed) {
+        g_err = "glgym_plan_rollout: bad arguments (H < 1, gamma, exactly one of actions / controls, ld >= B, non-null reward / info / done / accumulators)";
+        return GLGYM_EINVAL;
+    }
+    glgym_step_args s = a->step;                 // glgym_step checks its struct_size and the remaining members
+    s.metrics = nullptr;
+    glgym_plan_accumulate_args acc;
+    acc.struct_size = (int32_t)sizeof acc;
+    acc.B = s.B; acc.ld = s.ld; acc.reward = s.reward; acc.info = s.info; acc.done = s.done; acc.step_flags = s.step_flags;
+    acc.ret = a->ret; acc.viol = a->viol; acc.n_steps = a->n_steps; acc.alive = a->alive; acc.failed = a->failed;
+    const size_t plane = (size_t)NU * (size_t)s.ld * (h->dtype == GLGYM_F32 ? sizeof(float) : sizeof(double));
+    double w = 1.0;
+    for (int k = 0; k < a->H; ++k) {
+        s.action = a->actions ? a->actions + (size_t)k * (size_t)s.B * NU : nullptr;
+        s.control = a->controls ? (const void*)((const char*)a->controls + (size_t)k * plane) : nullptr;
+        const int rc = glgym_step(h, &s, stream);
+        if (rc != GLGYM_OK) return rc;
+        acc.w = w;
+        const int ra = glgym_plan_accumulate(h, &acc, stream);
+        if (ra != GLGYM_OK) return ra;
+        w = w * a->gamma;
+    }
+    return GLGYM_OK;
+}
+
+int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_select: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_select", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    const bool wants_actions = a->best_action || a->best_sequence || a->mean_sequence;
+    if (a->P < 1 || a->K < 1 || a->H < 1 || a->H > 65535 || (int64_t)a->P * a->K > INT32_MAX || !a->ret || !a->failed || !a->best_k ||
+        !a->best_ret || (wants_actions && !a->actions) || (a->mean_sequence && !(a->temperature > 0.0 && std::isfinite(a->temperature)))) {
+        g_err = "glgym_plan_select: bad arguments (P, K, H < 1, H > 65 535, null pointer, action outputs without actions, or mean_sequence "
+                "without a finite temperature > 0)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    HIPCHK(plan_select_launch(*a, (hipStream_t)stream));
     return GLGYM_OK;
 }
 

@@ -141,6 +141,40 @@ class VecNormArgs(C.Structure):
                 ("norm_reward", C.c_int32)]
 
 
+# device-side planning (include/glgym.h glgym_plan_*): every struct starts with struct_size; make_plan_args() fills it
+class PlanForkArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_children", C.c_int32), ("n_parents", C.c_int32), ("K", C.c_int32),
+                ("ld_parent", C.c_int32), ("ld_child", C.c_int32), ("parent", C.c_void_p), ("x_parent", C.c_void_p),
+                ("u_parent", C.c_void_p), ("timestep_parent", C.c_void_p), ("w_off_parent", C.c_void_p),
+                ("start_day_parent", C.c_void_p), ("crop_parent", C.c_void_p), ("x", C.c_void_p), ("u", C.c_void_p),
+                ("timestep", C.c_void_p), ("w_off", C.c_void_p), ("start_day", C.c_void_p), ("crop", C.c_void_p),
+                ("ret", C.c_void_p), ("viol", C.c_void_p), ("n_steps", C.c_void_p), ("alive", C.c_void_p), ("failed", C.c_void_p)]
+
+
+class PlanAccumulateArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("ld", C.c_int32), ("w", C.c_double), ("reward", C.c_void_p),
+                ("info", C.c_void_p), ("done", C.c_void_p), ("step_flags", C.c_void_p), ("ret", C.c_void_p), ("viol", C.c_void_p),
+                ("n_steps", C.c_void_p), ("alive", C.c_void_p), ("failed", C.c_void_p)]
+
+
+class PlanRolloutArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("H", C.c_int32), ("gamma", C.c_double), ("step", StepArgs), ("actions", C.c_void_p),
+                ("controls", C.c_void_p), ("ret", C.c_void_p), ("viol", C.c_void_p), ("n_steps", C.c_void_p), ("alive", C.c_void_p),
+                ("failed", C.c_void_p)]
+
+
+class PlanSelectArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("H", C.c_int32), ("ret", C.c_void_p),
+                ("failed", C.c_void_p), ("actions", C.c_void_p), ("best_k", C.c_void_p), ("best_ret", C.c_void_p),
+                ("best_action", C.c_void_p), ("best_sequence", C.c_void_p), ("temperature", C.c_double),
+                ("mean_sequence", C.c_void_p)]
+
+
+def make_plan_args(cls, *args, **kw):
+    """cls(...) of one of the Plan*Args structs without the leading struct_size, which is filled in here."""
+    return cls(C.sizeof(cls), *args, **kw)
+
+
 RULE_FIELDS = ("lamps_on", "lamps_off", "lamps_day_start", "lamps_day_stop", "lamps_off_sun", "lamp_rad_sum_limit",
                "temp_setpoint_day", "temp_setpoint_night", "heat_correction", "heat_deadzone", "co2_day",
                "vent_heat_Pband", "rh_max", "mech_dehumid_Pband", "vent_rh_Pband", "t_vent_off", "vent_cold_Pband",
@@ -202,6 +236,10 @@ PROTOTYPES = {
     "glgym_rng_crop_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "glgym_rng_reset_draw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "glgym_plan_fork": (C.c_int, [C.c_void_p, C.POINTER(PlanForkArgs), C.c_void_p]),
+    "glgym_plan_accumulate": (C.c_int, [C.c_void_p, C.POINTER(PlanAccumulateArgs), C.c_void_p]),
+    "glgym_plan_rollout": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutArgs), C.c_void_p]),
+    "glgym_plan_select": (C.c_int, [C.c_void_p, C.POINTER(PlanSelectArgs), C.c_void_p]),
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),

@@ -389,6 +389,44 @@ class TomatoVecEnv:
             raise ValueError(f"set_rng_state: expected {self.B} states, got an array of shape {words.shape}")
         self.rng_state_t[:, :self.B].copy_(self.torch.as_tensor(np.ascontiguousarray(words, dtype=np.uint64).view(np.int64)))
 
+    # ---- snapshots and planning -------------------------------------------------------------------
+    _STATE_TENSORS = ("x_T", "u_T", "timestep_t", "w_off_t", "start_day_t", "episode_t", "crop_T", "rng_state_t", "obs_t", "done_t")
+
+    def get_state(self) -> Dict[str, Any]:
+        """Snapshot of everything the next step_tensor depends on: clones of the device tensors x_T, u_T, timestep_t, w_off_t,
+        start_day_t, episode_t, crop_T (None at uncertainty_scale 0), rng_state_t (None with rng="philox"), obs_t, done_t, plus the
+        host scalars _draw (Philox draw counter) and seed_value, and the shape / dtype / rng mode set_state checks.  The reference has no
+        counterpart.  set_state(get_state()) of an earlier moment makes the environment repeat what it did from there, bit for bit."""
+        state: Dict[str, Any] = {k: (None if getattr(self, k) is None else getattr(self, k).clone()) for k in self._STATE_TENSORS}
+        state.update(_draw=int(self._draw), seed_value=int(self.seed_value), num_envs=self.B, dtype=str(self.tdtype), rng=self.rng)
+        return state
+
+    def set_state(self, state: Dict[str, Any]):
+        """Restore a get_state() snapshot.  A snapshot of an environment of another batch size, dtype, rng mode or crop-noise setting
+        raises ValueError and changes nothing."""
+        missing = [k for k in self._STATE_TENSORS + ("_draw", "seed_value", "num_envs", "dtype", "rng") if k not in state]
+        if missing:
+            raise ValueError(f"set_state: not a get_state() snapshot (missing {missing})")
+        if state["num_envs"] != self.B or state["dtype"] != str(self.tdtype) or state["rng"] != self.rng:
+            raise ValueError(f"set_state: snapshot of {state['num_envs']} envs, {state['dtype']}, rng={state['rng']!r} does not fit "
+                             f"this environment ({self.B} envs, {self.tdtype}, rng={self.rng!r})")
+        for k in self._STATE_TENSORS:
+            mine, theirs = getattr(self, k), state[k]
+            if (mine is None) != (theirs is None) or (mine is not None and (mine.shape != theirs.shape or mine.dtype != theirs.dtype)):
+                raise ValueError(f"set_state: {k} of the snapshot does not fit this environment")
+        for k in self._STATE_TENSORS:
+            if getattr(self, k) is not None:
+                getattr(self, k).copy_(state[k])
+        self._draw, self.seed_value = int(state["_draw"]), int(state["seed_value"])
+
+    def planner(self, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal"):
+        """A gl_gym_amd.planner.Planner for this environment: n_candidates control sequences per environment, simulated over `horizon`
+        env-steps on forked copies (buffers allocated once, here), scored and selected on the device.  crop="current" forks this
+        environment's per-env crop block (uncertainty_scale > 0) and holds it over the horizon; "nominal" plans with the handle's
+        parameters."""
+        from .planner import Planner
+        return Planner(self, n_candidates, horizon, gamma=gamma, crop=crop)
+
     def _launch_reset(self, mask_t):
         """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).
         rng="numpy": glgym_rng_reset_draw takes choice(years), choice(days) from each masked environment's stream first, and
@@ -903,6 +941,14 @@ class TomatoEnv:
     def set_crop_state(self, cBuf, cLeaf, cStem, cFruit, tCanSum):
         for i, v in zip((22, 23, 24, 25, 26), (cBuf, cLeaf, cStem, cFruit, tCanSum)):
             self.vec.x_T[i, 0] = v
+
+    def get_state(self):
+        """TomatoVecEnv.get_state of the wrapped environment, plus this view's `terminated`."""
+        return dict(self.vec.get_state(), terminated=self.terminated)
+
+    def set_state(self, state):
+        self.vec.set_state(state)
+        self.terminated = bool(state.get("terminated", False))
 
     def get_obs_names(self):
         return self.vec.get_obs_names()

@@ -121,6 +121,13 @@ class TomatoVectorEnv(_Base):
     def set_attr(self, name: str, values):
         self.venv.set_attr(name, values)
 
+    def get_state(self):
+        """Snapshot of the wrapped environment (TomatoVecEnv.get_state); set_state restores it."""
+        return self.venv.get_state()
+
+    def set_state(self, state):
+        self.venv.set_state(state)
+
     @property
     def unwrapped(self):
         return self

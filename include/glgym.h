@@ -152,7 +152,8 @@ typedef struct {
 
 /* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
- * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw */
+ * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
+ * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -367,6 +368,106 @@ int glgym_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, 
 int glgym_rng_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t* rng_state, void* stream);
 int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
                          const int32_t* start_rows, const float* start_days, int32_t* w_off, float* start_day, void* stream);
+
+/* ---- device-side planning: fork, horizon rollouts, selection (csrc/gl_plan.hpp, csrc/glgym_plan.hip) ------------------------
+ * Sampling-based MPC (random shooting, MPPI) on the device: from the current state of each of P parent environments, K candidate
+ * control sequences are simulated over H env-steps on COPIES of the parent (children, C = P * K of them, in caller-owned buffers of
+ * their own leading dimension), scored by their discounted return, and the best is picked per parent.  The parents' buffers are only
+ * read.  The reference has no counterpart (its README lists MPC as a next step).  Every args struct starts with struct_size and is
+ * refused (GLGYM_EINVAL) on a mismatch, like glgym_step_args.  Asynchronous on `stream`, no host synchronisation, no allocation
+ * (capturable).  Opt-in: no other entry point changes.
+ *
+ * Child accumulators, all caller-owned device arrays indexed by child: ret double [C] (discounted return), viol double SoA [3][ld]
+ * (sums of co2 / temp / rh violation: info rows 8, 7, 9), n_steps int32 [C], alive uint8 [C] (1 until the step that reports done),
+ * failed uint8 [C] (a step carried GLGYM_SF_FAILED). */
+typedef struct {
+    int32_t struct_size;
+    int32_t n_children;          /* C */
+    int32_t n_parents;           /* P */
+    int32_t K;                   /* parent == NULL: the parent of child c is c / K (needs C <= P * K) */
+    int32_t ld_parent, ld_child; /* leading dimensions of the parent / child SoA arrays (>= P / >= C) */
+    const int32_t* parent;       /* [C] parent index per child, or NULL.  A child whose index is outside 0..P-1 copies parent 0 and
+                                    starts with alive = 0, failed = 1 */
+    const void* x_parent;        /* SoA [28][ld_parent] T */
+    const void* u_parent;        /* SoA [6][ld_parent] T */
+    const int32_t* timestep_parent;   /* [P] */
+    const int32_t* w_off_parent;      /* [P] */
+    const float* start_day_parent;    /* [P] or NULL (then start_day is not written) */
+    const void* crop_parent;     /* SoA [34][ld_parent] T or NULL (then crop is not written) */
+    void* x;                     /* SoA [28][ld_child] T out */
+    void* u;                     /* SoA [6][ld_child] T out */
+    int32_t* timestep;           /* [C] out */
+    int32_t* w_off;              /* [C] out */
+    float* start_day;            /* [C] out or NULL */
+    void* crop;                  /* SoA [34][ld_child] T out or NULL */
+    double* ret;                 /* [C] out: 0 */
+    double* viol;                /* SoA [3][ld_child] out: 0 */
+    int32_t* n_steps;            /* [C] out: 0 */
+    uint8_t* alive;              /* [C] out: 1 */
+    uint8_t* failed;             /* [C] out: 0 */
+} glgym_plan_fork_args;
+
+/* After ONE glgym_step on the children: for every child that was alive BEFORE that step, ret += w * (double)reward (product and sum
+ * rounded separately), viol += (double)info rows 8, 7, 9, n_steps += 1, failed |= step_flags & GLGYM_SF_FAILED, alive &= !done.  The
+ * step that reports done is counted and nothing after it (the reference's episode of N + 1 steps). */
+typedef struct {
+    int32_t struct_size;
+    int32_t B, ld;               /* children, leading dimension of info / viol (reward is [ld]) */
+    double w;                    /* weight of this step's reward (gamma^k) */
+    const void* reward;          /* [ld] T: glgym_step_args.reward */
+    const void* info;            /* SoA [11][ld] T: glgym_step_args.info */
+    const uint8_t* done;         /* [B]: glgym_step_args.done */
+    const int32_t* step_flags;   /* [B]: glgym_step_args.step_flags, or NULL (failed is then left alone) */
+    double* ret;
+    double* viol;
+    int32_t* n_steps;
+    uint8_t* alive;
+    uint8_t* failed;
+} glgym_plan_accumulate_args;
+
+/* H env-steps of the children in one call: for k = 0 .. H-1 glgym_step(step with the action / control of step k, metrics = NULL),
+ * then glgym_plan_accumulate with w_0 = 1, w_{k+1} = w_k * gamma (a running product in double).  The handle's settings apply as
+ * they do to glgym_step (parameters, reward, scheme, n_sub, verify mode, explicit or BDF step integrator, GLGYM_ODE_PIPE with raw
+ * controls); the handle's metric accumulators are not touched.  No reset and no noise draw happens: a child past its season end keeps
+ * stepping on weather rows clamped to the table and is ignored through alive.  Exactly one of actions / controls is non-null. */
+typedef struct {
+    int32_t struct_size;
+    int32_t H;                   /* env-steps (>= 1) */
+    double gamma;                /* discount factor (finite, >= 0) */
+    glgym_step_args step;        /* the children's buffers; reward, info, done are required, step_flags may be NULL;
+                                    step.action, step.control and step.metrics are ignored (set per step / NULL) */
+    const float* actions;        /* [H][B][6] row-major f32: step k takes actions + k*B*6 (action path) */
+    const void* controls;        /* [H] planes of SoA [6][ld] T: step k takes its plane (raw controls) */
+    double* ret;                 /* accumulators as initialised by glgym_plan_fork */
+    double* viol;
+    int32_t* n_steps;
+    uint8_t* alive;
+    uint8_t* failed;
+} glgym_plan_rollout_args;
+
+/* One wavefront per parent over its K children.  best_k[p] = argmax of ret over the candidates that have not failed and whose ret is
+ * finite, ties to the lowest k; best_ret[p] its return.  A parent without such a candidate gets best_k = -1, best_ret = NaN and
+ * zeros (the action that holds the controls) in best_action / best_sequence / mean_sequence.  temperature > 0 with mean_sequence:
+ * the MPPI mean, w_k = exp((ret_k - max) / temperature) over the same candidates, normalised; mean_sequence[h][p][j] =
+ * sum_k w_k * actions[h][p*K + k][j], accumulated in double, stored f32. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, H;
+    const double* ret;           /* [P*K] */
+    const uint8_t* failed;       /* [P*K] */
+    const float* actions;        /* [H][P*K][6] f32, or NULL when none of the three action outputs is asked for */
+    int32_t* best_k;             /* [P] out */
+    double* best_ret;            /* [P] out */
+    float* best_action;          /* [P][6] out = actions[0][p*K + best_k], or NULL */
+    float* best_sequence;        /* [H][P][6] out or NULL */
+    double temperature;          /* > 0 with mean_sequence; ignored otherwise */
+    float* mean_sequence;        /* [H][P][6] out or NULL */
+} glgym_plan_select_args;
+
+int glgym_plan_fork(glgym_handle h, const glgym_plan_fork_args* a, void* stream);
+int glgym_plan_accumulate(glgym_handle h, const glgym_plan_accumulate_args* a, void* stream);
+int glgym_plan_rollout(glgym_handle h, const glgym_plan_rollout_args* a, void* stream);
+int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* stream);
 
 /* ---- rule-based controller (BASELINE config 1 "fixed rule-based actions") ------------------------------
  * u[6] = RuleBasedController.predict(x, weather[w_off + timestep], env clocks) for every env of the shard, written in the
