@@ -4,6 +4,7 @@
 //   step_kernel   fused TomatoEnv.step(): action->control, weather-row gather, tier-2 precompute,
 //                 n_sub x RK4 of the GreenLight ODE (gl_model.hpp), failure check, reward / violation /
 //                 info epilogue, terminal test, wave-level metric reduction.   [VALU/transcendental bound]
+//                 OBS builds (glgym_step_obs): the same, and each wavefront then also writes the observation rows of its 64 environments.
 //   obs_kernel    row-major observation assembly incl. the weather-forecast gather.      [HBM-write bound]
 //   reset_kernel  masked init_state().        crop_noise_kernel  Philox4x32-10 parameter noise.
 //   evalf_kernel / rhs_kernel                 row-major double I/O for the reference-compatible evalF and tests.
@@ -96,6 +97,67 @@ template <class T> __device__ __forceinline__ T wave_sum(T v)
 }
 
 // ---------------------------------------------------------------------------------------------------
+// the 23 core observation features (observations.py:70-161), shared by obs_kernel and the observation epilogue of step_kernel
+// ---------------------------------------------------------------------------------------------------
+// j: 0 co2_ppm(x0,x2) 1 x2 2 RH(x15,x2) 3 x9 | 4 x21 5 x25 6 x26 | 7..12 u | 13 d0 14 d1 15 RH(d2,d1)
+//    16 co2_ppm(d3,d1) 17 d4 | 18 timestep 19..22 sin/cos clocks
+// prim: the feature's own input (x, u or weather column; unused from j = 18), aux: tAir (j < 13) or tOut.  ts: the env's timestep AFTER
+// the step's increment; the row / "timestep" the reference shows is the pre-increment one, k = ts - 1 (0 for a freshly reset env).
+// Straight-line selects: with a run-time j (obs_kernel) no branch per feature, with a compile-time j (step_kernel) everything but the
+// feature's own arithmetic folds away.  ONE definition, so that both kernels produce the same bits.
+constexpr int OBS_NCORE = 23;
+__device__ __forceinline__ float obs_core_feature(int j, float prim, float aux, float sday, int ts, double doy_inc, double hod_inc)
+{
+    // No implicit contraction in here: which products the compiler fuses into a following add depends on the caller -- with a
+    // compile-time j it turned rev - floor(rev) into fma(t, c, -floor(t * c)), which is not 0 where rev is a whole number (step 96 of
+    // an episode), with a run-time j it did not.  The one fused operation obs_kernel has always had is written out.
+#pragma clang fp contract(off)
+    const float kPpm = (float)(8.3144598 / (101325.0 * 44.01e-3));
+    const int k = ts > 0 ? ts - 1 : 0;
+    // fp32 hardware transcendentals: the observation block is float32 (observation_space dtype)
+    const float sat = 610.78f * __builtin_amdgcn_exp2f(1.44269504f * 17.2694f * aux * __builtin_amdgcn_rcpf(aux + 238.3f));
+    const float rh = fminf(fmaxf(100.0f * prim * __builtin_amdgcn_rcpf(sat), 0.0f), 100.0f);
+    const float ppm = kPpm * (aux + 273.15f) * prim;
+    // v_sin_f32 / v_cos_f32 take revolutions: sin(2*pi*x)   (tomato_env.py:126-128)
+    const int c = j - 18;
+    const double rev = (c <= 2) ? __builtin_fma((double)ts, doy_inc, (double)sday) * (1.0 / 365.0)
+                                : (double)ts * hod_inc * (1.0 / 24.0);
+    const float fr = (float)(rev - floor(rev));
+    const float clk = (c == 1 || c == 3) ? __builtin_amdgcn_sinf(fr) : __builtin_amdgcn_cosf(fr);
+    float v = prim;
+    v = (j == 0 || j == 16) ? ppm : v;
+    v = (j == 2 || j == 15) ? rh : v;
+    v = (j == 18) ? (float)k : v;
+    v = (j > 18) ? clk : v;
+    return v;
+}
+// module (GLGYM_OBS_*) and column inside it of core feature j
+__device__ __forceinline__ constexpr int obs_core_module(int j) { return j < 4 ? 0 : j < 7 ? 1 : j < 13 ? 2 : j < 18 ? 3 : 4; }
+__device__ __forceinline__ constexpr int obs_core_col(int j) { return j < 4 ? j : j < 7 ? j - 4 : j < 13 ? j - 7 : j < 18 ? j - 13 : j - 18; }
+
+#ifndef GL_OBS_ROWS
+#define GL_OBS_ROWS 16
+#endif
+constexpr int OBS_ROWS = GL_OBS_ROWS, OBS_MAX_NP = 128;     // obs_kernel's LDS span = rows * (23 + 5 Np) floats <= 42 KB
+// what step_kernel's OBS build needs beyond StepArgsT to write the observation rows of its 64 environments (obs_kernel's arguments
+// that the step does not have already)
+struct StepObsArgs {
+    float* obs; const float* start_day;
+    double doy_inc, hod_inc;
+    int Np, dim, moff[6];
+};
+// widest row the epilogue can stage.  Two-waves build: what its window buffer (64 x 73 floats) holds of OBS_ROWS rows, 292 columns.
+// One-wave build: a static area of its own, 512 columns = 32 KB, 37 - 38 KB per workgroup with everything else: the four workgroups of
+// a CU (one wavefront per SIMD) fit its 160 KB.  NOT less: the compiler keeps the integrator's small per-window arrays in LDS only
+// while that does not lower the occupancy tier which the kernel's LDS use already implies; with a 18.7 KB or a 24 KB area (tiers of
+// eight and six workgroups per CU) it sent them to scratch instead, inside the window loop (profiles/step_obs_fusion.txt).
+constexpr int STEP_OBS_MAX_DIM_OCC2 = WAVE * ((2 * NX + GL_N_SLOW) | 1) / OBS_ROWS, STEP_OBS_MAX_DIM_OCC1 = 512;
+struct StepNoObs {};
+constexpr int GL_SCH_OBS = 8;          // step_kernel's scheme argument: | GL_SCH_OBS = the build with the observation epilogue
+template <bool OBS> struct StepObsSel { using type = StepNoObs; };
+template <> struct StepObsSel<true> { using type = StepObsArgs; };
+
+// ---------------------------------------------------------------------------------------------------
 // fused env-step
 // ---------------------------------------------------------------------------------------------------
 // DEFAULT_P = true: the handle's parameter block is bit-identical to the default one, so every tier-1 constant is a
@@ -136,16 +198,26 @@ template <class T, int SCH> struct SchemeWin { static constexpr int value = SCH 
 // slots' differences; x0 is re-read after the integrator) lives in LDS, 73 floats per lane = eight wavefronts per CU
 // (rk_delta<WBUF>); 208 B of scratch are left and stay in the L2: 1.06x at B = 131 072, 1.08x at 262 144, 1.11x from 524 288 --
 // the build batches of two or more wavefronts per SIMD take (launch_step).
-template <class T, bool PER_ENV_CROP, bool DEFAULT_P, bool PIPE = false, int SCH = 0, int OCC = GL_STEP_WAVES_PER_SIMD>
-__global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelConst<T> m_arg, RewardConst<T> rw)
+// OBS = true (glgym_step_obs): after its stores, each wavefront also writes the observation rows of its own 64 environments -- what
+// obs_kernel in full mode would write after the launch -- from the values its lanes hold, so that the rows of all but the slowest
+// wavefront are written while the launch waits for that one anyway.  A template argument, not a run-time branch: the build that runs
+// when no observation is asked for is the kernel it was (registers, scratch, the sub-step loop).
+// It rides on the scheme argument -- SCHX = GLGYM_SCHEME_* | GL_SCH_OBS -- so that the plain builds keep the names they have always had
+// (step_kernel<float, false, true, false, 3, 1> in every profile on record; tests/test_capi_surface.py finds its kernels by that prefix).
+template <class T, bool PER_ENV_CROP, bool DEFAULT_P, bool PIPE = false, int SCHX = 0, int OCC = GL_STEP_WAVES_PER_SIMD>
+__global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelConst<T> m_arg, RewardConst<T> rw,
+                                                         typename StepObsSel<(SCHX & GL_SCH_OBS) != 0>::type o)
 {
+    constexpr bool OBS = (SCHX & GL_SCH_OBS) != 0;
+    constexpr int SCH = SCHX & (GL_SCH_OBS - 1);
+    static_assert(!OBS || (sizeof(T) == 4 && !PIPE), "observation epilogue: fp32, default ODE");
     const ModelConst<T>& m = DEFAULT_P ? device_default<T>() : m_arg;
     // OCC = 2 (round 5): what the windows read once each -- z0, the increments del, the slow slots' window differences -- lives in LDS,
     // WSTRIDE floats per lane (odd: conflict-free), 19.2 KB per wavefront = eight wavefronts per CU; the action tile of the prologue
     // shares the storage (it is consumed before the integrator starts).  gl_model.hpp rk_delta<WBUF>.
     constexpr bool WBUF = OCC == 2;
     constexpr int WSTRIDE = (2 * NX + GL_N_SLOW) | 1;
-    __shared__ float sh_w[WBUF ? WAVE * WSTRIDE : WAVE * NU];
+    alignas(16) __shared__ float sh_w[WBUF ? WAVE * WSTRIDE : WAVE * NU];      // (the alignment the compiler gives it anyway; OBS reads it back with 16-byte loads)
     float* sh_act = sh_w;
     const int lane = threadIdx.x;
     const int b0 = blockIdx.x * WAVE;
@@ -283,6 +355,84 @@ __global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelCo
         for (int i = 0; i < GLGYM_NMETRIC; ++i) {
             const float sum = wave_sum(mv[i]);
             if (lane == 0) atomicAdd(mrep + i, sum);
+        }
+    }
+    if constexpr (OBS) {
+        // ---- observation epilogue: rows b0 .. b0 + 63 of the row-major block, obs_kernel's full mode for this wavefront's environments.
+        // Every lane computes the 23 core features of its own row from the registers it has just stored (x1; the control and the
+        // weather row, which did not stay live across the integrator, are re-read by the lane that wrote / gathered them); the rows are
+        // assembled OBS_ROWS at a time in LDS with obs_kernel's span layout -- the two-waves build in its window buffer, which is dead
+        // here -- the forecast elements gathered from the L2-resident table, one element of all 16 rows per lane and pass, and the span
+        // streamed out with 16-byte non-temporal stores ((b0 + 16 s) * dim * 4 bytes is a multiple of 64).
+        typedef float v4f __attribute__((ext_vector_type(4)));
+        float* span;
+        if constexpr (WBUF) {
+            span = sh_w;
+        } else {
+            __shared__ float4 sh_obs4[OBS_ROWS * STEP_OBS_MAX_DIM_OCC1 / 4];      // static, and this size: see STEP_OBS_MAX_DIM_OCC1
+            span = reinterpret_cast<float*>(sh_obs4);
+        }
+        const int dim = o.dim;
+        const int ts1 = ts + 1;                             // what the step has stored: obs_kernel's `ts`
+        const int base = a.w_off[bb] + (ts1 > 0 ? ts1 - 1 : 0);
+        const int basec = base >= a.weather_rows ? a.weather_rows - 1 : (base < 0 ? 0 : base);
+        const T* wrow = a.weather + (size_t)basec * a.nd;
+        float wv[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) wv[j] = wrow[j];
+        const float sday = o.start_day[bb];
+        const float uo[NU] = {uBoil, uCo2, a.u[(size_t)2 * a.ld + bb], a.u[(size_t)3 * a.ld + bb], uLamp, a.u[(size_t)5 * a.ld + bb]};
+        float f[OBS_NCORE];
+#pragma unroll
+        for (int j = 0; j < OBS_NCORE; ++j) {
+            const int xi = j == 0 ? 0 : j == 1 ? 2 : j == 2 ? 15 : j == 3 ? 9 : j == 4 ? 21 : j == 5 ? 25 : 26;
+            const float prim = j < 7 ? x1[xi] : (j < 13 ? uo[(j >= 7 && j < 13) ? j - 7 : 0] : wv[j < 18 ? j - 13 : 0]);
+            const float aux = j < 13 ? x1[2] : wv[1];
+            f[j] = obs_core_feature(j, prim, aux, sday, ts1, o.doy_inc, o.hod_inc);
+        }
+        const int n_live = min(WAVE, a.B - b0);
+        const int nf = o.moff[5] >= 0 ? 5 * o.Np : 0;
+        __syncthreads();                                    // the window buffer's last reader (del) is done
+        for (int s0 = 0; s0 < n_live; s0 += OBS_ROWS) {     // wave-uniform
+            const int nrows = min(OBS_ROWS, n_live - s0);
+            const int r_me = lane - s0;
+            if (r_me >= 0 && r_me < nrows) {
+#pragma unroll
+                for (int j = 0; j < OBS_NCORE; ++j) {
+                    const int mo = o.moff[obs_core_module(j)];
+                    if (mo >= 0) span[r_me * dim + mo + obs_core_col(j)] = f[j];
+                }
+            }
+            // first weather row of each of the strip's windows, unclamped as in obs_kernel (rows past the last live one repeat it:
+            // dead lanes shadow environment B - 1)
+            int base_r[OBS_ROWS];
+#pragma unroll
+            for (int r = 0; r < OBS_ROWS; ++r) base_r[r] = __builtin_amdgcn_readlane(base, s0 + r);
+            for (int q = lane; q < nf; q += WAVE) {
+                const int i = q / 5, c = q - i * 5;
+                float v[OBS_ROWS];
+#pragma unroll
+                for (int r = 0; r < OBS_ROWS; ++r) {
+                    int row = base_r[r] + 1 + i;
+                    row = row >= a.weather_rows ? a.weather_rows - 1 : (row < 0 ? 0 : row);
+                    v[r] = (float)a.weather[(size_t)row * a.nd + c];
+                }
+#pragma unroll
+                for (int r = 0; r < OBS_ROWS; ++r)
+                    if (r < nrows) span[r * dim + o.moff[5] + q] = v[r];
+            }
+            __syncthreads();
+            float* out = o.obs + (size_t)(b0 + s0) * dim;
+            if (nrows == OBS_ROWS) {
+                const int n4 = (OBS_ROWS * dim) >> 2;
+                const v4f* src4 = reinterpret_cast<const v4f*>(span);
+                v4f* dst4 = reinterpret_cast<v4f*>(out);
+                for (int e = lane; e < n4; e += WAVE) __builtin_nontemporal_store(src4[e], &dst4[e]);
+            } else {                                        // ragged tail of the batch: row-wise, as obs_kernel
+                for (int r = 0; r < nrows; ++r)
+                    for (int jj = lane; jj < dim; jj += WAVE) out[(size_t)r * dim + jj] = span[(size_t)r * dim + jj];
+            }
+            __syncthreads();
         }
     }
 }
@@ -701,10 +851,6 @@ template <class T> struct ObsArgsT {
 // -> 26 (branch-free features) -> 24 us (16 rows per block) = 2.9 TB/s written; a plain fill of the buffer takes 11.6 us.
 // Masked mode (auto-reset) copies only the finished rows, after saving their previous content as SB3's
 // terminal_observation.
-#ifndef GL_OBS_ROWS
-#define GL_OBS_ROWS 16
-#endif
-constexpr int OBS_ROWS = GL_OBS_ROWS, OBS_NCORE = 23, OBS_MAX_NP = 128;     // LDS span = rows * (23 + 5 Np) floats <= 42 KB
 template <class T> __global__ __launch_bounds__(256) void obs_kernel(ObsArgsT<T> a)
 {
     constexpr int ROWS = OBS_ROWS, NCORE = OBS_NCORE;
@@ -712,7 +858,6 @@ template <class T> __global__ __launch_bounds__(256) void obs_kernel(ObsArgsT<T>
     float* span = reinterpret_cast<float*>(span4);
     const int tid = threadIdx.x;
     const int dim = a.dim;
-    const float kPpm = (float)(8.3144598 / (101325.0 * 44.01e-3));
     for (int rb = blockIdx.x * ROWS; rb < a.B; rb += gridDim.x * ROWS) {
         const int nrows = min(ROWS, a.B - rb);
         if (a.mask) {                                 // masked mode: skip strips without a finished env
@@ -735,34 +880,18 @@ template <class T> __global__ __launch_bounds__(256) void obs_kernel(ObsArgsT<T>
             const int r = e / NCORE, j = e - r * NCORE;
             const int b = rb + (r < nrows ? r : 0);
             const int ts = a.timestep[b];
-            const int k = ts > 0 ? ts - 1 : 0;
             int base = 0;
 #pragma unroll
             for (int rr = 0; rr < ROWS; ++rr) base = (rr == r) ? base_r[rr] : base;
             base = base >= a.weather_rows ? a.weather_rows - 1 : (base < 0 ? 0 : base);
             const T* wrow = a.weather + (size_t)base * a.nd;
-            // j: 0 co2_ppm(x0,x2) 1 x2 2 RH(x15,x2) 3 x9 | 4 x21 5 x25 6 x26 | 7..12 u | 13 d0 14 d1 15 RH(d2,d1)
-            //    16 co2_ppm(d3,d1) 17 d4 | 18 timestep 19..22 sin/cos clocks      (observations.py:70-161)
+            // (the features and their inputs: obs_core_feature)
             const int xi = j == 0 ? 0 : j == 1 ? 2 : j == 2 ? 15 : j == 3 ? 9 : j == 4 ? 21 : j == 5 ? 25 : 26;
             const T* p1 = j < 7 ? a.x + (size_t)xi * a.ld + b
                                 : (j < 13 ? a.u + (size_t)(j - 7) * a.ld + b : wrow + (j < 18 ? j - 13 : 0));
             const T* p2 = j < 13 ? a.x + (size_t)2 * a.ld + b : wrow + 1;        // tAir or tOut
             const float prim = (float)*p1, aux = (float)*p2, sday = a.start_day[b];
-            // fp32 hardware transcendentals: the observation block is float32 (observation_space dtype)
-            const float sat = 610.78f * __builtin_amdgcn_exp2f(1.44269504f * 17.2694f * aux * __builtin_amdgcn_rcpf(aux + 238.3f));
-            const float rh = fminf(fmaxf(100.0f * prim * __builtin_amdgcn_rcpf(sat), 0.0f), 100.0f);
-            const float ppm = kPpm * (aux + 273.15f) * prim;
-            // v_sin_f32 / v_cos_f32 take revolutions: sin(2*pi*x)   (tomato_env.py:126-128)
-            const int c = j - 18;
-            const double rev = (c <= 2) ? ((double)sday + (double)ts * a.doy_inc) * (1.0 / 365.0)
-                                        : (double)ts * a.hod_inc * (1.0 / 24.0);
-            const float fr = (float)(rev - floor(rev));
-            const float clk = (c == 1 || c == 3) ? __builtin_amdgcn_sinf(fr) : __builtin_amdgcn_cosf(fr);
-            float v = prim;
-            v = (j == 0 || j == 16) ? ppm : v;
-            v = (j == 2 || j == 15) ? rh : v;
-            v = (j == 18) ? (float)k : v;
-            v = (j > 18) ? clk : v;
+            const float v = obs_core_feature(j, prim, aux, sday, ts, a.doy_inc, a.hod_inc);
             // column of feature j in the configured module order (TomatoEnv._get_obs concatenates the modules in
             // the order of the yml list, tomato_env.py:193-198)
             const int mo = j < 4 ? a.moff[0] : j < 7 ? a.moff[1] : j < 13 ? a.moff[2] : j < 18 ? a.moff[3] : a.moff[4];
@@ -1735,22 +1864,50 @@ int glgym_rhs(glgym_handle h, const double* x, const double* u, const double* d,
 }  // extern "C"
 
 // ---- device-pointer hot path ----------------------------------------------------------------------
+static const int OBS_MODULE_SIZE[6] = {4, 3, 6, 5, 5, 0};      // observations.py:64,84,102,123,143; forecast = 5 * Np (:168)
+// first column of each observation module in the handle's module order (-1 = absent) and the row width
+static void obs_layout(glgym_handle h, int Np, int moff[6], int* dim)
+{
+    for (int m = 0; m < 6; ++m) moff[m] = -1;
+    *dim = 0;
+    for (int i = 0; i < h->n_obs_modules; ++i) {
+        const int m = h->obs_modules[i];
+        moff[m] = *dim;
+        *dim += m == GLGYM_OBS_FORECAST ? 5 * Np : OBS_MODULE_SIZE[m];
+    }
+}
+static void obs_clock_increments(glgym_handle h, double* doy_inc, double* hod_inc)
+{
+    *doy_inc = std::fmod(h->dt / 86400.0, 365.0);
+    *hod_inc = h->dt / 3600.0;
+}
 // one lane per environment (fp32 only since round 4)
+// o != nullptr: the builds with the observation epilogue (OBS), for rows of at most STEP_OBS_MAX_DIM_OCC1 / _OCC2 columns
 template <int SCH>
 static void launch_step_sch(const glgym_step_args* a, const StepArgsT<float>& k, const ModelConst<float>& m, const RewardConst<float>& rw,
-                            dim3 grid, dim3 block, hipStream_t st, bool def, bool occ2)
+                            dim3 grid, dim3 block, hipStream_t st, bool def, bool occ2, const StepObsArgs* o)
 {
     using T = float;
+    const StepNoObs no;
+    constexpr int SCHO = SCH | GL_SCH_OBS;
+    if (o) {
+        if (occ2) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHO, 2>), grid, block, 0, st, k, m, rw, *o);
+        else if (a->crop_p && def) hipLaunchKernelGGL((step_kernel<T, true, true, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
+        else if (a->crop_p) hipLaunchKernelGGL((step_kernel<T, true, false, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
+        else if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
+        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
+        return;
+    }
     if (occ2) {
-        hipLaunchKernelGGL((step_kernel<T, false, true, false, SCH, 2>), grid, block, 0, st, k, m, rw);
+        hipLaunchKernelGGL((step_kernel<T, false, true, false, SCH, 2>), grid, block, 0, st, k, m, rw, no);
         return;
     }
     if (a->crop_p) {
-        if (def) hipLaunchKernelGGL((step_kernel<T, true, true, false, SCH>), grid, block, 0, st, k, m, rw);
-        else hipLaunchKernelGGL((step_kernel<T, true, false, false, SCH>), grid, block, 0, st, k, m, rw);
+        if (def) hipLaunchKernelGGL((step_kernel<T, true, true, false, SCH>), grid, block, 0, st, k, m, rw, no);
+        else hipLaunchKernelGGL((step_kernel<T, true, false, false, SCH>), grid, block, 0, st, k, m, rw, no);
     } else {
-        if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCH>), grid, block, 0, st, k, m, rw);
-        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCH>), grid, block, 0, st, k, m, rw);
+        if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCH>), grid, block, 0, st, k, m, rw, no);
+        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCH>), grid, block, 0, st, k, m, rw, no);
     }
 }
 
@@ -1776,9 +1933,12 @@ static void launch_quad_sch(const glgym_step_args* a, const StepArgsT<T>& k, con
     }
 }
 
+// oa (glgym_step_obs): full-mode observation arguments.  Where the launch takes a kernel with the observation epilogue -- fp32, one lane
+// per environment, default ODE, a row that fits the staging area, the same buffers in both argument blocks -- *fused is set and the
+// rows are written by this launch; everywhere else the step is launched as ever and the caller launches obs_kernel behind it.
 template <class T>
 static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelConst<T>& m, const RewardConst<T>& rw,
-                       hipStream_t st)
+                       hipStream_t st, const glgym_obs_args* oa = nullptr, bool* fused = nullptr)
 {
     StepArgsT<T> k;
     k.B = a->B; k.ld = a->ld;
@@ -1829,7 +1989,7 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
             return GLGYM_OK;
         }
         if (pipe) {
-            hipLaunchKernelGGL((step_kernel<T, false, false, true>), grid, block, 0, st, k, m, rw);
+            hipLaunchKernelGGL((step_kernel<T, false, false, true>), grid, block, 0, st, k, m, rw, StepNoObs{});
             HIPCHK(hipGetLastError());
             return GLGYM_OK;
         }
@@ -1837,11 +1997,22 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
         // of at least two wavefronts per SIMD take (131 072 environments on MI355X: 1.08x there, 1.11x from 524 288); glgym_set_occupancy
         // forces either build.  Default parameters and shared crop blocks only (the variants it is instantiated for).
         const bool occ2 = def && !a->crop_p && (h->occupancy == 2 || (h->occupancy == 0 && (size_t)a->B >= (size_t)2 * WAVE * h->n_simd));
-        if (h->scheme == GLGYM_SCHEME_RK2) launch_step_sch<GLGYM_SCHEME_RK2>(a, k, m, rw, grid, block, st, def, occ2);
-        else if (h->scheme == GLGYM_SCHEME_RK3) launch_step_sch<GLGYM_SCHEME_RK3>(a, k, m, rw, grid, block, st, def, occ2);
-        else if (h->scheme == GLGYM_SCHEME_LS5) launch_step_sch<GLGYM_SCHEME_LS5>(a, k, m, rw, grid, block, st, def, occ2);
-        else launch_step_sch<GLGYM_SCHEME_RK4>(a, k, m, rw, grid, block, st, def, occ2);
+        StepObsArgs ob;
+        const StepObsArgs* o = nullptr;
+        if (oa && !oa->mask && oa->B == a->B && oa->ld == a->ld && oa->x == a->x && oa->u == a->u && oa->weather == a->weather &&
+            oa->weather_rows == a->weather_rows && oa->w_off == a->w_off && oa->timestep == a->timestep &&
+            ((uintptr_t)oa->obs & 15) == 0) {
+            ob.obs = oa->obs; ob.start_day = oa->start_day; ob.Np = oa->Np;
+            obs_clock_increments(h, &ob.doy_inc, &ob.hod_inc);
+            obs_layout(h, oa->Np, ob.moff, &ob.dim);
+            if (ob.dim > 0 && ob.dim <= (occ2 ? STEP_OBS_MAX_DIM_OCC2 : STEP_OBS_MAX_DIM_OCC1)) o = &ob;
+        }
+        if (h->scheme == GLGYM_SCHEME_RK2) launch_step_sch<GLGYM_SCHEME_RK2>(a, k, m, rw, grid, block, st, def, occ2, o);
+        else if (h->scheme == GLGYM_SCHEME_RK3) launch_step_sch<GLGYM_SCHEME_RK3>(a, k, m, rw, grid, block, st, def, occ2, o);
+        else if (h->scheme == GLGYM_SCHEME_LS5) launch_step_sch<GLGYM_SCHEME_LS5>(a, k, m, rw, grid, block, st, def, occ2, o);
+        else launch_step_sch<GLGYM_SCHEME_RK4>(a, k, m, rw, grid, block, st, def, occ2, o);
         HIPCHK(hipGetLastError());
+        if (o && fused) *fused = true;
         return GLGYM_OK;
     }
 }
@@ -1868,7 +2039,7 @@ static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const Rewar
     return GLGYM_OK;
 }
 
-extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream)
+static int step_impl(glgym_handle h, const glgym_step_args* a, void* stream, const glgym_obs_args* oa, bool* fused)
 {
     if (!h || !a) { g_err = "glgym_step: null handle / arguments"; return GLGYM_EINVAL; }
     if (a->struct_size != (int32_t)sizeof(glgym_step_args)) {     // checked before any pointer member is read
@@ -1892,28 +2063,26 @@ extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream
     }
     DeviceGuard dev_guard(h);
     hipStream_t st = (hipStream_t)stream;
-    return h->dtype == GLGYM_F32 ? launch_step<float>(h, a, h->mf, h->rf, st)
+    return h->dtype == GLGYM_F32 ? launch_step<float>(h, a, h->mf, h->rf, st, oa, fused)
                                  : launch_step<double>(h, a, h->md, h->rd, st);
 }
 
-static const int OBS_MODULE_SIZE[6] = {4, 3, 6, 5, 5, 0};      // observations.py:64,84,102,123,143; forecast = 5 * Np (:168)
+extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream)
+{
+    return step_impl(h, a, stream, nullptr, nullptr);
+}
 
 template <class T> static int launch_obs(glgym_handle h, const glgym_obs_args* a, hipStream_t st)
 {
     ObsArgsT<T> k;
     k.B = a->B; k.ld = a->ld; k.x = (const T*)a->x; k.u = (const T*)a->u; k.weather = (const T*)a->weather;
     k.weather_rows = a->weather_rows; k.w_off = a->w_off; k.timestep = a->timestep; k.start_day = a->start_day;
-    k.Np = a->Np; k.obs = a->obs; k.mask = a->mask; k.term_obs = a->term_obs; k.doy_inc = std::fmod(h->dt / 86400.0, 365.0); k.hod_inc = h->dt / 3600.0; k.nd = h->nd;
+    k.Np = a->Np; k.obs = a->obs; k.mask = a->mask; k.term_obs = a->term_obs; k.nd = h->nd;
+    obs_clock_increments(h, &k.doy_inc, &k.hod_inc);
     int blocks = (a->B + OBS_ROWS - 1) / OBS_ROWS;   // OBS_ROWS env rows per block-iteration
     static const int cap = [] { const char* e = std::getenv("GLGYM_OBS_BLOCKS"); return e ? std::atoi(e) : 4096; }();
     if (blocks > cap) blocks = cap;              // grid-stride beyond that
-    for (int m = 0; m < 6; ++m) k.moff[m] = -1;
-    k.dim = 0;
-    for (int i = 0; i < h->n_obs_modules; ++i) {
-        const int m = h->obs_modules[i];
-        k.moff[m] = k.dim;
-        k.dim += m == GLGYM_OBS_FORECAST ? 5 * a->Np : OBS_MODULE_SIZE[m];
-    }
+    obs_layout(h, a->Np, k.moff, &k.dim);
     const size_t lds = (size_t)OBS_ROWS * k.dim * sizeof(float);
     hipLaunchKernelGGL((obs_kernel<T>), dim3(blocks), dim3(256), lds, st, k);
     HIPCHK(hipGetLastError());
@@ -2010,16 +2179,35 @@ extern "C" int glgym_vecnorm(glgym_handle h, const glgym_vecnorm_args* a, void* 
 
 extern "C" {
 
+static bool obs_args_ok(glgym_handle h, const glgym_obs_args* a)
+{
+    return h && a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->weather && a->w_off && a->timestep && a->start_day && a->obs &&
+           a->Np >= 0 && a->Np <= OBS_MAX_NP;
+}
+
 int glgym_obs(glgym_handle h, const glgym_obs_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);
-    if (!h || !a || a->B < 1 || a->ld < a->B || !a->x || !a->u || !a->weather || !a->w_off || !a->timestep ||
-        !a->start_day || !a->obs || a->Np < 0 || a->Np > OBS_MAX_NP) {
+    if (!obs_args_ok(h, a)) {
         g_err = "glgym_obs: bad arguments (null pointer, ld < B, or Np outside 0..128)";
         return GLGYM_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
     return h->dtype == GLGYM_F32 ? launch_obs<float>(h, a, st) : launch_obs<double>(h, a, st);
+}
+
+int glgym_step_obs(glgym_handle h, const glgym_step_args* a, const glgym_obs_args* oa, void* stream)
+{
+    if (!h || !a || !oa) { g_err = "glgym_step_obs: null handle / arguments"; return GLGYM_EINVAL; }
+    if (oa->mask) { g_err = "glgym_step_obs: full-mode observations only (glgym_obs_args.mask must be NULL)"; return GLGYM_EINVAL; }
+    if (!obs_args_ok(h, oa)) {         // before the step is launched: nothing runs on bad arguments
+        g_err = "glgym_step_obs: bad observation arguments (null pointer, ld < B, or Np outside 0..128)";
+        return GLGYM_EINVAL;
+    }
+    bool fused = false;
+    const int rc = step_impl(h, a, stream, oa, &fused);
+    if (rc != GLGYM_OK || fused) return rc;
+    return glgym_obs(h, oa, stream);
 }
 
 int glgym_set_obs_modules(glgym_handle h, const int32_t* modules, int n)

@@ -171,6 +171,24 @@ class LazyInfos:
         return (self[i] for i in range(len(self)))
 
 
+class _EpochLib:
+    """The library as a TomatoVecEnv sees it: every call through it -- kernel launches, setters, whatever a caller does with `env._lib` and
+    `env._h` through raw pointers -- advances the environment's epoch first, which invalidates the token of a fused observation
+    (TomatoVecEnv._launch_obs).  Wrappers are made once per entry point."""
+
+    def __init__(self, lib, env):
+        self.__dict__["_lib"], self.__dict__["_env"] = lib, env
+
+    def __getattr__(self, name):
+        fn, env = getattr(self._lib, name), self._env
+
+        def call(*args):
+            env._epoch += 1
+            return fn(*args)
+        self.__dict__[name] = call
+        return call
+
+
 class TomatoVecEnv:
     def __init__(self, num_envs: int, weather: Optional[np.ndarray] = None, params: Optional[np.ndarray] = None,
                  dt: float = 900.0, season_length: float = 60, pred_horizon: float = 0.5, dtype: str = "float32",
@@ -213,7 +231,14 @@ class TomatoVecEnv:
         if not torch.cuda.is_available():
             raise L.GlgymError("TomatoVecEnv needs a HIP device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
-        self._lib = L.load()
+        # fused observations (glgym_step_obs): _launch_step / _launch_obs
+        self._epoch = 0                     # advanced by every library call (_EpochLib) and by whatever else replaces a buffer
+        self._obs_token = None              # what a fused step left in obs_t, until something could have changed it
+        self._obs_followed = False          # the last _launch_step was followed by a full-mode _launch_obs(self.obs_t)
+        self._stepped = False               # a _launch_step has happened (the observation after a reset arms nothing)
+        self.n_fused_steps = 0              # steps launched through glgym_step_obs
+        self.n_obs_elided = 0               # full-mode _launch_obs calls that found their rows already written and launched nothing
+        self._lib = _EpochLib(L.load(), self)
         self.torch = torch
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -448,20 +473,51 @@ class TomatoVecEnv:
                         len(self.start_rows), self.start_day_t.data_ptr(), self.episode_t.data_ptr(), self.seed_value)
         L.check(self._lib.glgym_reset(self._h, C.byref(a), self._stream()), "glgym_reset")
 
-    def _launch_obs(self, out_t, mask_t=None, term_t=None):
-        a = L.ObsArgs(self.B, self.ld, self.x_T.data_ptr(), self.u_T.data_ptr(), self.weather_t.data_ptr(),
-                      self.weather_rows, self.w_off_t.data_ptr(), self.timestep_t.data_ptr(),
-                      self.start_day_t.data_ptr(), self.Np, out_t.data_ptr(),
-                      mask_t.data_ptr() if mask_t is not None else None,
-                      term_t.data_ptr() if term_t is not None else None)
-        L.check(self._lib.glgym_obs(self._h, C.byref(a), self._stream()), "glgym_obs")
+    def _obs_args(self, out_t, mask_t=None, term_t=None):
+        return L.ObsArgs(self.B, self.ld, self.x_T.data_ptr(), self.u_T.data_ptr(), self.weather_t.data_ptr(),
+                         self.weather_rows, self.w_off_t.data_ptr(), self.timestep_t.data_ptr(),
+                         self.start_day_t.data_ptr(), self.Np, out_t.data_ptr(),
+                         mask_t.data_ptr() if mask_t is not None else None,
+                         term_t.data_ptr() if term_t is not None else None)
 
-    def _launch_step(self, raw_control: bool):
+    def _obs_deps(self):
+        """Address and torch version counter of every tensor a full-mode observation reads or lands in."""
+        return tuple((t.data_ptr(), t._version) for t in (self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t,
+                                                          self.weather_t, self.obs_t))
+
+    def _launch_obs(self, out_t, mask_t=None, term_t=None):
+        """glgym_obs into out_t: every row (mask_t None, "full mode"), or the rows of mask_t after saving them to term_t.
+
+        A full-mode call right after a fused step (_launch_step) launches nothing: that step's kernel has already written exactly these
+        rows.  The call returns without a launch if and only if (a) out_t is the very obs_t the fused step wrote, (b) the epoch is the
+        one recorded after that step -- every call into the library through this environment (reset, rule-based controller, crop noise,
+        any setter, the planner, raw-pointer calls through env._lib) and every assignment that replaces a buffer advances it -- and (c) the
+        torch version counters of x_T, u_T, timestep_t, w_off_t, start_day_t, weather_t and obs_t are the recorded ones.  (c) is the
+        safety argument for torch-side writes: an in-place operation on any of these tensors or on a view of them (env.x.copy_(...),
+        x_T.mul_(...), obs_t.fill_(...)) between the two calls changes a counter, so the observation is computed again from what is in
+        memory, as it always was.  The token is single-use.  In every other case the call does what it always did."""
+        if mask_t is None:
+            token, self._obs_token = self._obs_token, None
+            if out_t is self.obs_t:
+                self._obs_followed = self._stepped
+                if token is not None and token == (id(out_t), self._epoch, self._obs_deps()):
+                    self.n_obs_elided += 1
+                    return
+        L.check(self._lib.glgym_obs(self._h, C.byref(self._obs_args(out_t, mask_t, term_t)), self._stream()), "glgym_obs")
+
+    def _launch_step(self, raw_control: bool, want_obs: Optional[bool] = None):
+        """One glgym_step.  want_obs True: glgym_step_obs, which also leaves the full-mode observation of the new state in obs_t (one
+        launch where the library has a fused kernel for this configuration, step and observation kernels back to back elsewhere); the
+        full-mode _launch_obs(self.obs_t) that follows finds it there.  False: the plain step.  None (a bare call, as bench.py's loop):
+        adaptive -- fused when the previous step of this environment was followed by a full-mode _launch_obs(self.obs_t), so that loops
+        that never ask for observations never pay for them, and a fused observation that went unconsumed ends the fusing."""
         if self._env_at_create is not None and tuple(os.environ.get(k) for k in ("GLGYM_LAYOUT", "GLGYM_OCC", "GLGYM_VERIFY")) != self._env_at_create:
             import warnings
             warnings.warn("GLGYM_LAYOUT / GLGYM_OCC / GLGYM_VERIFY changed after this TomatoVecEnv was created: they are read once, at glgym_create, "
                           "and have no effect on an existing handle -- use set_layout() / set_occupancy() / set_verify()", RuntimeWarning, stacklevel=3)
             self._env_at_create = None                     # once
+        fuse = self._obs_followed if want_obs is None else bool(want_obs)
+        self._obs_followed, self._obs_token, self._stepped = False, None, True
         if self.rng == "numpy":
             if not getattr(self, "freeze_crop_noise", False):   # tomato_env.py:118: 34 draws every step, also at scale 0 (no block: streams advance)
                 L.check(self._lib.glgym_rng_crop_noise(self._h, self.crop_T.data_ptr() if self.crop_T is not None else None, self.B, self.ld,
@@ -479,7 +535,12 @@ class TomatoVecEnv:
                        self.crop_T.data_ptr() if self.crop_T is not None else None, self.N,
                        self.reward_t.data_ptr(), self.info_T.data_ptr(), self.done_t.data_ptr(),
                        self.metrics_t.data_ptr() if self.metrics_t is not None else None, self.step_flags_t.data_ptr())
-        L.check(self._lib.glgym_step(self._h, C.byref(a), self._stream()), "glgym_step")
+        if not fuse:
+            L.check(self._lib.glgym_step(self._h, C.byref(a), self._stream()), "glgym_step")
+            return
+        L.check(self._lib.glgym_step_obs(self._h, C.byref(a), C.byref(self._obs_args(self.obs_t)), self._stream()), "glgym_step_obs")
+        self.n_fused_steps += 1
+        self._obs_token = (id(self.obs_t), self._epoch, self._obs_deps())
 
     # ---- tensor interface (no host synchronisation) ---------------------------------------------
     def reset_tensor(self, seed: Optional[int] = None):
@@ -521,7 +582,7 @@ class TomatoVecEnv:
             self.ctrl_T[:, :self.B].copy_(controls_t.reshape(self.B, L.NU).t())
         else:
             self._launch_rule_based(controller)
-        self._launch_step(raw_control=actions_t is None)
+        self._launch_step(raw_control=actions_t is None, want_obs=want_obs)
         if want_obs:
             self._launch_obs(self.obs_t)
         if self.auto_reset:      # SB3 semantics: finished envs restart; their last obs goes to term_obs_t
@@ -673,6 +734,7 @@ class TomatoVecEnv:
             raise ValueError(f"weather_data has {table.shape[0]} rows, an episode needs {need}")
         self._weather_data = table
         self.weather_rows = int(table.shape[0])
+        self._epoch += 1                    # another table, another row count: a fused observation of the old one is void
         self.weather_t = torch.as_tensor(table, dtype=self.tdtype, device=self.device).contiguous()
         self.start_rows = np.zeros(1, dtype=np.int64)
         self.start_days = np.asarray(self.start_days[:1], dtype=np.float32)
@@ -737,9 +799,10 @@ class TomatoVecEnv:
         return {k: float(v[i]) for i, k in enumerate(L.METRIC_KEYS)}
 
     def capture_step_graph(self, want_obs: bool = True):
-        """Capture one full step (action copy -> glgym_step -> glgym_obs -> masked glgym_reset -> masked glgym_obs) in a
-        HIP graph.  The library's device-pointer entry points never synchronise, so they can be stream-captured; one
-        graph launch then replaces five kernel launches (about 2 % at B = 65 536, more when B is small).  Returns
+        """Capture one full step (action copy -> glgym_step_obs -> masked glgym_reset -> masked glgym_obs; without want_obs:
+        action copy -> glgym_step -> masked glgym_reset) in a HIP graph, a single chain of nodes.  The library's device-pointer entry
+        points never synchronise, so they can be stream-captured; one graph launch then replaces the kernel launches of a step
+        (about 2 % at B = 65 536, more when B is small).  Returns
         ``replay(actions_t) -> (obs, reward, done, info)`` with the same device tensors ``step_tensor`` returns.
         Per-env crop noise (uncertainty_scale > 0) of rng="philox" advances a host-side draw counter per step and is not capturable;
         with rng="numpy" the streams live on the device and the noise and start-draw launches are captured with the rest."""
@@ -751,7 +814,7 @@ class TomatoVecEnv:
         def seq():
             self.action_t.copy_(static_a)
             self._action_src = self.action_t
-            self._launch_step(raw_control=False)
+            self._launch_step(raw_control=False, want_obs=want_obs)
             if want_obs:
                 self._launch_obs(self.obs_t)
             if self.auto_reset:

@@ -4,7 +4,7 @@
  *
  * Plain C, pointers and sizes only (no torch / pybind types).  One handle = one HIP device + one
  * parameter block + one dtype.  The library never allocates per call on the hot path and never
- * synchronises the stream in glgym_step / glgym_obs / glgym_reset (safe to capture in a hipGraph);
+ * synchronises the stream in glgym_step / glgym_obs / glgym_step_obs / glgym_reset (safe to capture in a hipGraph);
  * the host-pointer convenience entry points (glgym_evalF, glgym_rhs) do synchronise.
  * Every function returns a glgym_status; nothing throws.  There is NO CPU fallback: without a HIP
  * device glgym_create() returns GLGYM_ENODEV.
@@ -18,6 +18,7 @@
  *                     (action_to_control :109-113, evalF call :120, terminal test :131-132,
  *                      reward rewards.py:218-231, info tomato_env.py:208-222), batched over B envs
  *   glgym_obs      <- TomatoEnv._get_obs + 6 observation modules gl_gym/environments/observations.py:59-182
+ *   glgym_step_obs <- the two above in one call (one launch where the step kernel can write the observation rows itself)
  *   glgym_reset    <- TomatoEnv.reset (state part)               gl_gym/environments/tomato_env.py:262-266,
  *                     init_state                                  gl_gym/environments/utils.py:13-46
  *   glgym_crop_noise <- parametric_crop_uncertainty               gl_gym/environments/noise.py:3-23
@@ -153,7 +154,7 @@ typedef struct {
 /* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
- * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select */
+ * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -339,6 +340,15 @@ int glgym_obs_dim(glgym_handle h, int Np);
  * (measured on the storm / jump fixtures: <= 2.5e-4 scaled between the two fp32 layouts, tests/test_gpu_storm.py). */
 int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream);
 int glgym_obs(glgym_handle h, const glgym_obs_args* a, void* stream);
+/* Exactly glgym_step(h, step, stream) followed by glgym_obs(h, obs, stream) in full mode; obs->mask must be NULL (GLGYM_EINVAL).
+ * Both argument blocks are checked before anything is launched.  ONE launch where the handle's configuration has a step kernel with the
+ * observation epilogue: GLGYM_F32, one lane per environment, the default ODE, any scheme, shared or per-env crop parameters, either
+ * occupancy build, a row of at most 512 columns (292 in the two-waves build; the default modules up to Np = 97 / 53), `obs` 16-byte aligned, and x / u / weather / w_off /
+ * timestep / B / ld the same in both blocks.  Each wavefront then writes the observation rows of its own 64 environments as soon as it
+ * has finished integrating -- while the launch waits for its slowest wavefront anyway -- with the same bits glgym_obs writes.  Everywhere
+ * else (four lanes per environment, GLGYM_F64, GLGYM_ODE_PIPE, GLGYM_INTEGRATOR_BDF env-steps, wider rows, differing buffers) the two
+ * kernels are launched back to back; the caller never needs to know which.  Never synchronises (capturable like the calls it replaces). */
+int glgym_step_obs(glgym_handle h, const glgym_step_args* step, const glgym_obs_args* obs, void* stream);
 int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream);
 /* crop_p[i][b] = fl(p[128+i] * (1 + U(-scale/2, scale/2))), then p144 = p141/p142; Philox4x32-10 keyed by
  * (seed, stream_id), counter (env index, draw_index).  crop_p: SoA [34][ld] T. */
