@@ -135,6 +135,62 @@ __device__ __forceinline__ float obs_core_feature(int j, float prim, float aux, 
 __device__ __forceinline__ constexpr int obs_core_module(int j) { return j < 4 ? 0 : j < 7 ? 1 : j < 13 ? 2 : j < 18 ? 3 : 4; }
 __device__ __forceinline__ constexpr int obs_core_col(int j) { return j < 4 ? j : j < 7 ? j - 4 : j < 13 ? j - 7 : j < 18 ? j - 13 : j - 18; }
 
+// counter-based generator shared by the reset (episode start draw) and crop-noise kernels
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                              unsigned k1, unsigned* out)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// one environment's reset: the episode start draw and init_state (utils.py:13-46) -- reset_kernel's body, shared with the auto-reset
+// epilogue of step_kernel.  ONE definition, so that both produce the same bits.
+// ---------------------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ void reset_env(int b, int ld, T* x, T* u, int* timestep, const T* weather, int weather_rows, int* w_off,
+                                          const int* start_rows, const float* start_days, int n_starts, float* start_day, int* episode,
+                                          unsigned long long seed, int nd)
+{
+    // No implicit contraction in here (obs_core_feature): the two fused operations reset_kernel has always had are written out.
+#pragma clang fp contract(off)
+    if (start_rows && n_starts > 0) {            // draw this episode's start (tomato_env.py:236-244)
+        const int ep = episode ? episode[b] : 0;
+        unsigned rnd[4];
+        philox4x32_10((unsigned)b, (unsigned)ep, 0x5eedu, 0u, (unsigned)seed, (unsigned)(seed >> 32), rnd);
+        const int j = (int)(rnd[0] % (unsigned)n_starts);
+        w_off[b] = start_rows[j];
+        if (start_day && start_days) start_day[b] = start_days[j];
+        if (episode) episode[b] = ep + 1;
+    }
+    int r = w_off[b];
+    r = r < 0 ? 0 : (r >= weather_rows ? weather_rows - 1 : r);
+    const double co2Out = (double)weather[(size_t)r * nd + 3], tSoOut = (double)weather[(size_t)r * nd + 6];
+    const double tAir = 16.5;
+    double xi[NX];
+    xi[0] = xi[1] = co2Out;
+    for (int i = 2; i <= 10; ++i) xi[i] = tAir;
+    xi[4] = tAir + 4;
+    xi[11] = 0.25 * (3.0 * tAir + tSoOut);
+    xi[12] = 0.25 * __builtin_fma(2.0, tSoOut, 2.0 * tAir);
+    xi[13] = 0.25 * __builtin_fma(3.0, tSoOut, tAir);
+    xi[14] = tSoOut;
+    xi[15] = xi[16] = 90.0 / 100.0 * (610.78 * exp(17.2694 * tAir / (tAir + 238.3)));
+    xi[17] = xi[18] = xi[19] = xi[20] = tAir;
+    xi[21] = xi[4];
+    xi[22] = 0.0; xi[23] = 9.5283e4; xi[24] = 2.5107e5; xi[25] = 5.5338e4; xi[26] = 3.0978e3; xi[27] = 0.0;
+    for (int i = 0; i < NX; ++i) x[(size_t)i * ld + b] = T(xi[i]);
+    for (int j = 0; j < NU; ++j) u[(size_t)j * ld + b] = T(0);
+    timestep[b] = 0;
+}
+
 #ifndef GL_OBS_ROWS
 #define GL_OBS_ROWS 16
 #endif
@@ -153,9 +209,19 @@ struct StepObsArgs {
 // eight and six workgroups per CU) it sent them to scratch instead, inside the window loop (profiles/step_obs_fusion.txt).
 constexpr int STEP_OBS_MAX_DIM_OCC2 = WAVE * ((2 * NX + GL_N_SLOW) | 1) / OBS_ROWS, STEP_OBS_MAX_DIM_OCC1 = 512;
 struct StepNoObs {};
+// ... and what the auto-reset epilogue needs on top (glgym_step_obs_reset): the terminal-observation block and reset_kernel's arguments that
+// the step does not have already (w_off / start_day are the step's and the observation's own buffers, writable here)
+struct StepObsResetArgs : StepObsArgs {
+    float* term_obs;
+    int* w_off_rw; float* start_day_rw; int* episode;
+    const int* start_rows; const float* start_days; int n_starts;
+    unsigned long long seed;
+};
 constexpr int GL_SCH_OBS = 8;          // step_kernel's scheme argument: | GL_SCH_OBS = the build with the observation epilogue
-template <bool OBS> struct StepObsSel { using type = StepNoObs; };
-template <> struct StepObsSel<true> { using type = StepObsArgs; };
+constexpr int GL_SCH_RESET = 16;       // | GL_SCH_RESET (with GL_SCH_OBS): the auto-reset epilogue behind it
+template <int EPI> struct StepObsSel { using type = StepNoObs; };
+template <> struct StepObsSel<GL_SCH_OBS> { using type = StepObsArgs; };
+template <> struct StepObsSel<GL_SCH_OBS | GL_SCH_RESET> { using type = StepObsResetArgs; };
 
 // ---------------------------------------------------------------------------------------------------
 // fused env-step
@@ -206,11 +272,12 @@ template <class T, int SCH> struct SchemeWin { static constexpr int value = SCH 
 // (step_kernel<float, false, true, false, 3, 1> in every profile on record; tests/test_capi_surface.py finds its kernels by that prefix).
 template <class T, bool PER_ENV_CROP, bool DEFAULT_P, bool PIPE = false, int SCHX = 0, int OCC = GL_STEP_WAVES_PER_SIMD>
 __global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelConst<T> m_arg, RewardConst<T> rw,
-                                                         typename StepObsSel<(SCHX & GL_SCH_OBS) != 0>::type o)
+                                                         typename StepObsSel<(SCHX & (GL_SCH_OBS | GL_SCH_RESET))>::type o)
 {
-    constexpr bool OBS = (SCHX & GL_SCH_OBS) != 0;
+    constexpr bool OBS = (SCHX & GL_SCH_OBS) != 0, RST = (SCHX & GL_SCH_RESET) != 0;
     constexpr int SCH = SCHX & (GL_SCH_OBS - 1);
     static_assert(!OBS || (sizeof(T) == 4 && !PIPE), "observation epilogue: fp32, default ODE");
+    static_assert(!RST || (OBS && !PER_ENV_CROP), "auto-reset epilogue: behind the observation epilogue, shared crop parameters");
     const ModelConst<T>& m = DEFAULT_P ? device_default<T>() : m_arg;
     // OCC = 2 (round 5): what the windows read once each -- z0, the increments del, the slow slots' window differences -- lives in LDS,
     // WSTRIDE floats per lane (odd: conflict-free), 19.2 KB per wavefront = eight wavefronts per CU; the action tile of the prologue
@@ -433,6 +500,62 @@ __global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelCo
                     for (int jj = lane; jj < dim; jj += WAVE) out[(size_t)r * dim + jj] = span[(size_t)r * dim + jj];
             }
             __syncthreads();
+        }
+        if constexpr (RST) {
+            // ---- auto-reset epilogue (glgym_step_obs_reset): what reset_kernel over the mask `done` and obs_kernel in masked mode would do
+            // behind this launch, for this wavefront's own finished environments.  One wave-uniform test; a wavefront without a finished
+            // environment -- almost every wavefront of almost every step -- executes nothing else.  done, reward, info, step_flags and the
+            // metrics stay as the step wrote them.
+            const bool fin = live && term;
+            const unsigned long long fin_mask = __builtin_amdgcn_ballot_w64(fin);
+            if (fin_mask != 0) {
+                const size_t row0 = (size_t)b0 * dim;
+                __syncthreads();                            // (the strips' stores to obs, made by other lanes, are read back below)
+                // (a) the finished rows as they stand, the terminal observations, to the same rows of term_obs; a row per pass
+                if (o.term_obs) {
+                    for (unsigned long long mk = fin_mask; mk != 0; mk &= mk - 1) {
+                        const size_t e0 = row0 + (size_t)__builtin_ctzll(mk) * dim;
+                        for (int jj = lane; jj < dim; jj += WAVE) o.term_obs[e0 + jj] = o.obs[e0 + jj];
+                    }
+                }
+                __syncthreads();                            // all of them read before the first is overwritten
+                // (b) the new episode: start draw, initial state, zero controls, timestep 0 (reset_env, reset_kernel's body)
+                // (c) the row of the reset state: its 23 core features by the lane that owns the environment ...
+                int base_new = 0;
+                if (fin) {
+                    reset_env<T>(b, a.ld, a.x, a.u, a.timestep, a.weather, a.weather_rows, o.w_off_rw, o.start_rows, o.start_days, o.n_starts,
+                                 o.start_day_rw, o.episode, o.seed, a.nd);
+                    base_new = o.w_off_rw[b];               // timestep 0: the window starts at the episode's first row
+                    const int basen = base_new >= a.weather_rows ? a.weather_rows - 1 : (base_new < 0 ? 0 : base_new);
+                    const T* wrown = a.weather + (size_t)basen * a.nd;
+                    float wn[5];
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) wn[j] = wrown[j];
+                    const float sdayn = o.start_day_rw[b];
+                    const float tAirn = a.x[(size_t)2 * a.ld + b];
+                    float* orow = o.obs + row0 + (size_t)lane * dim;
+#pragma unroll
+                    for (int j = 0; j < OBS_NCORE; ++j) {
+                        const int xi = j == 0 ? 0 : j == 1 ? 2 : j == 2 ? 15 : j == 3 ? 9 : j == 4 ? 21 : j == 5 ? 25 : 26;
+                        const float prim = j < 7 ? a.x[(size_t)xi * a.ld + b] : (j < 13 ? 0.0f : wn[j < 18 ? j - 13 : 0]);
+                        const float aux = j < 13 ? tAirn : wn[1];
+                        const int mo = o.moff[obs_core_module(j)];
+                        if (mo >= 0) orow[mo + obs_core_col(j)] = obs_core_feature(j, prim, aux, sdayn, 0, o.doy_inc, o.hod_inc);
+                    }
+                }
+                // ... and its forecast block by the whole wavefront, a row per pass
+                for (unsigned long long mk = fin_mask; mk != 0; mk &= mk - 1) {
+                    const int r = __builtin_ctzll(mk);
+                    const int base_r1 = __builtin_amdgcn_readlane(base_new, r);
+                    float* orow = o.obs + row0 + (size_t)r * dim + o.moff[5];
+                    for (int q = lane; q < nf; q += WAVE) {
+                        const int i = q / 5, c = q - i * 5;
+                        int row = base_r1 + 1 + i;
+                        row = row >= a.weather_rows ? a.weather_rows - 1 : (row < 0 ? 0 : row);
+                        orow[q] = (float)a.weather[(size_t)row * a.nd + c];
+                    }
+                }
+            }
         }
     }
 }
@@ -999,22 +1122,6 @@ __global__ __launch_bounds__(256) void rule_based_kernel(glgym_rule_cfg c, int B
     control[(size_t)5 * ld + b] = (T)(c.useBlScr * (1.0 - isDaySmooth) * lamp_on);
 }
 
-// counter-based generator shared by the reset (episode start draw) and crop-noise kernels
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned* out)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-
 // ---------------------------------------------------------------------------------------------------
 // masked reset: init_state (utils.py:13-46)
 // ---------------------------------------------------------------------------------------------------
@@ -1025,34 +1132,7 @@ __global__ void reset_kernel(int B, int ld, const unsigned char* mask, T* x, T* 
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B || (mask && !mask[b])) return;
-    if (start_rows && n_starts > 0) {            // draw this episode's start (tomato_env.py:236-244)
-        const int ep = episode ? episode[b] : 0;
-        unsigned rnd[4];
-        philox4x32_10((unsigned)b, (unsigned)ep, 0x5eedu, 0u, (unsigned)seed, (unsigned)(seed >> 32), rnd);
-        const int j = (int)(rnd[0] % (unsigned)n_starts);
-        w_off[b] = start_rows[j];
-        if (start_day && start_days) start_day[b] = start_days[j];
-        if (episode) episode[b] = ep + 1;
-    }
-    int r = w_off[b];
-    r = r < 0 ? 0 : (r >= weather_rows ? weather_rows - 1 : r);
-    const double co2Out = (double)weather[(size_t)r * nd + 3], tSoOut = (double)weather[(size_t)r * nd + 6];
-    const double tAir = 16.5;
-    double xi[NX];
-    xi[0] = xi[1] = co2Out;
-    for (int i = 2; i <= 10; ++i) xi[i] = tAir;
-    xi[4] = tAir + 4;
-    xi[11] = 0.25 * (3.0 * tAir + tSoOut);
-    xi[12] = 0.25 * (2.0 * tAir + 2 * tSoOut);
-    xi[13] = 0.25 * (tAir + 3 * tSoOut);
-    xi[14] = tSoOut;
-    xi[15] = xi[16] = 90.0 / 100.0 * (610.78 * exp(17.2694 * tAir / (tAir + 238.3)));
-    xi[17] = xi[18] = xi[19] = xi[20] = tAir;
-    xi[21] = xi[4];
-    xi[22] = 0.0; xi[23] = 9.5283e4; xi[24] = 2.5107e5; xi[25] = 5.5338e4; xi[26] = 3.0978e3; xi[27] = 0.0;
-    for (int i = 0; i < NX; ++i) x[(size_t)i * ld + b] = T(xi[i]);
-    for (int j = 0; j < NU; ++j) u[(size_t)j * ld + b] = T(0);
-    timestep[b] = 0;
+    reset_env<T>(b, ld, x, u, timestep, weather, weather_rows, w_off, start_rows, start_days, n_starts, start_day, episode, seed, nd);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1885,11 +1965,17 @@ static void obs_clock_increments(glgym_handle h, double* doy_inc, double* hod_in
 // o != nullptr: the builds with the observation epilogue (OBS), for rows of at most STEP_OBS_MAX_DIM_OCC1 / _OCC2 columns
 template <int SCH>
 static void launch_step_sch(const glgym_step_args* a, const StepArgsT<float>& k, const ModelConst<float>& m, const RewardConst<float>& rw,
-                            dim3 grid, dim3 block, hipStream_t st, bool def, bool occ2, const StepObsArgs* o)
+                            dim3 grid, dim3 block, hipStream_t st, bool def, bool occ2, const StepObsArgs* o, const StepObsResetArgs* r)
 {
     using T = float;
     const StepNoObs no;
-    constexpr int SCHO = SCH | GL_SCH_OBS;
+    constexpr int SCHO = SCH | GL_SCH_OBS, SCHR = SCHO | GL_SCH_RESET;
+    if (r) {             // observation and auto-reset epilogues: shared crop parameters only
+        if (occ2) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHR, 2>), grid, block, 0, st, k, m, rw, *r);
+        else if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHR>), grid, block, 0, st, k, m, rw, *r);
+        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCHR>), grid, block, 0, st, k, m, rw, *r);
+        return;
+    }
     if (o) {
         if (occ2) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHO, 2>), grid, block, 0, st, k, m, rw, *o);
         else if (a->crop_p && def) hipLaunchKernelGGL((step_kernel<T, true, true, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
@@ -1935,10 +2021,13 @@ static void launch_quad_sch(const glgym_step_args* a, const StepArgsT<T>& k, con
 
 // oa (glgym_step_obs): full-mode observation arguments.  Where the launch takes a kernel with the observation epilogue -- fp32, one lane
 // per environment, default ODE, a row that fits the staging area, the same buffers in both argument blocks -- *fused is set and the
-// rows are written by this launch; everywhere else the step is launched as ever and the caller launches obs_kernel behind it.
+// rows are written by this launch (*fused = 1); everywhere else the step is launched as ever and the caller launches obs_kernel behind it.
+// ra (glgym_step_obs_reset, with oa): the reset of the environments the step finishes.  Where the observation epilogue is taken, the crop
+// parameters are shared, ra carries a start table and names the step's own buffers, the kernel also has the auto-reset epilogue
+// (*fused = 2): nothing is left for the caller to launch.
 template <class T>
 static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelConst<T>& m, const RewardConst<T>& rw,
-                       hipStream_t st, const glgym_obs_args* oa = nullptr, bool* fused = nullptr)
+                       hipStream_t st, const glgym_obs_args* oa = nullptr, int* fused = nullptr, const glgym_reset_args* ra = nullptr)
 {
     StepArgsT<T> k;
     k.B = a->B; k.ld = a->ld;
@@ -1997,8 +2086,9 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
         // of at least two wavefronts per SIMD take (131 072 environments on MI355X: 1.08x there, 1.11x from 524 288); glgym_set_occupancy
         // forces either build.  Default parameters and shared crop blocks only (the variants it is instantiated for).
         const bool occ2 = def && !a->crop_p && (h->occupancy == 2 || (h->occupancy == 0 && (size_t)a->B >= (size_t)2 * WAVE * h->n_simd));
-        StepObsArgs ob;
+        StepObsResetArgs ob;
         const StepObsArgs* o = nullptr;
+        const StepObsResetArgs* r = nullptr;
         if (oa && !oa->mask && oa->B == a->B && oa->ld == a->ld && oa->x == a->x && oa->u == a->u && oa->weather == a->weather &&
             oa->weather_rows == a->weather_rows && oa->w_off == a->w_off && oa->timestep == a->timestep &&
             ((uintptr_t)oa->obs & 15) == 0) {
@@ -2007,12 +2097,20 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
             obs_layout(h, oa->Np, ob.moff, &ob.dim);
             if (ob.dim > 0 && ob.dim <= (occ2 ? STEP_OBS_MAX_DIM_OCC2 : STEP_OBS_MAX_DIM_OCC1)) o = &ob;
         }
-        if (h->scheme == GLGYM_SCHEME_RK2) launch_step_sch<GLGYM_SCHEME_RK2>(a, k, m, rw, grid, block, st, def, occ2, o);
-        else if (h->scheme == GLGYM_SCHEME_RK3) launch_step_sch<GLGYM_SCHEME_RK3>(a, k, m, rw, grid, block, st, def, occ2, o);
-        else if (h->scheme == GLGYM_SCHEME_LS5) launch_step_sch<GLGYM_SCHEME_LS5>(a, k, m, rw, grid, block, st, def, occ2, o);
-        else launch_step_sch<GLGYM_SCHEME_RK4>(a, k, m, rw, grid, block, st, def, occ2, o);
+        if (o && ra && !a->crop_p && ra->B == a->B && ra->ld == a->ld && ra->x == a->x && ra->u == a->u && ra->timestep == a->timestep &&
+            ra->weather == a->weather && ra->weather_rows == a->weather_rows && ra->w_off == a->w_off && ra->start_rows &&
+            ra->start_days && ra->n_starts > 0 && ra->start_day && ra->start_day == oa->start_day && ra->episode) {
+            ob.term_obs = oa->term_obs; ob.w_off_rw = ra->w_off; ob.start_day_rw = ra->start_day; ob.episode = ra->episode;
+            ob.start_rows = ra->start_rows; ob.start_days = ra->start_days; ob.n_starts = ra->n_starts;
+            ob.seed = (unsigned long long)ra->seed;
+            r = &ob;
+        }
+        if (h->scheme == GLGYM_SCHEME_RK2) launch_step_sch<GLGYM_SCHEME_RK2>(a, k, m, rw, grid, block, st, def, occ2, o, r);
+        else if (h->scheme == GLGYM_SCHEME_RK3) launch_step_sch<GLGYM_SCHEME_RK3>(a, k, m, rw, grid, block, st, def, occ2, o, r);
+        else if (h->scheme == GLGYM_SCHEME_LS5) launch_step_sch<GLGYM_SCHEME_LS5>(a, k, m, rw, grid, block, st, def, occ2, o, r);
+        else launch_step_sch<GLGYM_SCHEME_RK4>(a, k, m, rw, grid, block, st, def, occ2, o, r);
         HIPCHK(hipGetLastError());
-        if (o && fused) *fused = true;
+        if (o && fused) *fused = r ? 2 : 1;
         return GLGYM_OK;
     }
 }
@@ -2039,7 +2137,8 @@ static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const Rewar
     return GLGYM_OK;
 }
 
-static int step_impl(glgym_handle h, const glgym_step_args* a, void* stream, const glgym_obs_args* oa, bool* fused)
+static int step_impl(glgym_handle h, const glgym_step_args* a, void* stream, const glgym_obs_args* oa, int* fused,
+                     const glgym_reset_args* ra = nullptr)
 {
     if (!h || !a) { g_err = "glgym_step: null handle / arguments"; return GLGYM_EINVAL; }
     if (a->struct_size != (int32_t)sizeof(glgym_step_args)) {     // checked before any pointer member is read
@@ -2063,7 +2162,7 @@ static int step_impl(glgym_handle h, const glgym_step_args* a, void* stream, con
     }
     DeviceGuard dev_guard(h);
     hipStream_t st = (hipStream_t)stream;
-    return h->dtype == GLGYM_F32 ? launch_step<float>(h, a, h->mf, h->rf, st, oa, fused)
+    return h->dtype == GLGYM_F32 ? launch_step<float>(h, a, h->mf, h->rf, st, oa, fused, ra)
                                  : launch_step<double>(h, a, h->md, h->rd, st);
 }
 
@@ -2204,7 +2303,7 @@ int glgym_step_obs(glgym_handle h, const glgym_step_args* a, const glgym_obs_arg
         g_err = "glgym_step_obs: bad observation arguments (null pointer, ld < B, or Np outside 0..128)";
         return GLGYM_EINVAL;
     }
-    bool fused = false;
+    int fused = 0;
     const int rc = step_impl(h, a, stream, oa, &fused);
     if (rc != GLGYM_OK || fused) return rc;
     return glgym_obs(h, oa, stream);
@@ -2255,6 +2354,34 @@ int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream)
                            (unsigned long long)a->seed, h->nd);
     HIPCHK(hipGetLastError());
     return GLGYM_OK;
+}
+
+int glgym_step_obs_reset(glgym_handle h, const glgym_step_args* a, const glgym_obs_args* oa, const glgym_reset_args* ra, void* stream,
+                         int32_t* fused_out)
+{
+    if (fused_out) *fused_out = 0;
+    if (!h || !a || !oa || !ra) { g_err = "glgym_step_obs_reset: null handle / arguments"; return GLGYM_EINVAL; }
+    if (a->struct_size != (int32_t)sizeof(glgym_step_args)) return step_impl(h, a, stream, nullptr, nullptr);      // its message, nothing launched
+    if ((oa->mask && oa->mask != a->done) || (ra->mask && ra->mask != a->done)) {
+        g_err = "glgym_step_obs_reset: the masks of the observation and reset blocks must be NULL or the step's `done`";
+        return GLGYM_EINVAL;
+    }
+    if (!obs_args_ok(h, oa) || ra->B < 1 || ra->ld < ra->B || !ra->x || !ra->u || !ra->timestep || !ra->weather || !ra->w_off) {
+        g_err = "glgym_step_obs_reset: bad observation or reset arguments";      // before the step is launched: nothing runs on bad arguments
+        return GLGYM_EINVAL;
+    }
+    glgym_obs_args full = *oa, masked = *oa;
+    full.mask = nullptr; full.term_obs = oa->term_obs;
+    masked.mask = a->done;
+    glgym_reset_args rst = *ra;
+    rst.mask = a->done;
+    int fused = 0;
+    int rc = step_impl(h, a, stream, &full, &fused, &rst);
+    if (rc == GLGYM_OK && fused == 2 && fused_out) *fused_out = 1;
+    if (rc != GLGYM_OK || fused == 2) return rc;
+    if (!fused && (rc = glgym_obs(h, &full, stream)) != GLGYM_OK) return rc;
+    if ((rc = glgym_reset(h, &rst, stream)) != GLGYM_OK) return rc;
+    return glgym_obs(h, &masked, stream);
 }
 
 int glgym_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t seed, uint64_t draw_index,

@@ -238,6 +238,12 @@ class TomatoVecEnv:
         self._stepped = False               # a _launch_step has happened (the observation after a reset arms nothing)
         self.n_fused_steps = 0              # steps launched through glgym_step_obs
         self.n_obs_elided = 0               # full-mode _launch_obs calls that found their rows already written and launched nothing
+        # fused auto-reset (glgym_step_obs_reset): _launch_step / _launch_reset / _launch_obs
+        self._reset_token = None            # what a fused auto-reset left behind, until something could have changed it
+        self._pattern = -1                  # how far the calls since the last _launch_step have followed full obs (1), reset(done_t) (2), masked obs (3)
+        self._auto_reset_applied = None     # left by a step that has done its own auto-reset, until the next step (_launch_reset, _launch_obs)
+        self.n_fused_resets = 0             # steps whose auto-reset and terminal observations ran inside the step's own launch
+        self.n_reset_elided = 0             # _launch_reset(done_t) / masked _launch_obs calls that found their work done and launched nothing
         self._lib = _EpochLib(L.load(), self)
         self.torch = torch
         self.device = torch.device(device)
@@ -455,7 +461,32 @@ class TomatoVecEnv:
     def _launch_reset(self, mask_t):
         """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).
         rng="numpy": glgym_rng_reset_draw takes choice(years), choice(days) from each masked environment's stream first, and
-        glgym_reset, called without a start table, initialises from the w_off it wrote."""
+        glgym_reset, called without a start table, initialises from the w_off it wrote.
+
+        _launch_reset(self.done_t) right after a step whose kernel has already reset the finished environments (_launch_step) launches
+        nothing, under the conditions of _reset_elided().  Where those do not hold (a setter call, a torch write to one of the buffers, a
+        reset with another mask came between) the reset of that step's `done` mask is still the one the step has applied, and
+        reset_kernel, which counts episodes and draws a new start each time it runs, must not run over it a second time: the first
+        _launch_reset(done_t) after such a step launches nothing either while done_t is unwritten (the mask is the one the step used).
+        After an in-place write to done_t the mask is whatever the caller made of it: the reset then runs over done_t AND timestep_t != 0.
+        A step leaves timestep_t >= 1 in every environment it did not reset, so this takes out exactly the environments the step has
+        reset and keeps the ones the caller added; an environment at timestep 0 is at an episode start already.  If timestep_t was
+        written as well nothing tells the two apart, and the call raises instead of resetting twice."""
+        token, self._reset_token = self._reset_token, None
+        self._pattern = 2 if (mask_t is self.done_t and self._pattern == 1) else -1
+        if mask_t is self.done_t and self._reset_elided(token):
+            self._reset_token = token                      # the masked observation that follows is part of the same fused step
+            return
+        st = self._auto_reset_applied
+        if mask_t is self.done_t and st is not None and not st["reset_seen"]:
+            st["reset_seen"] = True
+            if st["done"] == (self.done_t.data_ptr(), self.done_t._version):
+                return                                     # this step's reset, already applied by the step's own launch
+            if st["timestep"] != (self.timestep_t.data_ptr(), self.timestep_t._version):
+                raise RuntimeError("done_t and timestep_t were both written between a step with a fused auto-reset and its "
+                                   "_launch_reset(done_t): the environments that step has already reset cannot be told from the ones "
+                                   "added to the mask; reset those through a mask tensor of their own")
+            mask_t = st["added"] = self.done_t * (self.timestep_t != 0).to(self.done_t.dtype)
         mask_ptr = mask_t.data_ptr() if mask_t is not None else None
         if self.rng == "numpy":
             L.check(self._lib.glgym_rng_reset_draw(self._h, self.B, self.ld, mask_ptr, self.rng_state_t.data_ptr(), self.start_grid[0],
@@ -467,11 +498,14 @@ class TomatoVecEnv:
                             self.start_day_t.data_ptr(), self.episode_t.data_ptr(), self.seed_value)
             L.check(self._lib.glgym_reset(self._h, C.byref(a), self._stream()), "glgym_reset")
             return
-        a = L.ResetArgs(self.B, self.ld, mask_t.data_ptr() if mask_t is not None else None, self.x_T.data_ptr(),
-                        self.u_T.data_ptr(), self.timestep_t.data_ptr(), self.weather_t.data_ptr(), self.weather_rows,
-                        self.w_off_t.data_ptr(), self._start_rows_t.data_ptr(), self._start_days_t.data_ptr(),
-                        len(self.start_rows), self.start_day_t.data_ptr(), self.episode_t.data_ptr(), self.seed_value)
-        L.check(self._lib.glgym_reset(self._h, C.byref(a), self._stream()), "glgym_reset")
+        L.check(self._lib.glgym_reset(self._h, C.byref(self._reset_args(mask_t)), self._stream()), "glgym_reset")
+
+    def _reset_args(self, mask_t):
+        """glgym_reset's arguments with the start table (rng="philox")."""
+        return L.ResetArgs(self.B, self.ld, mask_t.data_ptr() if mask_t is not None else None, self.x_T.data_ptr(),
+                           self.u_T.data_ptr(), self.timestep_t.data_ptr(), self.weather_t.data_ptr(), self.weather_rows,
+                           self.w_off_t.data_ptr(), self._start_rows_t.data_ptr(), self._start_days_t.data_ptr(),
+                           len(self.start_rows), self.start_day_t.data_ptr(), self.episode_t.data_ptr(), self.seed_value)
 
     def _obs_args(self, out_t, mask_t=None, term_t=None):
         return L.ObsArgs(self.B, self.ld, self.x_T.data_ptr(), self.u_T.data_ptr(), self.weather_t.data_ptr(),
@@ -485,6 +519,21 @@ class TomatoVecEnv:
         return tuple((t.data_ptr(), t._version) for t in (self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t,
                                                           self.weather_t, self.obs_t))
 
+    def _reset_deps(self):
+        """Address and torch version counter of every tensor a fused auto-reset reads or writes."""
+        return tuple((t.data_ptr(), t._version) for t in (self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t,
+                                                          self.done_t, self.obs_t, self.term_obs_t, self.weather_t))
+
+    def _reset_elided(self, token):
+        """True, and counted, if `token` is that of a fused auto-reset nothing has come after: the epoch is the one recorded after that
+        step (no library call through this environment since: no reset with another mask, no setter, no observation that had to be
+        launched) and the version counters of x_T, u_T, timestep_t, w_off_t, start_day_t, episode_t, done_t, obs_t, term_obs_t and
+        weather_t are the recorded ones (no in-place torch write to any of them or to a view of them)."""
+        if token is None or token != (self._epoch, self._reset_deps()):
+            return False
+        self.n_reset_elided += 1
+        return True
+
     def _launch_obs(self, out_t, mask_t=None, term_t=None):
         """glgym_obs into out_t: every row (mask_t None, "full mode"), or the rows of mask_t after saving them to term_t.
 
@@ -495,29 +544,72 @@ class TomatoVecEnv:
         torch version counters of x_T, u_T, timestep_t, w_off_t, start_day_t, weather_t and obs_t are the recorded ones.  (c) is the
         safety argument for torch-side writes: an in-place operation on any of these tensors or on a view of them (env.x.copy_(...),
         x_T.mul_(...), obs_t.fill_(...)) between the two calls changes a counter, so the observation is computed again from what is in
-        memory, as it always was.  The token is single-use.  In every other case the call does what it always did."""
+        memory, as it always was.  The token is single-use.  In every other case the call does what it always did.
+
+        The masked call _launch_obs(self.obs_t, self.done_t, self.term_obs_t) after a fused auto-reset and its elided _launch_reset(done_t)
+        launches nothing either (_reset_elided): the terminal rows are in term_obs_t and the rows of the new episodes in obs_t.  Where it
+        is not elided it computes those rows again from memory and leaves term_obs_t as that step wrote it (see _launch_reset)."""
         if mask_t is None:
             token, self._obs_token = self._obs_token, None
+            self._pattern = 1 if (out_t is self.obs_t and self._pattern == 0) else -1
             if out_t is self.obs_t:
                 self._obs_followed = self._stepped
                 if token is not None and token == (id(out_t), self._epoch, self._obs_deps()):
                     self.n_obs_elided += 1
                     return
+            self._reset_token = None                       # a launched observation: the pattern of a fused auto-reset is broken
+        else:
+            token, self._reset_token = self._reset_token, None
+            whole = out_t is self.obs_t and mask_t is self.done_t and term_t is self.term_obs_t
+            elide = whole and self._pattern == 2 and self._reset_elided(token)
+            self._pattern = 3 if (whole and self._pattern == 2) else -1
+            if elide:
+                return
+            st = self._auto_reset_applied
+            if mask_t is self.done_t and term_t is not None and st is not None and not st["obs_seen"]:
+                # not elided, but the step has saved the terminal rows and reset these environments: saving again would put the rows of
+                # the new episodes into term_obs_t.  The rows are computed again from what is in memory, without the save; the
+                # environments a written done_t added (_launch_reset) get both, first.
+                if not whole:
+                    raise RuntimeError("the terminal observations of a step with a fused auto-reset are in term_obs_t; a masked "
+                                       "_launch_obs over done_t after it takes obs_t and term_obs_t")
+                st["obs_seen"] = True
+                if st["added"] is not None:
+                    L.check(self._lib.glgym_obs(self._h, C.byref(self._obs_args(out_t, st["added"], term_t)), self._stream()), "glgym_obs")
+                term_t = None
         L.check(self._lib.glgym_obs(self._h, C.byref(self._obs_args(out_t, mask_t, term_t)), self._stream()), "glgym_obs")
 
-    def _launch_step(self, raw_control: bool, want_obs: Optional[bool] = None):
+    def _launch_step(self, raw_control: bool, want_obs: Optional[bool] = None, with_reset: Optional[bool] = None):
         """One glgym_step.  want_obs True: glgym_step_obs, which also leaves the full-mode observation of the new state in obs_t (one
         launch where the library has a fused kernel for this configuration, step and observation kernels back to back elsewhere); the
         full-mode _launch_obs(self.obs_t) that follows finds it there.  False: the plain step.  None (a bare call, as bench.py's loop):
         adaptive -- fused when the previous step of this environment was followed by a full-mode _launch_obs(self.obs_t), so that loops
-        that never ask for observations never pay for them, and a fused observation that went unconsumed ends the fusing."""
+        that never ask for observations never pay for them, and a fused observation that went unconsumed ends the fusing.
+
+        with_reset True (step_tensor, capture_step_graph; auto_reset only): glgym_step_obs_reset -- the step, the full-mode observation,
+        the reset of the environments this step finished (mask done_t) and their masked observation with the terminal rows saved to
+        term_obs_t, in one launch where the library has a kernel with the auto-reset epilogue for this configuration and back to back
+        elsewhere.  None with a bare call: adaptive again -- only with auto_reset, and only when the previous step of this environment was
+        followed by exactly _launch_obs(obs_t), _launch_reset(done_t), _launch_obs(obs_t, done_t, term_obs_t) in this order (bench.py's
+        loop).  After such a step these three calls launch nothing (_launch_obs, _reset_elided); a fused reset that is not followed by
+        the three ends the fusing.  Only a caller's own three calls arm it: step_tensor and capture_step_graph leave it unarmed.
+        CONTRACT: after a step with a fused auto-reset, x_T, u_T, timestep_t, w_off_t, start_day_t and
+        episode_t hold the POST-RESET state of the finished environments and obs_t the first observation of their new episodes -- what
+        step_tensor has always left behind -- already when _launch_step returns; done_t, reward_t, info_T, step_flags_t and the metrics
+        are the step's.  A torch write between the step and the follow-up calls therefore lands on the post-reset state, and the follow-up
+        calls that are not elided never apply that step's reset or save its terminal rows a second time (_launch_reset, _launch_obs).
+        rng="numpy" (start draws from device streams between step and reset) never takes this path."""
         if self._env_at_create is not None and tuple(os.environ.get(k) for k in ("GLGYM_LAYOUT", "GLGYM_OCC", "GLGYM_VERIFY")) != self._env_at_create:
             import warnings
             warnings.warn("GLGYM_LAYOUT / GLGYM_OCC / GLGYM_VERIFY changed after this TomatoVecEnv was created: they are read once, at glgym_create, "
                           "and have no effect on an existing handle -- use set_layout() / set_occupancy() / set_verify()", RuntimeWarning, stacklevel=3)
             self._env_at_create = None                     # once
         fuse = self._obs_followed if want_obs is None else bool(want_obs)
+        if with_reset is None:
+            with_reset = want_obs is None and self._pattern == 3
+        with_reset = bool(with_reset) and fuse and self.auto_reset and self.rng != "numpy"
         self._obs_followed, self._obs_token, self._stepped = False, None, True
+        self._reset_token, self._pattern, self._auto_reset_applied = None, 0, None
         if self.rng == "numpy":
             if not getattr(self, "freeze_crop_noise", False):   # tomato_env.py:118: 34 draws every step, also at scale 0 (no block: streams advance)
                 L.check(self._lib.glgym_rng_crop_noise(self._h, self.crop_T.data_ptr() if self.crop_T is not None else None, self.B, self.ld,
@@ -537,6 +629,18 @@ class TomatoVecEnv:
                        self.metrics_t.data_ptr() if self.metrics_t is not None else None, self.step_flags_t.data_ptr())
         if not fuse:
             L.check(self._lib.glgym_step(self._h, C.byref(a), self._stream()), "glgym_step")
+            return
+        if with_reset:
+            one = C.c_int32(0)
+            L.check(self._lib.glgym_step_obs_reset(self._h, C.byref(a), C.byref(self._obs_args(self.obs_t, None, self.term_obs_t)),
+                                                   C.byref(self._reset_args(self.done_t)), self._stream(), C.byref(one)),
+                    "glgym_step_obs_reset")
+            self.n_fused_steps += 1
+            self.n_fused_resets += one.value
+            self._obs_token = (id(self.obs_t), self._epoch, self._obs_deps())
+            self._reset_token = (self._epoch, self._reset_deps())
+            self._auto_reset_applied = dict(done=(self.done_t.data_ptr(), self.done_t._version), reset_seen=False, obs_seen=False, added=None,
+                                            timestep=(self.timestep_t.data_ptr(), self.timestep_t._version))
             return
         L.check(self._lib.glgym_step_obs(self._h, C.byref(a), C.byref(self._obs_args(self.obs_t)), self._stream()), "glgym_step_obs")
         self.n_fused_steps += 1
@@ -582,7 +686,10 @@ class TomatoVecEnv:
             self.ctrl_T[:, :self.B].copy_(controls_t.reshape(self.B, L.NU).t())
         else:
             self._launch_rule_based(controller)
-        self._launch_step(raw_control=actions_t is None, want_obs=want_obs)
+        # one library call for step, observation, auto-reset and terminal observations (one launch where the library has the kernel)
+        # unless the host infos need the applied controls copied between step and reset (step_wait)
+        self._launch_step(raw_control=actions_t is None, want_obs=want_obs,
+                          with_reset=want_obs and self.auto_reset and not self._keep_applied_u)
         if want_obs:
             self._launch_obs(self.obs_t)
         if self.auto_reset:      # SB3 semantics: finished envs restart; their last obs goes to term_obs_t
@@ -596,6 +703,7 @@ class TomatoVecEnv:
             self._launch_reset(self.done_t)
             if want_obs:
                 self._launch_obs(self.obs_t, self.done_t, self.term_obs_t)
+        self._pattern = -1               # these were step_tensor's own calls: they arm no bare _launch_step
         return self.obs_t, self.reward_t[:self.B], self.done_t, self.info_T[:, :self.B]
 
     # ---- SB3 VecEnv calling convention ------------------------------------------------------------
@@ -799,7 +907,7 @@ class TomatoVecEnv:
         return {k: float(v[i]) for i, k in enumerate(L.METRIC_KEYS)}
 
     def capture_step_graph(self, want_obs: bool = True):
-        """Capture one full step (action copy -> glgym_step_obs -> masked glgym_reset -> masked glgym_obs; without want_obs:
+        """Capture one full step (action copy -> glgym_step_obs_reset, one node where the library has the kernel with both epilogues; without want_obs:
         action copy -> glgym_step -> masked glgym_reset) in a HIP graph, a single chain of nodes.  The library's device-pointer entry
         points never synchronise, so they can be stream-captured; one graph launch then replaces the kernel launches of a step
         (about 2 % at B = 65 536, more when B is small).  Returns
@@ -814,13 +922,14 @@ class TomatoVecEnv:
         def seq():
             self.action_t.copy_(static_a)
             self._action_src = self.action_t
-            self._launch_step(raw_control=False, want_obs=want_obs)
+            self._launch_step(raw_control=False, want_obs=want_obs, with_reset=want_obs and self.auto_reset)
             if want_obs:
                 self._launch_obs(self.obs_t)
             if self.auto_reset:
                 self._launch_reset(self.done_t)
                 if want_obs:
                     self._launch_obs(self.obs_t, self.done_t, self.term_obs_t)
+            self._pattern = -1              # the captured sequence's own calls: they arm no bare _launch_step
 
         # warm-up on a side stream (torch's capture protocol), with the state restored afterwards
         state = [self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t, self.obs_t]

@@ -4,7 +4,7 @@
  *
  * Plain C, pointers and sizes only (no torch / pybind types).  One handle = one HIP device + one
  * parameter block + one dtype.  The library never allocates per call on the hot path and never
- * synchronises the stream in glgym_step / glgym_obs / glgym_step_obs / glgym_reset (safe to capture in a hipGraph);
+ * synchronises the stream in glgym_step / glgym_obs / glgym_step_obs / glgym_step_obs_reset / glgym_reset (safe to capture in a hipGraph);
  * the host-pointer convenience entry points (glgym_evalF, glgym_rhs) do synchronise.
  * Every function returns a glgym_status; nothing throws.  There is NO CPU fallback: without a HIP
  * device glgym_create() returns GLGYM_ENODEV.
@@ -19,6 +19,8 @@
  *                      reward rewards.py:218-231, info tomato_env.py:208-222), batched over B envs
  *   glgym_obs      <- TomatoEnv._get_obs + 6 observation modules gl_gym/environments/observations.py:59-182
  *   glgym_step_obs <- the two above in one call (one launch where the step kernel can write the observation rows itself)
+ *   glgym_step_obs_reset <- the same, then the auto-reset of a vectorised environment: terminal observation kept, finished
+ *                     environments re-initialised, their rows recomputed (one launch where the step kernel can do all of it)
  *   glgym_reset    <- TomatoEnv.reset (state part)               gl_gym/environments/tomato_env.py:262-266,
  *                     init_state                                  gl_gym/environments/utils.py:13-46
  *   glgym_crop_noise <- parametric_crop_uncertainty               gl_gym/environments/noise.py:3-23
@@ -154,7 +156,7 @@ typedef struct {
 /* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
- * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs */
+ * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -350,6 +352,21 @@ int glgym_obs(glgym_handle h, const glgym_obs_args* a, void* stream);
  * kernels are launched back to back; the caller never needs to know which.  Never synchronises (capturable like the calls it replaces). */
 int glgym_step_obs(glgym_handle h, const glgym_step_args* step, const glgym_obs_args* obs, void* stream);
 int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream);
+/* One env-step with auto-reset.  Exactly glgym_step_obs(h, step, obs in full mode, stream), then glgym_reset(h, reset with mask = step->done,
+ * stream), then glgym_obs(h, obs with mask = step->done, stream): step->done is the mask of both, whatever the two blocks say (their
+ * `mask` must be NULL or step->done itself: GLGYM_EINVAL otherwise); obs->term_obs receives the rows of the finished environments as
+ * they were before the reset (may be NULL).  Afterwards x / u / timestep / w_off / start_day / episode hold the POST-RESET state of the
+ * finished environments and `obs` their first observation; done, reward, info, step_flags and the metrics are the step's.
+ * ONE launch where glgym_step_obs is one launch and in addition the crop parameters are shared (step->crop_p NULL), `reset` carries a
+ * start table (start_rows, start_days, n_starts > 0, start_day, episode) and names the step's buffers (x, u, timestep, weather, w_off,
+ * B, ld; start_day the observation's): each wavefront that holds a finished environment then does the three steps for it right after
+ * writing its rows, with the same bits; a wavefront that holds none executes one test.  Everywhere else -- four lanes per environment,
+ * GLGYM_F64, GLGYM_ODE_PIPE, GLGYM_INTEGRATOR_BDF env-steps, per-env crop blocks, rows wider than glgym_step_obs's limit, no start
+ * table (as with glgym_rng_reset_draw) -- the kernels are launched back to back, with the same results.  All three
+ * argument blocks are checked before anything is launched.  Never synchronises (capturable).
+ * fused (may be NULL): set to 1 when the call was the one launch, to 0 when it launched the kernels back to back. */
+int glgym_step_obs_reset(glgym_handle h, const glgym_step_args* step, const glgym_obs_args* obs, const glgym_reset_args* reset,
+                         void* stream, int32_t* fused);
 /* crop_p[i][b] = fl(p[128+i] * (1 + U(-scale/2, scale/2))), then p144 = p141/p142; Philox4x32-10 keyed by
  * (seed, stream_id), counter (env index, draw_index).  crop_p: SoA [34][ld] T. */
 int glgym_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t seed, uint64_t draw_index,
