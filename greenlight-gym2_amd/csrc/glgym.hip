@@ -17,12 +17,14 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "glgym.h"
 #include "gl_model.hpp"
 #include "gl_model_quad.hpp"
 #include "gl_reward.hpp"
+#include "gl_step_select.hpp"
 #include "glgym_bdf.h"
 #include "glgym_rng.h"
 #include "glgym_plan.h"
@@ -1756,37 +1758,45 @@ static int ensure_scratch(glgym_handle h, size_t elems)
     return GLGYM_OK;
 }
 
+// the run-time scheme as a compile-time constant: f(std::integral_constant<int, GLGYM_SCHEME_*>)
+template <class F> static void with_scheme(int scheme, F&& f)
+{
+    if (scheme == GLGYM_SCHEME_RK2) f(std::integral_constant<int, GLGYM_SCHEME_RK2>{});
+    else if (scheme == GLGYM_SCHEME_RK3) f(std::integral_constant<int, GLGYM_SCHEME_RK3>{});
+    else if (scheme == GLGYM_SCHEME_LS5) f(std::integral_constant<int, GLGYM_SCHEME_LS5>{});
+    else f(std::integral_constant<int, GLGYM_SCHEME_RK4>{});
+}
+
 template <class T, int SCH>
 static void launch_evalf_sch(glgym_handle h, const ModelConst<T>& m, const double* p_used, const double* dx, const double* du,
-                             const double* dd, const double* dcrop, int B, double* dout, dim3 grid, dim3 block)
+                             const double* dd, const double* dcrop, int B, double* dout)
 {
     const int verify = h->verify_mode != GLGYM_VERIFY_NEVER;
+    const int pipe = h->variant == GLGYM_ODE_PIPE ? 1 : 0;
+    const dim3 grid((B + WAVE - 1) / WAVE), qgrid((4 * B + WAVE - 1) / WAVE), pgrid((8 * B + WAVE - 1) / WAVE), block(WAVE);
+    const auto go = [&](auto kernel, dim3 g, auto... tail) {
+        hipLaunchKernelGGL(kernel, g, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub, T(p_used[39]), T(p_used[162]), m,
+                           dout, tail...);
+    };
+    const auto one = [&](auto kernel) { go(kernel, grid, 0, h->nd, h->fail_dev, verify, h->window); };
+    const auto quad = [&](auto kernel, dim3 g) { go(kernel, g, h->nd, h->fail_dev, verify, pipe, h->window); };
     // verified calls on batches that leave lanes free run the ladder two rungs at a time, two quads per row (evalf_kernel_quad<PAIR>):
     // up to one wavefront per SIMD of the device (8 lanes per row); beyond that the sequential ladder does the same work on fewer lanes
     const bool pair = verify && h->ladder_parallel && !dcrop && (size_t)8 * B <= (size_t)WAVE * h->n_simd &&
                       (sizeof(T) == 8 || h->layout != GLGYM_LAYOUT_ONE);
-    if constexpr (sizeof(T) == 8) {      // fp64: four lanes per row (no one-lane fp64 integrator exists any more)
-        const dim3 qgrid((4 * B + WAVE - 1) / WAVE), pgrid((8 * B + WAVE - 1) / WAVE);
-        const int pipe = h->variant == GLGYM_ODE_PIPE ? 1 : 0;
-        if (pair) hipLaunchKernelGGL((evalf_kernel_quad<T, SCH, true, false, true>), pgrid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                                     T(p_used[39]), T(p_used[162]), m, dout, h->nd, h->fail_dev, verify, pipe, h->window);
-        else if (dcrop) hipLaunchKernelGGL((evalf_kernel_quad<T, SCH, true, true>), qgrid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                                      T(p_used[39]), T(p_used[162]), m, dout, h->nd, h->fail_dev, verify, pipe, h->window);
-        else hipLaunchKernelGGL((evalf_kernel_quad<T, SCH, true, false>), qgrid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                                T(p_used[39]), T(p_used[162]), m, dout, h->nd, h->fail_dev, verify, pipe, h->window);
+    if constexpr (sizeof(T) == 8) {      // fp64: four lanes per row (no one-lane fp64 integrator exists any more), the variant selected at run time
+        if (pair) quad(evalf_kernel_quad<T, SCH, true, false, true>, pgrid);
+        else if (dcrop) quad(evalf_kernel_quad<T, SCH, true, true>, qgrid);
+        else quad(evalf_kernel_quad<T, SCH, true, false>, qgrid);
     } else {
-        const dim3 pgrid((8 * B + WAVE - 1) / WAVE);
-        if (pair) hipLaunchKernelGGL((evalf_kernel_quad<T, SCH, false, false, true>), pgrid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                                     T(p_used[39]), T(p_used[162]), m, dout, h->nd, h->fail_dev, verify, 0, h->window);
+        if (pipe) one(evalf_kernel<T, false, true>);        // the single generic RK4 build (run_evalf)
+        else if (pair) quad(evalf_kernel_quad<T, SCH, false, false, true>, pgrid);
         // fp32 rows without their own parameter block take the four-lanes-per-row kernel where glgym_step does (up to one round of
         // quad wavefronts: 16 384 rows on MI355X; glgym_set_layout overrides)
         else if (!dcrop && (h->layout == GLGYM_LAYOUT_QUAD || (h->layout == GLGYM_LAYOUT_AUTO && B <= 4 * h->n_simd * 4)))
-            hipLaunchKernelGGL((evalf_kernel_quad<T, SCH, false, false, false>), dim3((4 * B + WAVE - 1) / WAVE), block, 0, (hipStream_t)0, dx, du, dd, dcrop, B,
-                               T(h->dt), h->n_sub, T(p_used[39]), T(p_used[162]), m, dout, h->nd, h->fail_dev, verify, 0, h->window);
-        else if (dcrop) hipLaunchKernelGGL((evalf_kernel<T, true, false, SCH>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                                      T(p_used[39]), T(p_used[162]), m, dout, 0, h->nd, h->fail_dev, verify, h->window);
-        else hipLaunchKernelGGL((evalf_kernel<T, false, false, SCH>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                                T(p_used[39]), T(p_used[162]), m, dout, 0, h->nd, h->fail_dev, verify, h->window);
+            quad(evalf_kernel_quad<T, SCH, false, false, false>, qgrid);
+        else if (dcrop) one(evalf_kernel<T, true, false, SCH>);
+        else one(evalf_kernel<T, false, false, SCH>);
     }
 }
 
@@ -1794,36 +1804,20 @@ template <class T>
 static int run_evalf(glgym_handle h, const ModelConst<T>& m, const double* p_used, const double* dx, const double* du,
                      const double* dd, const double* dcrop, int B, double* dout, int rhs_only)
 {
-    const dim3 grid((B + WAVE - 1) / WAVE), block(WAVE);
     const bool pipe = h->variant == GLGYM_ODE_PIPE;
     if (rhs_only) {                      // the right-hand side at one state per row (test hook): one lane per row in either dtype
+        const dim3 grid((B + WAVE - 1) / WAVE), block(WAVE);
         if (pipe) hipLaunchKernelGGL((rhs_kernel<T, false, true>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(p_used[39]), T(p_used[162]), m, dout, h->nd);
         else if (dcrop) hipLaunchKernelGGL((rhs_kernel<T, true, false>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(p_used[39]), T(p_used[162]), m, dout, h->nd);
         else hipLaunchKernelGGL((rhs_kernel<T, false, false>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(p_used[39]), T(p_used[162]), m, dout, h->nd);
         HIPCHK(hipGetLastError());
         return GLGYM_OK;
     }
-    if (pipe) {
-        if (dcrop || h->scheme != GLGYM_SCHEME_RK4) {
-            g_err = "glgym_evalF: GLGYM_ODE_PIPE supports neither per-row parameter blocks nor schemes other than GLGYM_SCHEME_RK4";
-            return GLGYM_EINVAL;
-        }
-        if constexpr (sizeof(T) == 8) {      // (the fp64 kernels select the variant at run time)
-            launch_evalf_sch<T, GLGYM_SCHEME_RK4>(h, m, p_used, dx, du, dd, dcrop, B, dout, grid, block);
-        } else {
-            const int verify = h->verify_mode != GLGYM_VERIFY_NEVER;
-            hipLaunchKernelGGL((evalf_kernel<T, false, true>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub,
-                               T(p_used[39]), T(p_used[162]), m, dout, 0, h->nd, h->fail_dev, verify, h->window);
-        }
-    } else if (h->scheme == GLGYM_SCHEME_RK2) {
-        launch_evalf_sch<T, GLGYM_SCHEME_RK2>(h, m, p_used, dx, du, dd, dcrop, B, dout, grid, block);
-    } else if (h->scheme == GLGYM_SCHEME_RK3) {
-        launch_evalf_sch<T, GLGYM_SCHEME_RK3>(h, m, p_used, dx, du, dd, dcrop, B, dout, grid, block);
-    } else if (h->scheme == GLGYM_SCHEME_LS5) {
-        launch_evalf_sch<T, GLGYM_SCHEME_LS5>(h, m, p_used, dx, du, dd, dcrop, B, dout, grid, block);
-    } else {
-        launch_evalf_sch<T, GLGYM_SCHEME_RK4>(h, m, p_used, dx, du, dd, dcrop, B, dout, grid, block);
+    if (pipe && (dcrop || h->scheme != GLGYM_SCHEME_RK4)) {
+        g_err = "glgym_evalF: GLGYM_ODE_PIPE supports neither per-row parameter blocks nor schemes other than GLGYM_SCHEME_RK4";
+        return GLGYM_EINVAL;
     }
+    with_scheme(h->scheme, [&](auto sch) { launch_evalf_sch<T, decltype(sch)::value>(h, m, p_used, dx, du, dd, dcrop, B, dout); });
     HIPCHK(hipGetLastError());
     return GLGYM_OK;
 }
@@ -1961,70 +1955,35 @@ static void obs_clock_increments(glgym_handle h, double* doy_inc, double* hod_in
     *doy_inc = std::fmod(h->dt / 86400.0, 365.0);
     *hod_inc = h->dt / 3600.0;
 }
-// one lane per environment (fp32 only since round 4)
-// o != nullptr: the builds with the observation epilogue (OBS), for rows of at most STEP_OBS_MAX_DIM_OCC1 / _OCC2 columns
-template <int SCH>
-static void launch_step_sch(const glgym_step_args* a, const StepArgsT<float>& k, const ModelConst<float>& m, const RewardConst<float>& rw,
-                            dim3 grid, dim3 block, hipStream_t st, bool def, bool occ2, const StepObsArgs* o, const StepObsResetArgs* r)
+// the observation block of a glgym_step_obs call names the step's own buffers, in full mode, with rows the epilogue's float4 stores can take
+static bool obs_same_buffers(const glgym_step_args* a, const glgym_obs_args* oa)
 {
-    using T = float;
-    const StepNoObs no;
-    constexpr int SCHO = SCH | GL_SCH_OBS, SCHR = SCHO | GL_SCH_RESET;
-    if (r) {             // observation and auto-reset epilogues: shared crop parameters only
-        if (occ2) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHR, 2>), grid, block, 0, st, k, m, rw, *r);
-        else if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHR>), grid, block, 0, st, k, m, rw, *r);
-        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCHR>), grid, block, 0, st, k, m, rw, *r);
-        return;
-    }
-    if (o) {
-        if (occ2) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHO, 2>), grid, block, 0, st, k, m, rw, *o);
-        else if (a->crop_p && def) hipLaunchKernelGGL((step_kernel<T, true, true, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
-        else if (a->crop_p) hipLaunchKernelGGL((step_kernel<T, true, false, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
-        else if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
-        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCHO>), grid, block, 0, st, k, m, rw, *o);
-        return;
-    }
-    if (occ2) {
-        hipLaunchKernelGGL((step_kernel<T, false, true, false, SCH, 2>), grid, block, 0, st, k, m, rw, no);
-        return;
-    }
-    if (a->crop_p) {
-        if (def) hipLaunchKernelGGL((step_kernel<T, true, true, false, SCH>), grid, block, 0, st, k, m, rw, no);
-        else hipLaunchKernelGGL((step_kernel<T, true, false, false, SCH>), grid, block, 0, st, k, m, rw, no);
-    } else {
-        if (def) hipLaunchKernelGGL((step_kernel<T, false, true, false, SCH>), grid, block, 0, st, k, m, rw, no);
-        else hipLaunchKernelGGL((step_kernel<T, false, false, false, SCH>), grid, block, 0, st, k, m, rw, no);
-    }
+    return oa && !oa->mask && oa->B == a->B && oa->ld == a->ld && oa->x == a->x && oa->u == a->u && oa->weather == a->weather &&
+           oa->weather_rows == a->weather_rows && oa->w_off == a->w_off && oa->timestep == a->timestep && ((uintptr_t)oa->obs & 15) == 0;
+}
+// the reset block of a glgym_step_obs_reset call names the step's and the observation's own buffers and carries a start table
+static bool reset_same_buffers(const glgym_step_args* a, const glgym_obs_args* oa, const glgym_reset_args* ra)
+{
+    return ra && ra->B == a->B && ra->ld == a->ld && ra->x == a->x && ra->u == a->u && ra->timestep == a->timestep &&
+           ra->weather == a->weather && ra->weather_rows == a->weather_rows && ra->w_off == a->w_off && ra->start_rows &&
+           ra->start_days && ra->n_starts > 0 && ra->start_day && ra->start_day == oa->start_day && ra->episode;
 }
 
-// four lanes per environment.  fp64: every scheme, per-env crop blocks, the handle's parameters as a kernel argument; fp32 (small
-// batches): the shared-crop kernels of every scheme, with the default block compiled in where the handle holds it.
+static_assert(glsel::WAVE == WAVE && glsel::SCH_OBS == GL_SCH_OBS && glsel::SCH_RESET == GL_SCH_RESET && glsel::RK4 == GLGYM_SCHEME_RK4 &&
+              glsel::OBS_MAX_DIM_OCC1 == STEP_OBS_MAX_DIM_OCC1 && glsel::OBS_MAX_DIM_OCC2 == STEP_OBS_MAX_DIM_OCC2, "gl_step_select.hpp");
+template <int EPI> static typename StepObsSel<EPI>::type epilogue_args(const StepObsResetArgs& ob)
+{
+    if constexpr (EPI == 0) return {}; else return ob;
+}
+
+// The step launcher: the build is chosen by glsel::select_step (gl_step_select.hpp, where the rules and the list of builds are) and
+// mapped to its kernel through that list.
+// oa (glgym_step_obs): full-mode observation arguments.  Where the chosen build has the observation epilogue, *fused is set and the
+// rows are written by this launch (*fused = 1); everywhere else the step is launched as ever and the caller launches obs_kernel behind it.
+// ra (glgym_step_obs_reset, with oa): the reset of the environments the step finishes.  Where the build also has the auto-reset epilogue
+// (*fused = 2) nothing is left for the caller to launch.
 // (No fp64 build with the default block compiled in: measured without the scheduler flag that used to break it -- csrc/Makefile --
 // it buys 0.7 % over the LDS-staged block, 1.379e6 against 1.369e6 env-steps/s at config 2, for six more 500-register kernels.)
-// pair: verified steps on batches that leave lanes free run the ladder two rungs at a time on two quads per environment (PAIR)
-template <class T, int SCH>
-static void launch_quad_sch(const glgym_step_args* a, const StepArgsT<T>& k, const ModelConst<T>& m, const RewardConst<T>& rw,
-                            dim3 qgrid, dim3 block, hipStream_t st, bool def, bool pair)
-{
-    const dim3 pgrid((8 * (size_t)a->B + WAVE - 1) / WAVE);
-    if constexpr (sizeof(T) == 8) {          // ODE_pipe compiled in, selected by k.pipe
-        if (pair) hipLaunchKernelGGL((step_kernel_quad<T, false, SCH, true, false, true>), pgrid, block, 0, st, k, m, rw);
-        else if (a->crop_p) hipLaunchKernelGGL((step_kernel_quad<T, false, SCH, true, true>), qgrid, block, 0, st, k, m, rw);
-        else hipLaunchKernelGGL((step_kernel_quad<T, false, SCH, true, false>), qgrid, block, 0, st, k, m, rw);
-    } else {
-        if (pair && def) hipLaunchKernelGGL((step_kernel_quad<T, true, SCH, false, false, true>), pgrid, block, 0, st, k, m, rw);
-        else if (pair) hipLaunchKernelGGL((step_kernel_quad<T, false, SCH, false, false, true>), pgrid, block, 0, st, k, m, rw);
-        else if (def) hipLaunchKernelGGL((step_kernel_quad<T, true, SCH, false, false>), qgrid, block, 0, st, k, m, rw);
-        else hipLaunchKernelGGL((step_kernel_quad<T, false, SCH, false, false>), qgrid, block, 0, st, k, m, rw);
-    }
-}
-
-// oa (glgym_step_obs): full-mode observation arguments.  Where the launch takes a kernel with the observation epilogue -- fp32, one lane
-// per environment, default ODE, a row that fits the staging area, the same buffers in both argument blocks -- *fused is set and the
-// rows are written by this launch (*fused = 1); everywhere else the step is launched as ever and the caller launches obs_kernel behind it.
-// ra (glgym_step_obs_reset, with oa): the reset of the environments the step finishes.  Where the observation epilogue is taken, the crop
-// parameters are shared, ra carries a start table and names the step's own buffers, the kernel also has the auto-reset epilogue
-// (*fused = 2): nothing is left for the caller to launch.
 template <class T>
 static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelConst<T>& m, const RewardConst<T>& rw,
                        hipStream_t st, const glgym_obs_args* oa = nullptr, int* fused = nullptr, const glgym_reset_args* ra = nullptr)
@@ -2043,76 +2002,57 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
     k.pipe = h->variant == GLGYM_ODE_PIPE ? 1 : 0;
     k.window = h->window;
     k.verify = h->verify_mode == GLGYM_VERIFY_ALWAYS || (h->verify_mode == GLGYM_VERIFY_AUTO && (!a->action || h->du > 0.1001f));
-    const dim3 grid((a->B + WAVE - 1) / WAVE), block(WAVE), qgrid((4 * a->B + WAVE - 1) / WAVE);
-    const bool pipe = h->variant == GLGYM_ODE_PIPE;
-    if (pipe && (a->crop_p || h->scheme != GLGYM_SCHEME_RK4)) {
-        g_err = "glgym_step: GLGYM_ODE_PIPE supports neither per-env crop parameters nor schemes other than GLGYM_SCHEME_RK4";
-        return GLGYM_EINVAL;
+    // glgym_set_layout / _occupancy are handle state since round 5; the environment variables GLGYM_LAYOUT / GLGYM_OCC are only their
+    // INITIAL values, read once at glgym_create (changing os.environ afterwards has no effect on an existing handle).
+    glsel::StepSelectIn in;
+    in.f64 = sizeof(T) == 8; in.scheme = h->scheme; in.pipe = k.pipe != 0; in.crop = a->crop_p != nullptr;
+    in.def = h->use_specialised && std::memcmp(&m, &DefaultConst<T>::value, sizeof m) == 0;
+    in.layout = h->layout; in.occupancy = h->occupancy; in.B = a->B; in.n_simd = h->n_simd;
+    in.verify = k.verify != 0; in.ladder_parallel = h->ladder_parallel != 0;
+    StepObsResetArgs ob;
+    in.obs_ok = !glsel::takes_quad(in) && obs_same_buffers(a, oa);      // the quad builds have no epilogue: nothing of oa / ra is looked at
+    in.obs_dim = 0;
+    if (in.obs_ok) {
+        ob.obs = oa->obs; ob.start_day = oa->start_day; ob.Np = oa->Np;
+        obs_clock_increments(h, &ob.doy_inc, &ob.hod_inc);
+        obs_layout(h, oa->Np, ob.moff, &ob.dim);
+        in.obs_dim = ob.dim;
     }
-    // Layout.  fp64 (the parity configuration): four lanes per environment, always -- coefficient blocks in LDS, no mailbox, no scratch
-    // to speak of; it scales with the batch in rounds of 16 384 environments (2.86 ms per round at n_sub 240).  fp32: four lanes per
-    // environment while the batch leaves SIMDs idle (B <= 16 384; shared crop parameters, default ODE), one lane per environment
-    // beyond.  glgym_set_layout(h, one | quad) overrides for fp32 -- handle state since round 5; the environment variable GLGYM_LAYOUT is
-    // only its INITIAL value, read once at glgym_create (changing os.environ afterwards has no effect on an existing handle).
-    const bool def = h->use_specialised && std::memcmp(&m, &DefaultConst<T>::value, sizeof m) == 0;
-    // verified steps (raw controls) on batches of at most one wavefront per SIMD at EIGHT lanes per environment: the ladder two rungs at a
-    // time (glgym_set_ladder_parallel, as glgym_evalF since round 5): two thirds of the latency, identical results and step_flags
-    const bool pair = k.verify && h->ladder_parallel && !a->crop_p && (size_t)8 * a->B <= (size_t)WAVE * h->n_simd;
-    if constexpr (sizeof(T) == 8) {
-        if (h->scheme == GLGYM_SCHEME_RK2) launch_quad_sch<T, GLGYM_SCHEME_RK2>(a, k, m, rw, qgrid, block, st, def, pair);
-        else if (h->scheme == GLGYM_SCHEME_RK3) launch_quad_sch<T, GLGYM_SCHEME_RK3>(a, k, m, rw, qgrid, block, st, def, pair);
-        else if (h->scheme == GLGYM_SCHEME_LS5) launch_quad_sch<T, GLGYM_SCHEME_LS5>(a, k, m, rw, qgrid, block, st, def, pair);
-        else launch_quad_sch<T, GLGYM_SCHEME_RK4>(a, k, m, rw, qgrid, block, st, def, pair);
-        HIPCHK(hipGetLastError());
-        return GLGYM_OK;
-    } else {
-        const int layout_env = h->layout;                        // handle state (glgym_set_layout): 0 auto, 1 one, 2 quad
-        const bool quad_ok = !pipe && !a->crop_p;
-        const int b_small = 4 * h->n_simd * 4;                   // 16 384 on MI355X: one quad-kernel round
-        if (quad_ok && (layout_env == 2 || (layout_env == 0 && a->B <= b_small))) {
-            if (h->scheme == GLGYM_SCHEME_RK2) launch_quad_sch<T, GLGYM_SCHEME_RK2>(a, k, m, rw, qgrid, block, st, def, pair);
-            else if (h->scheme == GLGYM_SCHEME_RK3) launch_quad_sch<T, GLGYM_SCHEME_RK3>(a, k, m, rw, qgrid, block, st, def, pair);
-            else if (h->scheme == GLGYM_SCHEME_LS5) launch_quad_sch<T, GLGYM_SCHEME_LS5>(a, k, m, rw, qgrid, block, st, def, pair);
-            else launch_quad_sch<T, GLGYM_SCHEME_RK4>(a, k, m, rw, qgrid, block, st, def, pair);
-            HIPCHK(hipGetLastError());
-            return GLGYM_OK;
-        }
-        if (pipe) {
-            hipLaunchKernelGGL((step_kernel<T, false, false, true>), grid, block, 0, st, k, m, rw, StepNoObs{});
-            HIPCHK(hipGetLastError());
-            return GLGYM_OK;
-        }
-        // The two-waves-per-SIMD build (256 registers; the windows' state in LDS since round 5: profiles/r05_occupancy2.txt) is what batches
-        // of at least two wavefronts per SIMD take (131 072 environments on MI355X: 1.08x there, 1.11x from 524 288); glgym_set_occupancy
-        // forces either build.  Default parameters and shared crop blocks only (the variants it is instantiated for).
-        const bool occ2 = def && !a->crop_p && (h->occupancy == 2 || (h->occupancy == 0 && (size_t)a->B >= (size_t)2 * WAVE * h->n_simd));
-        StepObsResetArgs ob;
-        const StepObsArgs* o = nullptr;
-        const StepObsResetArgs* r = nullptr;
-        if (oa && !oa->mask && oa->B == a->B && oa->ld == a->ld && oa->x == a->x && oa->u == a->u && oa->weather == a->weather &&
-            oa->weather_rows == a->weather_rows && oa->w_off == a->w_off && oa->timestep == a->timestep &&
-            ((uintptr_t)oa->obs & 15) == 0) {
-            ob.obs = oa->obs; ob.start_day = oa->start_day; ob.Np = oa->Np;
-            obs_clock_increments(h, &ob.doy_inc, &ob.hod_inc);
-            obs_layout(h, oa->Np, ob.moff, &ob.dim);
-            if (ob.dim > 0 && ob.dim <= (occ2 ? STEP_OBS_MAX_DIM_OCC2 : STEP_OBS_MAX_DIM_OCC1)) o = &ob;
-        }
-        if (o && ra && !a->crop_p && ra->B == a->B && ra->ld == a->ld && ra->x == a->x && ra->u == a->u && ra->timestep == a->timestep &&
-            ra->weather == a->weather && ra->weather_rows == a->weather_rows && ra->w_off == a->w_off && ra->start_rows &&
-            ra->start_days && ra->n_starts > 0 && ra->start_day && ra->start_day == oa->start_day && ra->episode) {
-            ob.term_obs = oa->term_obs; ob.w_off_rw = ra->w_off; ob.start_day_rw = ra->start_day; ob.episode = ra->episode;
-            ob.start_rows = ra->start_rows; ob.start_days = ra->start_days; ob.n_starts = ra->n_starts;
-            ob.seed = (unsigned long long)ra->seed;
-            r = &ob;
-        }
-        if (h->scheme == GLGYM_SCHEME_RK2) launch_step_sch<GLGYM_SCHEME_RK2>(a, k, m, rw, grid, block, st, def, occ2, o, r);
-        else if (h->scheme == GLGYM_SCHEME_RK3) launch_step_sch<GLGYM_SCHEME_RK3>(a, k, m, rw, grid, block, st, def, occ2, o, r);
-        else if (h->scheme == GLGYM_SCHEME_LS5) launch_step_sch<GLGYM_SCHEME_LS5>(a, k, m, rw, grid, block, st, def, occ2, o, r);
-        else launch_step_sch<GLGYM_SCHEME_RK4>(a, k, m, rw, grid, block, st, def, occ2, o, r);
-        HIPCHK(hipGetLastError());
-        if (o && fused) *fused = r ? 2 : 1;
-        return GLGYM_OK;
+    in.reset_ok = in.obs_ok && reset_same_buffers(a, oa, ra);
+    if (in.reset_ok) {
+        ob.term_obs = oa->term_obs; ob.w_off_rw = ra->w_off; ob.start_day_rw = ra->start_day; ob.episode = ra->episode;
+        ob.start_rows = ra->start_rows; ob.start_days = ra->start_days; ob.n_starts = ra->n_starts;
+        ob.seed = (unsigned long long)ra->seed;
     }
+    const glsel::StepChoice c = glsel::select_step(in);
+    if (c.error) { g_err = c.error; return GLGYM_EINVAL; }
+    const dim3 grid(c.grid), block(WAVE);
+    const glsel::StepBuild& b = c.build;
+    bool launched = false;
+    with_scheme(b.sch, [&](auto sch) {
+        constexpr int SCH = decltype(sch)::value;
+#define GL_LAUNCH_QUAD(F64, DEF, PIPE, CROP, PAIR)                                                                                    \
+        if constexpr (F64 == (sizeof(T) == 8))                                                                                       \
+            if (!launched && b == glsel::StepBuild{PAIR ? glsel::QUAD_PAIR : glsel::QUAD, F64, CROP, DEF, PIPE, SCH, 0, 1}) {        \
+                hipLaunchKernelGGL((step_kernel_quad<T, DEF, SCH, PIPE, CROP, PAIR>), grid, block, 0, st, k, m, rw);                 \
+                launched = true;                                                                                                     \
+            }
+        GL_STEP_QUAD_BUILDS(GL_LAUNCH_QUAD)
+#undef GL_LAUNCH_QUAD
+#define GL_LAUNCH_ONE(CROP, DEF, PIPE, EPI, OCC)                                                                                      \
+        if constexpr (sizeof(T) == 4 && glsel::one_lane_build_exists(PIPE, SCH))                                                     \
+            if (!launched && b == glsel::StepBuild{glsel::ONE_LANE, false, CROP, DEF, PIPE, SCH, EPI, OCC}) {                        \
+                hipLaunchKernelGGL((step_kernel<T, CROP, DEF, PIPE, SCH | EPI, OCC>), grid, block, 0, st, k, m, rw, epilogue_args<EPI>(ob)); \
+                launched = true;                                                                                                     \
+            }
+        GL_STEP_ONE_LANE_BUILDS(GL_LAUNCH_ONE)
+#undef GL_LAUNCH_ONE
+    });
+    // unreachable: every build select_step returns is in the lists (tests/test_step_select_host.py asserts it over the full product)
+    if (!launched) { g_err = "glgym_step: no kernel was built for the selected configuration (gl_step_select.hpp)"; return GLGYM_EINVAL; }
+    HIPCHK(hipGetLastError());
+    if (c.fused && fused) *fused = c.fused;
+    return GLGYM_OK;
 }
 
 // glgym_set_step_integrator(h, GLGYM_INTEGRATOR_BDF): one wavefront per environment in glgym_bdf.hip, fp64 integration for either dtype
@@ -2328,16 +2268,20 @@ int glgym_set_obs_modules(glgym_handle h, const int32_t* modules, int n)
 int glgym_obs_dim(glgym_handle h, int Np)
 {
     if (!h || Np < 0 || Np > OBS_MAX_NP) return GLGYM_EINVAL;
-    int dim = 0;
-    for (int i = 0; i < h->n_obs_modules; ++i)
-        dim += h->obs_modules[i] == GLGYM_OBS_FORECAST ? 5 * Np : OBS_MODULE_SIZE[h->obs_modules[i]];
+    int moff[6], dim;
+    obs_layout(h, Np, moff, &dim);
     return dim;
+}
+
+static bool reset_args_ok(const glgym_reset_args* a)
+{
+    return a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->timestep && a->weather && a->w_off;
 }
 
 int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);
-    if (!h || !a || a->B < 1 || a->ld < a->B || !a->x || !a->u || !a->timestep || !a->weather || !a->w_off) {
+    if (!h || !reset_args_ok(a)) {
         g_err = "glgym_reset: bad arguments";
         return GLGYM_EINVAL;
     }
@@ -2366,7 +2310,7 @@ int glgym_step_obs_reset(glgym_handle h, const glgym_step_args* a, const glgym_o
         g_err = "glgym_step_obs_reset: the masks of the observation and reset blocks must be NULL or the step's `done`";
         return GLGYM_EINVAL;
     }
-    if (!obs_args_ok(h, oa) || ra->B < 1 || ra->ld < ra->B || !ra->x || !ra->u || !ra->timestep || !ra->weather || !ra->w_off) {
+    if (!obs_args_ok(h, oa) || !reset_args_ok(ra)) {
         g_err = "glgym_step_obs_reset: bad observation or reset arguments";      // before the step is launched: nothing runs on bad arguments
         return GLGYM_EINVAL;
     }

@@ -33,6 +33,7 @@ from . import _lib as L
 from . import np_stream
 from .greenlight_model import _check_integrator, _check_tolerances
 from .parameters import init_default_params
+from .step_fusion import StepFusion
 from .utils import synthetic_weather
 
 try:  # spaces are optional plumbing: use gymnasium's when present
@@ -173,17 +174,17 @@ class LazyInfos:
 
 class _EpochLib:
     """The library as a TomatoVecEnv sees it: every call through it -- kernel launches, setters, whatever a caller does with `env._lib` and
-    `env._h` through raw pointers -- advances the environment's epoch first, which invalidates the token of a fused observation
-    (TomatoVecEnv._launch_obs).  Wrappers are made once per entry point."""
+    `env._h` through raw pointers -- advances the epoch of the environment's StepFusion first, which invalidates the tokens of a fused
+    step.  Wrappers are made once per entry point."""
 
-    def __init__(self, lib, env):
-        self.__dict__["_lib"], self.__dict__["_env"] = lib, env
+    def __init__(self, lib, fusion):
+        self.__dict__["_lib"], self.__dict__["_fusion"] = lib, fusion
 
     def __getattr__(self, name):
-        fn, env = getattr(self._lib, name), self._env
+        fn, advance = getattr(self._lib, name), self._fusion.advance
 
         def call(*args):
-            env._epoch += 1
+            advance()
             return fn(*args)
         self.__dict__[name] = call
         return call
@@ -231,20 +232,8 @@ class TomatoVecEnv:
         if not torch.cuda.is_available():
             raise L.GlgymError("TomatoVecEnv needs a HIP device (torch.cuda.is_available() is False); "
                                "there is no CPU fallback")
-        # fused observations (glgym_step_obs): _launch_step / _launch_obs
-        self._epoch = 0                     # advanced by every library call (_EpochLib) and by whatever else replaces a buffer
-        self._obs_token = None              # what a fused step left in obs_t, until something could have changed it
-        self._obs_followed = False          # the last _launch_step was followed by a full-mode _launch_obs(self.obs_t)
-        self._stepped = False               # a _launch_step has happened (the observation after a reset arms nothing)
-        self.n_fused_steps = 0              # steps launched through glgym_step_obs
-        self.n_obs_elided = 0               # full-mode _launch_obs calls that found their rows already written and launched nothing
-        # fused auto-reset (glgym_step_obs_reset): _launch_step / _launch_reset / _launch_obs
-        self._reset_token = None            # what a fused auto-reset left behind, until something could have changed it
-        self._pattern = -1                  # how far the calls since the last _launch_step have followed full obs (1), reset(done_t) (2), masked obs (3)
-        self._auto_reset_applied = None     # left by a step that has done its own auto-reset, until the next step (_launch_reset, _launch_obs)
-        self.n_fused_resets = 0             # steps whose auto-reset and terminal observations ran inside the step's own launch
-        self.n_reset_elided = 0             # _launch_reset(done_t) / masked _launch_obs calls that found their work done and launched nothing
-        self._lib = _EpochLib(L.load(), self)
+        self._fusion = StepFusion()         # what the last _launch_step has already done: _launch_step / _launch_obs / _launch_reset
+        self._lib = _EpochLib(L.load(), self._fusion)
         self.torch = torch
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -378,11 +367,19 @@ class TomatoVecEnv:
         self.observation_space = _box(lo, hi, (self.obs_dim,), np.float32)
         self.action_space = _box(-1.0, 1.0, (L.NU,), np.float32)
         self._actions = None
-        self._keep_applied_u, self._u_applied_T = False, None
+        self._action_src = self.action_t    # where the step kernel reads the actions (step_tensor: the caller's tensor where it can be read in place)
+        self.freeze_crop_noise = False      # True: no per-step crop noise draw (a hand-set per-env block is held)
+        self._keep_applied_u, self._u_applied_T, self._u_applied_valid = False, None, False
+        self._hod_table_t = None
         self.reset_infos: List[dict] = [{} for _ in range(self.B)]
         # pinned host staging for the numpy (SB3) path: the 1 KB/env observation block dominates the D2H traffic
         self._obs_host = [torch.empty(self.B, self.obs_dim, dtype=torch.float32).pin_memory() for _ in range(2)]
         self._obs_flip = 0
+
+    n_fused_steps = property(lambda self: self._fusion.n_fused_steps)        # the StepFusion's counters
+    n_obs_elided = property(lambda self: self._fusion.n_obs_elided)
+    n_fused_resets = property(lambda self: self._fusion.n_fused_resets)
+    n_reset_elided = property(lambda self: self._fusion.n_reset_elided)
 
     def _obs_to_host(self, obs_t):
         """D2H into one of two pinned buffers (alternating) and return a numpy VIEW of it: the array stays valid
@@ -462,31 +459,11 @@ class TomatoVecEnv:
         """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).
         rng="numpy": glgym_rng_reset_draw takes choice(years), choice(days) from each masked environment's stream first, and
         glgym_reset, called without a start table, initialises from the w_off it wrote.
-
-        _launch_reset(self.done_t) right after a step whose kernel has already reset the finished environments (_launch_step) launches
-        nothing, under the conditions of _reset_elided().  Where those do not hold (a setter call, a torch write to one of the buffers, a
-        reset with another mask came between) the reset of that step's `done` mask is still the one the step has applied, and
-        reset_kernel, which counts episodes and draws a new start each time it runs, must not run over it a second time: the first
-        _launch_reset(done_t) after such a step launches nothing either while done_t is unwritten (the mask is the one the step used).
-        After an in-place write to done_t the mask is whatever the caller made of it: the reset then runs over done_t AND timestep_t != 0.
-        A step leaves timestep_t >= 1 in every environment it did not reset, so this takes out exactly the environments the step has
-        reset and keeps the ones the caller added; an environment at timestep 0 is at an episode start already.  If timestep_t was
-        written as well nothing tells the two apart, and the call raises instead of resetting twice."""
-        token, self._reset_token = self._reset_token, None
-        self._pattern = 2 if (mask_t is self.done_t and self._pattern == 1) else -1
-        if mask_t is self.done_t and self._reset_elided(token):
-            self._reset_token = token                      # the masked observation that follows is part of the same fused step
+        After a step that has done its own auto-reset the call launches nothing, or runs over the environments the caller added to
+        done_t only (step_fusion.StepFusion)."""
+        launch, mask_t = self._fusion.reset(self, mask_t)
+        if not launch:
             return
-        st = self._auto_reset_applied
-        if mask_t is self.done_t and st is not None and not st["reset_seen"]:
-            st["reset_seen"] = True
-            if st["done"] == (self.done_t.data_ptr(), self.done_t._version):
-                return                                     # this step's reset, already applied by the step's own launch
-            if st["timestep"] != (self.timestep_t.data_ptr(), self.timestep_t._version):
-                raise RuntimeError("done_t and timestep_t were both written between a step with a fused auto-reset and its "
-                                   "_launch_reset(done_t): the environments that step has already reset cannot be told from the ones "
-                                   "added to the mask; reset those through a mask tensor of their own")
-            mask_t = st["added"] = self.done_t * (self.timestep_t != 0).to(self.done_t.dtype)
         mask_ptr = mask_t.data_ptr() if mask_t is not None else None
         if self.rng == "numpy":
             L.check(self._lib.glgym_rng_reset_draw(self._h, self.B, self.ld, mask_ptr, self.rng_state_t.data_ptr(), self.start_grid[0],
@@ -514,114 +491,42 @@ class TomatoVecEnv:
                          mask_t.data_ptr() if mask_t is not None else None,
                          term_t.data_ptr() if term_t is not None else None)
 
-    def _obs_deps(self):
-        """Address and torch version counter of every tensor a full-mode observation reads or lands in."""
-        return tuple((t.data_ptr(), t._version) for t in (self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t,
-                                                          self.weather_t, self.obs_t))
-
-    def _reset_deps(self):
-        """Address and torch version counter of every tensor a fused auto-reset reads or writes."""
-        return tuple((t.data_ptr(), t._version) for t in (self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t,
-                                                          self.done_t, self.obs_t, self.term_obs_t, self.weather_t))
-
-    def _reset_elided(self, token):
-        """True, and counted, if `token` is that of a fused auto-reset nothing has come after: the epoch is the one recorded after that
-        step (no library call through this environment since: no reset with another mask, no setter, no observation that had to be
-        launched) and the version counters of x_T, u_T, timestep_t, w_off_t, start_day_t, episode_t, done_t, obs_t, term_obs_t and
-        weather_t are the recorded ones (no in-place torch write to any of them or to a view of them)."""
-        if token is None or token != (self._epoch, self._reset_deps()):
-            return False
-        self.n_reset_elided += 1
-        return True
-
     def _launch_obs(self, out_t, mask_t=None, term_t=None):
         """glgym_obs into out_t: every row (mask_t None, "full mode"), or the rows of mask_t after saving them to term_t.
-
-        A full-mode call right after a fused step (_launch_step) launches nothing: that step's kernel has already written exactly these
-        rows.  The call returns without a launch if and only if (a) out_t is the very obs_t the fused step wrote, (b) the epoch is the
-        one recorded after that step -- every call into the library through this environment (reset, rule-based controller, crop noise,
-        any setter, the planner, raw-pointer calls through env._lib) and every assignment that replaces a buffer advances it -- and (c) the
-        torch version counters of x_T, u_T, timestep_t, w_off_t, start_day_t, weather_t and obs_t are the recorded ones.  (c) is the
-        safety argument for torch-side writes: an in-place operation on any of these tensors or on a view of them (env.x.copy_(...),
-        x_T.mul_(...), obs_t.fill_(...)) between the two calls changes a counter, so the observation is computed again from what is in
-        memory, as it always was.  The token is single-use.  In every other case the call does what it always did.
-
-        The masked call _launch_obs(self.obs_t, self.done_t, self.term_obs_t) after a fused auto-reset and its elided _launch_reset(done_t)
-        launches nothing either (_reset_elided): the terminal rows are in term_obs_t and the rows of the new episodes in obs_t.  Where it
-        is not elided it computes those rows again from memory and leaves term_obs_t as that step wrote it (see _launch_reset)."""
+        Launches nothing where the last step's own launch has written these rows already, and does not save terminal rows a second time
+        (step_fusion.StepFusion)."""
         if mask_t is None:
-            token, self._obs_token = self._obs_token, None
-            self._pattern = 1 if (out_t is self.obs_t and self._pattern == 0) else -1
-            if out_t is self.obs_t:
-                self._obs_followed = self._stepped
-                if token is not None and token == (id(out_t), self._epoch, self._obs_deps()):
-                    self.n_obs_elided += 1
-                    return
-            self._reset_token = None                       # a launched observation: the pattern of a fused auto-reset is broken
+            launches = [] if self._fusion.full_obs(self, out_t) else [(None, term_t)]
         else:
-            token, self._reset_token = self._reset_token, None
-            whole = out_t is self.obs_t and mask_t is self.done_t and term_t is self.term_obs_t
-            elide = whole and self._pattern == 2 and self._reset_elided(token)
-            self._pattern = 3 if (whole and self._pattern == 2) else -1
-            if elide:
-                return
-            st = self._auto_reset_applied
-            if mask_t is self.done_t and term_t is not None and st is not None and not st["obs_seen"]:
-                # not elided, but the step has saved the terminal rows and reset these environments: saving again would put the rows of
-                # the new episodes into term_obs_t.  The rows are computed again from what is in memory, without the save; the
-                # environments a written done_t added (_launch_reset) get both, first.
-                if not whole:
-                    raise RuntimeError("the terminal observations of a step with a fused auto-reset are in term_obs_t; a masked "
-                                       "_launch_obs over done_t after it takes obs_t and term_obs_t")
-                st["obs_seen"] = True
-                if st["added"] is not None:
-                    L.check(self._lib.glgym_obs(self._h, C.byref(self._obs_args(out_t, st["added"], term_t)), self._stream()), "glgym_obs")
-                term_t = None
-        L.check(self._lib.glgym_obs(self._h, C.byref(self._obs_args(out_t, mask_t, term_t)), self._stream()), "glgym_obs")
+            launches = self._fusion.masked_obs(self, out_t, mask_t, term_t)
+        for mask_t, term_t in launches:
+            L.check(self._lib.glgym_obs(self._h, C.byref(self._obs_args(out_t, mask_t, term_t)), self._stream()), "glgym_obs")
 
     def _launch_step(self, raw_control: bool, want_obs: Optional[bool] = None, with_reset: Optional[bool] = None):
-        """One glgym_step.  want_obs True: glgym_step_obs, which also leaves the full-mode observation of the new state in obs_t (one
-        launch where the library has a fused kernel for this configuration, step and observation kernels back to back elsewhere); the
-        full-mode _launch_obs(self.obs_t) that follows finds it there.  False: the plain step.  None (a bare call, as bench.py's loop):
-        adaptive -- fused when the previous step of this environment was followed by a full-mode _launch_obs(self.obs_t), so that loops
-        that never ask for observations never pay for them, and a fused observation that went unconsumed ends the fusing.
-
-        with_reset True (step_tensor, capture_step_graph; auto_reset only): glgym_step_obs_reset -- the step, the full-mode observation,
-        the reset of the environments this step finished (mask done_t) and their masked observation with the terminal rows saved to
-        term_obs_t, in one launch where the library has a kernel with the auto-reset epilogue for this configuration and back to back
-        elsewhere.  None with a bare call: adaptive again -- only with auto_reset, and only when the previous step of this environment was
-        followed by exactly _launch_obs(obs_t), _launch_reset(done_t), _launch_obs(obs_t, done_t, term_obs_t) in this order (bench.py's
-        loop).  After such a step these three calls launch nothing (_launch_obs, _reset_elided); a fused reset that is not followed by
-        the three ends the fusing.  Only a caller's own three calls arm it: step_tensor and capture_step_graph leave it unarmed.
-        CONTRACT: after a step with a fused auto-reset, x_T, u_T, timestep_t, w_off_t, start_day_t and
-        episode_t hold the POST-RESET state of the finished environments and obs_t the first observation of their new episodes -- what
-        step_tensor has always left behind -- already when _launch_step returns; done_t, reward_t, info_T, step_flags_t and the metrics
-        are the step's.  A torch write between the step and the follow-up calls therefore lands on the post-reset state, and the follow-up
-        calls that are not elided never apply that step's reset or save its terminal rows a second time (_launch_reset, _launch_obs).
-        rng="numpy" (start draws from device streams between step and reset) never takes this path."""
+        """One glgym_step.  want_obs True: glgym_step_obs, which also leaves the full-mode observation of the new state in obs_t; False:
+        the plain step.  with_reset True (auto_reset, rng="philox" only): glgym_step_obs_reset -- the step, the full-mode observation, the
+        reset of the environments this step finished (mask done_t) and their masked observation with the terminal rows saved to
+        term_obs_t.  Either is one launch where the library has a kernel with that epilogue for this configuration, and back to back
+        launches elsewhere.  None (a bare call, as bench.py's loop): adaptive, by what followed the previous step.  The rules, and the
+        contract on what the buffers hold after a fused auto-reset: step_fusion.StepFusion."""
         if self._env_at_create is not None and tuple(os.environ.get(k) for k in ("GLGYM_LAYOUT", "GLGYM_OCC", "GLGYM_VERIFY")) != self._env_at_create:
             import warnings
             warnings.warn("GLGYM_LAYOUT / GLGYM_OCC / GLGYM_VERIFY changed after this TomatoVecEnv was created: they are read once, at glgym_create, "
                           "and have no effect on an existing handle -- use set_layout() / set_occupancy() / set_verify()", RuntimeWarning, stacklevel=3)
             self._env_at_create = None                     # once
-        fuse = self._obs_followed if want_obs is None else bool(want_obs)
-        if with_reset is None:
-            with_reset = want_obs is None and self._pattern == 3
-        with_reset = bool(with_reset) and fuse and self.auto_reset and self.rng != "numpy"
-        self._obs_followed, self._obs_token, self._stepped = False, None, True
-        self._reset_token, self._pattern, self._auto_reset_applied = None, 0, None
+        fuse, with_reset = self._fusion.begin_step(want_obs, with_reset, self.auto_reset and self.rng != "numpy")
         if self.rng == "numpy":
-            if not getattr(self, "freeze_crop_noise", False):   # tomato_env.py:118: 34 draws every step, also at scale 0 (no block: streams advance)
+            if not self.freeze_crop_noise:   # tomato_env.py:118: 34 draws every step, also at scale 0 (no block: streams advance)
                 L.check(self._lib.glgym_rng_crop_noise(self._h, self.crop_T.data_ptr() if self.crop_T is not None else None, self.B, self.ld,
                                                        self.uncertainty_scale, self.rng_state_t.data_ptr(), self._stream()),
                         "glgym_rng_crop_noise")
-        elif self.crop_T is not None and not getattr(self, "freeze_crop_noise", False):       # noise.py: a fresh draw every step
+        elif self.crop_T is not None and not self.freeze_crop_noise:       # noise.py: a fresh draw every step
             L.check(self._lib.glgym_crop_noise(self._h, self.crop_T.data_ptr(), self.B, self.ld,
                                                self.uncertainty_scale, self.seed_value, self._draw, self._stream()),
                     "glgym_crop_noise")
             self._draw += 1
         a = L.make_step_args(self.B, self.ld, self.x_T.data_ptr(), self.u_T.data_ptr(),
-                       None if raw_control else getattr(self, "_action_src", self.action_t).data_ptr(),
+                       None if raw_control else self._action_src.data_ptr(),
                        self.ctrl_T.data_ptr() if raw_control else None, self.weather_t.data_ptr(), self.weather_rows,
                        self.w_off_t.data_ptr(), self.timestep_t.data_ptr(),
                        self.crop_T.data_ptr() if self.crop_T is not None else None, self.N,
@@ -635,16 +540,10 @@ class TomatoVecEnv:
             L.check(self._lib.glgym_step_obs_reset(self._h, C.byref(a), C.byref(self._obs_args(self.obs_t, None, self.term_obs_t)),
                                                    C.byref(self._reset_args(self.done_t)), self._stream(), C.byref(one)),
                     "glgym_step_obs_reset")
-            self.n_fused_steps += 1
-            self.n_fused_resets += one.value
-            self._obs_token = (id(self.obs_t), self._epoch, self._obs_deps())
-            self._reset_token = (self._epoch, self._reset_deps())
-            self._auto_reset_applied = dict(done=(self.done_t.data_ptr(), self.done_t._version), reset_seen=False, obs_seen=False, added=None,
-                                            timestep=(self.timestep_t.data_ptr(), self.timestep_t._version))
+            self._fusion.step_launched(self, True, one.value)
             return
         L.check(self._lib.glgym_step_obs(self._h, C.byref(a), C.byref(self._obs_args(self.obs_t)), self._stream()), "glgym_step_obs")
-        self.n_fused_steps += 1
-        self._obs_token = (id(self.obs_t), self._epoch, self._obs_deps())
+        self._fusion.step_launched(self, False)
 
     # ---- tensor interface (no host synchronisation) ---------------------------------------------
     def reset_tensor(self, seed: Optional[int] = None):
@@ -703,7 +602,7 @@ class TomatoVecEnv:
             self._launch_reset(self.done_t)
             if want_obs:
                 self._launch_obs(self.obs_t, self.done_t, self.term_obs_t)
-        self._pattern = -1               # these were step_tensor's own calls: they arm no bare _launch_step
+        self._fusion.own_calls()         # these were step_tensor's own calls: they arm no bare _launch_step
         return self.obs_t, self.reward_t[:self.B], self.done_t, self.info_T[:, :self.B]
 
     # ---- SB3 VecEnv calling convention ------------------------------------------------------------
@@ -741,7 +640,7 @@ class TomatoVecEnv:
         # infos: SB3 wants a list of per-env dicts.  Built from two bulk D2H copies (info block, controls) with
         # zip over Python lists -- the cheapest pure-Python construction (about 1 us per env per key).
         rows = info_T.double().t().cpu().numpy()
-        applied = self._u_applied_T if (self.auto_reset and getattr(self, "_u_applied_valid", False)) else self.u_T
+        applied = self._u_applied_T if (self.auto_reset and self._u_applied_valid) else self.u_T
         ctrl = applied[:, :self.B].t().double().cpu().numpy()
         term = None
         if self.auto_reset and dones.any():
@@ -842,7 +741,7 @@ class TomatoVecEnv:
             raise ValueError(f"weather_data has {table.shape[0]} rows, an episode needs {need}")
         self._weather_data = table
         self.weather_rows = int(table.shape[0])
-        self._epoch += 1                    # another table, another row count: a fused observation of the old one is void
+        self._fusion.advance()              # another table, another row count: a fused observation of the old one is void
         self.weather_t = torch.as_tensor(table, dtype=self.tdtype, device=self.device).contiguous()
         self.start_rows = np.zeros(1, dtype=np.int64)
         self.start_days = np.asarray(self.start_days[:1], dtype=np.float32)
@@ -875,7 +774,7 @@ class TomatoVecEnv:
         drifts by ulps and reads 17.999999999999996 where the product reads 18.0 -- and the rule-based controller compares the clock with
         whole hours (baseline.py:76-77, 107, 113): 13 of 960 steps of the dt = 300 hold-out switch the lamps one step apart.  The table
         holds the reference's sum for every timestep of an episode; timestep indexes it."""
-        if getattr(self, "_hod_table_t", None) is None:
+        if self._hod_table_t is None:
             t = np.empty(self.N + 4, dtype=np.float64)
             h = 0.0
             for k in range(len(t)):
@@ -929,7 +828,7 @@ class TomatoVecEnv:
                 self._launch_reset(self.done_t)
                 if want_obs:
                     self._launch_obs(self.obs_t, self.done_t, self.term_obs_t)
-            self._pattern = -1              # the captured sequence's own calls: they arm no bare _launch_step
+            self._fusion.own_calls()        # the captured sequence's own calls: they arm no bare _launch_step
 
         # warm-up on a side stream (torch's capture protocol), with the state restored afterwards
         state = [self.x_T, self.u_T, self.timestep_t, self.w_off_t, self.start_day_t, self.episode_t, self.obs_t]

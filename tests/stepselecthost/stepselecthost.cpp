@@ -1,0 +1,55 @@
+// Host (g++) instantiation of the product's csrc/gl_step_select.hpp -- tests only (tests/test_step_select_host.py): the selection in
+// batches, and the build list expanded into rows.
+#include "gl_step_select.hpp"
+
+using namespace glsel;
+
+namespace {
+void put(const StepBuild& b, int* o)
+{
+    o[0] = b.family; o[1] = b.f64; o[2] = b.crop; o[3] = b.def; o[4] = b.pipe; o[5] = b.sch; o[6] = b.epi; o[7] = b.occ;
+}
+}  // namespace
+
+extern "C" {
+
+// in: n rows of 15 ints, StepSelectIn's fields in their order; out: n rows of 11 ints: error (0/1), the build's 8 fields, grid, fused
+void stepselect_batch(int n, const int* in, int* out)
+{
+    for (int r = 0; r < n; ++r, in += 15, out += 11) {
+        const StepSelectIn s{in[0] != 0, in[1], in[2] != 0, in[3] != 0, in[4] != 0, in[5], in[6], in[7], in[8], in[9] != 0, in[10] != 0,
+                             in[11] != 0, in[12], in[13] != 0};
+        const StepChoice c = select_step(s);
+        out[0] = c.error != nullptr;
+        put(c.build, out + 1);
+        out[9] = (int)c.grid; out[10] = c.fused;
+    }
+}
+
+const char* stepselect_error_text()
+{
+    return select_step(StepSelectIn{false, RK4, true, true, false, 0, 0, 1, 1, false, false, false, 0, false}).error;
+}
+
+// the build list as rows of 8 ints (at most cap rows are written); returns the number of builds
+int stepselect_builds(int* out, int cap)
+{
+    int n = 0;
+    for (int sch = 0; sch < 4; ++sch) {
+#define ROW_ONE(CROP, DEF, PIPE, EPI, OCC)                                                         \
+        if (one_lane_build_exists(PIPE, sch)) {                                                    \
+            if (n < cap) put(StepBuild{ONE_LANE, false, CROP, DEF, PIPE, sch, EPI, OCC}, out + 8 * n); \
+            ++n;                                                                                   \
+        }
+        GL_STEP_ONE_LANE_BUILDS(ROW_ONE)
+#undef ROW_ONE
+#define ROW_QUAD(F64, DEF, PIPE, CROP, PAIR)                                                       \
+        if (n < cap) put(StepBuild{PAIR ? QUAD_PAIR : QUAD, F64, CROP, DEF, PIPE, sch, 0, 1}, out + 8 * n); \
+        ++n;
+        GL_STEP_QUAD_BUILDS(ROW_QUAD)
+#undef ROW_QUAD
+    }
+    return n;
+}
+
+}  // extern "C"
