@@ -2459,6 +2459,53 @@ int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* str
     return GLGYM_OK;
 }
 
+// the cross-entropy method's stages (gl_cem.hpp): every check that needs no device memory happens here, before anything is launched
+int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_sample: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_sample", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->K < 1 || a->H < 1 || (int64_t)a->P * a->K > INT32_MAX - 255 || !a->mean || !a->std || !a->actions ||
+        !(a->beta >= 0.0 && a->beta < 1.0) || a->carry < 0 ||
+        (a->carry > 0 && (!a->prev_actions || !a->prev_elite_k || !a->prev_n_elite || a->prev_E < a->carry || a->prev_actions == a->actions))) {
+        g_err = "glgym_plan_sample: bad arguments (P, K, H < 1, null pointer, beta outside [0, 1), carry < 0, or with carry > 0: a missing "
+                "prev_ member, carry > prev_E, or prev_actions == actions -- sample into the other of two blocks)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    HIPCHK(plan_sample_launch(*a, (hipStream_t)stream));
+    return GLGYM_OK;
+}
+
+int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_elites: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_elites", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->K < 1 || a->E < 1 || a->E > a->K || (int64_t)a->P * a->K > INT32_MAX - 255 || !a->ret || !a->failed || !a->elite_k ||
+        !a->n_elite) {
+        g_err = "glgym_plan_elites: bad arguments (P, K < 1, E outside 1..K, or null pointer)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    HIPCHK(plan_elites_launch(*a, (hipStream_t)stream));
+    return GLGYM_OK;
+}
+
+int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_refit: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_refit", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->K < 1 || a->H < 1 || a->H > 65535 || a->E < 1 || a->E > a->K || (int64_t)a->P * a->K > INT32_MAX - 255 ||
+        !a->actions || !a->elite_k || !a->n_elite || !a->mean || !a->std || !a->mean_out || !a->std_out ||
+        !(a->alpha >= 0.0 && a->alpha < 1.0) || !(a->min_std >= 0.0 && std::isfinite(a->min_std))) {
+        g_err = "glgym_plan_refit: bad arguments (P, K, H < 1, H > 65 535, E outside 1..K, null pointer, alpha outside [0, 1), or min_std "
+                "negative or not finite)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    HIPCHK(plan_refit_launch(*a, (hipStream_t)stream));
+    return GLGYM_OK;
+}
+
 int glgym_rule_based(glgym_handle h, const glgym_rule_cfg* cfg, const glgym_rule_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);

@@ -13,3 +13,7 @@ hipError_t plan_fork_launch(const glgym_plan_fork_args& a, hipStream_t stream);
 template <class T>
 hipError_t plan_accumulate_launch(const glgym_plan_accumulate_args& a, hipStream_t stream);
 hipError_t plan_select_launch(const glgym_plan_select_args& a, hipStream_t stream);
+// The cross-entropy method's stages (gl_cem.hpp): independent of the handle's dtype (the action block is f32, the returns double).
+hipError_t plan_sample_launch(const glgym_plan_sample_args& a, hipStream_t stream);
+hipError_t plan_elites_launch(const glgym_plan_elites_args& a, hipStream_t stream);
+hipError_t plan_refit_launch(const glgym_plan_refit_args& a, hipStream_t stream);

@@ -9,9 +9,19 @@
 // shuffles; the action block [H][P*K][6] f32 is read with lanes over k, 6 consecutive floats each, so a wavefront touches 1 536
 // contiguous bytes per load round.  The MPPI mean runs one wavefront per (parent, horizon step): the K returns are re-read from L2 by
 // each (9 bytes per candidate against the 24 bytes of its action row), which keeps the call free of workspace and allocation.
-// No LDS, no atomics, plain vector stores.
+// These four use no LDS; no kernel here uses atomics, all stores are plain vector stores.
+//
+// The cross-entropy method's stages (glgym_plan_sample / _elites / _refit; scalar logic in gl_cem.hpp, instantiated on the host by
+// tests/cemhost/cemhost.cpp).  sample: lane = child, four wavefronts per 64 children share the horizon's steps (the normals are the
+// cost; the recurrence along h runs per lane over normals staged in LDS); 6 consecutive floats per lane, so a wavefront writes 1 536
+// contiguous bytes per step; the mean / std rows of a parent are broadcast reads.  elites: lane = candidate, ceil(K / 64) blocks of
+// four wavefronts per parent; the parent's K returns pass through LDS in tiles of 256 (every lane reads the same LDS address, a
+// broadcast) and each thread counts the candidates that come before its own -- the rank IS the output slot, so there is no sort
+// network and no atomic.  refit: one wavefront per (parent, horizon step), lanes stride over the elites, two passes over at most E
+// gathered rows.
 #include "glgym_plan.h"
 
+#include "gl_cem.hpp"
 #include "gl_plan.hpp"
 
 namespace {
@@ -130,7 +140,126 @@ __global__ __launch_bounds__(WAVE) void plan_mean_kernel(glgym_plan_select_args 
     }
 }
 
+// grid = ceil(C / 64) blocks of SAMPLE_WAVES wavefronts: lane = child, wave w draws the normals of the steps h = g*SAMPLE_WAVES + w
+// (the costly part: two Philox blocks, three ln / sqrt / sin / cos in double) and stages them in LDS; every lane then runs its child's
+// recurrence n_h = beta n_{h-1} + sb e_h over the group's steps in step order -- 6 x SAMPLE_WAVES multiply-adds, repeated by each wave
+// rather than exchanged -- keeps n at the group's end, and writes the row of its own step: 1 536 contiguous bytes per wave.
+constexpr int SAMPLE_WAVES = 4;
+__global__ __launch_bounds__(SAMPLE_WAVES * WAVE) void plan_sample_kernel(glgym_plan_sample_args a)
+{
+    __shared__ double s_e[SAMPLE_WAVES][NU][WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int n_child = a.P * a.K;
+    const int c_raw = blockIdx.x * WAVE + lane;
+    const bool live = c_raw < n_child;
+    const int c = live ? c_raw : n_child - 1;           // lanes past the end shadow the last child and store nothing
+    const int p = c / a.K, k = c - p * a.K;
+    const uint64_t D = a.draw_index + (a.draw_base ? *a.draw_base : 0ull);
+    int src = 0;
+    const int kind = glcem::reserved(p, k, a.K, a.carry, a.prev_E, a.prev_elite_k, a.prev_n_elite, &src);
+    const double sb = glcem::sb_of(a.beta);
+    double n[NU] = {0, 0, 0, 0, 0, 0};
+    for (int g = 0; g < a.H; g += SAMPLE_WAVES) {       // block-uniform trip count: every thread reaches both barriers
+        const int h = g + w;
+        if (h < a.H && kind == 0) {
+            double e[NU];
+            glcem::normals_of(c, h, D, a.seed, e);
+            for (int j = 0; j < NU; ++j) s_e[w][j][lane] = e[j];
+        }
+        __syncthreads();
+        double mine[NU] = {0, 0, 0, 0, 0, 0};
+        if (kind == 0) {
+            const int n_steps = a.H - g < SAMPLE_WAVES ? a.H - g : SAMPLE_WAVES;
+            for (int s = 0; s < n_steps; ++s) {
+                double e[NU];
+                for (int j = 0; j < NU; ++j) e[j] = s_e[s][j][lane];
+                glcem::colour(g + s, a.beta, sb, e, n);
+                if (s == w)
+                    for (int j = 0; j < NU; ++j) mine[j] = n[j];
+            }
+        }
+        if (live && h < a.H) glcem::write_row(kind, src, h, p, c, a.P, a.K, a.mean, a.std, mine, a.prev_actions, a.actions);
+        __syncthreads();                                // the group's normals have been read by everyone
+    }
+}
+
+// grid = P * n_chunks blocks of ELITE_WAVES wavefronts: block (p, i) ranks the 64 candidates i*64 .. i*64 + 63 of parent p, lane =
+// candidate.  The parent's keys (return, or NaN if not admissible) pass through LDS in tiles of 256; wave w counts the tile's
+// w-th 64 keys against its lane's candidate -- each LDS read is a broadcast -- and the four partial ranks are added through LDS.
+constexpr int ELITE_WAVES = glcem::TILE / glcem::CHUNK;
+__global__ __launch_bounds__(glcem::TILE) void plan_elites_kernel(glgym_plan_elites_args a, int n_chunks)
+{
+    constexpr int TILE = glcem::TILE, CHUNK = glcem::CHUNK;
+    __shared__ double s_key[TILE];
+    __shared__ int s_rank[ELITE_WAVES][CHUNK];
+    const int p = blockIdx.x / n_chunks, tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int k0 = (blockIdx.x - p * n_chunks) * CHUNK, t = k0 + lane;
+    const double* ret = a.ret + (size_t)p * a.K;
+    const uint8_t* failed = a.failed + (size_t)p * a.K;
+    const double rk = t < a.K ? glcem::key(ret[t], failed[t]) : __builtin_nan("");
+    int rank = 0, n_adm = 0;
+    for (int j0 = 0; j0 < a.K; j0 += TILE) {            // block-uniform trip count: every thread reaches both barriers
+        const int j = j0 + tid;
+        const double kj = j < a.K ? glcem::key(ret[j], failed[j]) : __builtin_nan("");
+        s_key[tid] = kj;
+        n_adm += __syncthreads_count(kj == kj);         // a barrier, and the tile's number of admissible candidates
+        const int c0 = j0 + w * CHUNK, n = a.K - c0 < CHUNK ? a.K - c0 : CHUNK;
+        if (n > 0) rank += glcem::count_chunk(s_key + w * CHUNK, c0, n, rk, t, k0);
+        __syncthreads();                                // the tile has been read by everyone
+    }
+    s_rank[w][lane] = rank;
+    __syncthreads();
+    if (w == 0) {
+        for (int i = 1; i < ELITE_WAVES; ++i) rank += s_rank[i][lane];
+        glcem::store_rank(t, a.K, a.E, rk == rk, rank, n_adm, a.elite_k + (size_t)p * a.E, a.n_elite + p);
+    }
+}
+
+// grid = (P, H), one wavefront each
+__global__ __launch_bounds__(WAVE) void plan_refit_kernel(glgym_plan_refit_args a)
+{
+    const int p = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+    int n = a.n_elite[p];
+    n = n < 0 ? 0 : (n > a.E ? a.E : n);
+    const int32_t* elite = a.elite_k + (size_t)p * a.E;
+    const float* rows = a.actions + ((size_t)h * a.P + p) * a.K * NU;
+    const size_t o = ((size_t)h * a.P + p) * NU;
+    double acc[NU], m[NU], s[NU];
+    const bool ok = glcem::lane_sum(lane, n, elite, a.K, rows, acc);
+    const bool keep = n == 0 || __any(!ok);             // wave-uniform
+    if (!keep) {
+        for (int j = 0; j < NU; ++j) m[j] = wave_sum(acc[j]) / (double)n;
+        glcem::lane_sqdev(lane, n, elite, rows, m, acc);
+        for (int j = 0; j < NU; ++j) s[j] = sqrt(wave_sum(acc[j]) / (double)n);
+    }
+    if (lane == 0)
+        for (int j = 0; j < NU; ++j) {
+            const float mean = a.mean[o + j], sd = a.std[o + j];      // read before the (possibly aliased) stores
+            a.mean_out[o + j] = keep ? mean : (float)glcem::blend_mean(a.alpha, mean, m[j]);
+            a.std_out[o + j] = keep ? sd : (float)glcem::blend_std(a.alpha, sd, s[j], a.min_std);
+        }
+}
+
 }  // namespace
+
+hipError_t plan_sample_launch(const glgym_plan_sample_args& a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(plan_sample_kernel, dim3((unsigned)(((int64_t)a.P * a.K + WAVE - 1) / WAVE)), dim3(SAMPLE_WAVES * WAVE), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t plan_elites_launch(const glgym_plan_elites_args& a, hipStream_t stream)
+{
+    const int n_chunks = (a.K + glcem::CHUNK - 1) / glcem::CHUNK;
+    hipLaunchKernelGGL(plan_elites_kernel, dim3((unsigned)((int64_t)a.P * n_chunks)), dim3(glcem::TILE), 0, stream, a, n_chunks);
+    return hipGetLastError();
+}
+
+hipError_t plan_refit_launch(const glgym_plan_refit_args& a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(plan_refit_kernel, dim3(a.P, a.H), dim3(WAVE), 0, stream, a);
+    return hipGetLastError();
+}
 
 template <class T>
 hipError_t plan_fork_launch(const glgym_plan_fork_args& a, hipStream_t stream)

@@ -170,6 +170,24 @@ class PlanSelectArgs(C.Structure):
                 ("mean_sequence", C.c_void_p)]
 
 
+class PlanSampleArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("H", C.c_int32), ("mean", C.c_void_p),
+                ("std", C.c_void_p), ("beta", C.c_double), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p),
+                ("actions", C.c_void_p), ("carry", C.c_int32), ("prev_E", C.c_int32), ("prev_actions", C.c_void_p),
+                ("prev_elite_k", C.c_void_p), ("prev_n_elite", C.c_void_p)]
+
+
+class PlanElitesArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("E", C.c_int32), ("ret", C.c_void_p),
+                ("failed", C.c_void_p), ("elite_k", C.c_void_p), ("n_elite", C.c_void_p)]
+
+
+class PlanRefitArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("H", C.c_int32), ("E", C.c_int32),
+                ("actions", C.c_void_p), ("elite_k", C.c_void_p), ("n_elite", C.c_void_p), ("alpha", C.c_double),
+                ("min_std", C.c_double), ("mean", C.c_void_p), ("std", C.c_void_p), ("mean_out", C.c_void_p), ("std_out", C.c_void_p)]
+
+
 def make_plan_args(cls, *args, **kw):
     """cls(...) of one of the Plan*Args structs without the leading struct_size, which is filled in here."""
     return cls(C.sizeof(cls), *args, **kw)
@@ -243,6 +261,9 @@ PROTOTYPES = {
     "glgym_plan_accumulate": (C.c_int, [C.c_void_p, C.POINTER(PlanAccumulateArgs), C.c_void_p]),
     "glgym_plan_rollout": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutArgs), C.c_void_p]),
     "glgym_plan_select": (C.c_int, [C.c_void_p, C.POINTER(PlanSelectArgs), C.c_void_p]),
+    "glgym_plan_sample": (C.c_int, [C.c_void_p, C.POINTER(PlanSampleArgs), C.c_void_p]),
+    "glgym_plan_elites": (C.c_int, [C.c_void_p, C.POINTER(PlanElitesArgs), C.c_void_p]),
+    "glgym_plan_refit": (C.c_int, [C.c_void_p, C.POINTER(PlanRefitArgs), C.c_void_p]),
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),

@@ -9,7 +9,11 @@ crop="current" the parent's present crop block is held over the horizon, with "n
 happens either: a child that reaches its season end stops accumulating (`alive`), the step that reports `done` being its last.
 
 The parent environment is only read: its state, random streams, draw counter, episode counters, metrics() and step_flags_t are after
-a rollout what they were before."""
+a rollout what they were before.
+
+Iterated sampling (the cross-entropy method, glgym_plan_sample / _elites / _refit): cem() draws the candidates on the device from a
+Gaussian per (horizon step, greenhouse, actuator), simulates them, ranks each greenhouse's returns, refits mean and spread to the best
+n_elite, and repeats; sample(), elites() and refit() are the single stages, shift() the receding-horizon warm start."""
 from __future__ import annotations
 
 import ctypes as C
@@ -55,6 +59,16 @@ class Planner:
         self.mean_sequence_t = z(self.H, self.B, L.NU, dtype=torch.float32)
         self._actions_buf = self._controls_T = None                  # staging, allocated at first use
         self._actions = None                                         # the [H, C, 6] block of the last rollout (select reads it)
+        # the cross-entropy method's buffers, allocated at first use: two action blocks (a population is sampled into the one the
+        # previous population does not occupy, so that its elites can be carried over), elite indices, the distribution
+        self._cem_blocks = None
+        self._cem_cur = None                                         # which block holds the population sampled last
+        self._rolled = None                                          # which of the two blocks the last rollout simulated, if one of them
+        self._elites = None                                          # (E, block) of the last elites(): row length of elite_k_t, and the
+                                                                     # block it ranks if the next sample() may carry from it, else None
+        self.elite_k_t = self.n_elite_t = self.cem_mean_t = self.cem_std_t = None
+        self.draw_base_t = z(1, dtype=torch.int64)                   # device word added to every draw index: add to it between replays
+        self._draw = 0                                               # draw index of cem()'s next population
         self.x, self.u = self.x_T[:, :self.C].t(), self.u_T[:, :self.C].t()
 
     def set_layout(self, layout: str):
@@ -102,11 +116,12 @@ class Planner:
                 raise ValueError(f"actions_t must hold horizon x (num_envs * n_candidates) x 6 = {n} values, got {tuple(actions_t.shape)}")
             if actions_t.dtype == torch.float32 and actions_t.is_cuda and actions_t.device == e.device and actions_t.is_contiguous():
                 self._actions = actions_t.view(self.H, self.C, L.NU)
+                self._rolled = next((i for i, b in enumerate(self._cem_blocks or ()) if actions_t is b), None)
             else:
                 if self._actions_buf is None:
                     self._actions_buf = torch.zeros(self.H, self.C, L.NU, dtype=torch.float32, device=e.device)
                 self._actions_buf.copy_(actions_t.reshape(self.H, self.C, L.NU))
-                self._actions = self._actions_buf
+                self._actions, self._rolled = self._actions_buf, None
             act_ptr = self._actions.data_ptr()
         else:
             if controls_t.numel() != n:
@@ -114,7 +129,7 @@ class Planner:
             if self._controls_T is None:
                 self._controls_T = torch.zeros(self.H, L.NU, self.ld, dtype=e.tdtype, device=e.device)
             self._controls_T[:, :, :self.C].copy_(controls_t.reshape(self.H, self.C, L.NU).transpose(1, 2))
-            self._actions = None
+            self._actions = self._rolled = None
             ctl_ptr = self._controls_T.data_ptr()
         self.fork()
         a = L.make_plan_args(L.PlanRolloutArgs, self.H, self.gamma, self._step_args(), act_ptr, ctl_ptr, self.ret_t.data_ptr(),
@@ -150,3 +165,142 @@ class Planner:
         if temperature is not None:
             out["mean_sequence"] = self.mean_sequence_t
         return out
+
+    # ---- the cross-entropy method ------------------------------------------------------------------------------------------
+    def _cem_alloc(self):
+        if self._cem_blocks is None:
+            torch, dev = self.torch, self.env.device
+            self._cem_blocks = [torch.zeros(self.H, self.C, L.NU, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.elite_k_t = torch.full((self.C,), -1, dtype=torch.int32, device=dev)       # rows of E <= K entries: [B, E] is a view
+            self.n_elite_t = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.cem_mean_t = torch.zeros(self.H, self.B, L.NU, dtype=torch.float32, device=dev)
+            self.cem_std_t = torch.zeros(self.H, self.B, L.NU, dtype=torch.float32, device=dev)
+
+    def _drop_carry(self):
+        if self._elites:
+            self._elites = (self._elites[0], None)
+
+    def _check_dist(self, mean_t, std_t):
+        torch, n = self.torch, self.H * self.B * L.NU
+        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
+            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.env.device or not t.is_contiguous()
+                    or t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of horizon x num_envs x 6 = {n} values on the environment's device")
+
+    def sample(self, mean_t, std_t, beta: float = 0.0, seed: int = 0, draw_index: int = 0, carry: int = 0):
+        """glgym_plan_sample: draw the population [H, B*K, 6] from N(mean_t, std_t) [H, B, 6] with lag-1 correlation beta along the
+        horizon, clipped to [-1, 1], into the planner's action block that the previous population does not occupy; returns it (pass it
+        to rollout()).  Candidate 0 is the clipped mean; with carry >= 1, and elites() of the previous sampled population at hand,
+        candidates 1 .. carry are its best sequences.  Noise: Philox keyed by seed, counter (child, step, draw_index + draw_base_t)."""
+        self._check_dist(mean_t, std_t)
+        if not 0.0 <= float(beta) < 1.0:
+            raise ValueError("beta must be in [0, 1)")
+        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
+            raise ValueError("carry, seed and draw_index must be >= 0")
+        n_elites, src = self._elites or (0, None)
+        carried = int(carry) if src is not None else 0           # nothing ranked to carry from: every candidate but 0 is sampled
+        if carried > n_elites:
+            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
+        self._cem_alloc()
+        e = self.env
+        dst = 0 if self._cem_cur is None else 1 - self._cem_cur      # src, when set, is _cem_cur: the other block
+        prev = self._cem_blocks[src].data_ptr() if carried else None
+        a = L.make_plan_args(L.PlanSampleArgs, self.B, self.K, self.H, mean_t.data_ptr(), std_t.data_ptr(), float(beta),
+                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.draw_base_t.data_ptr(),
+                             self._cem_blocks[dst].data_ptr(), carried, n_elites if carried else 0, prev,
+                             self.elite_k_t.data_ptr() if carried else None, self.n_elite_t.data_ptr() if carried else None)
+        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
+        self._cem_cur = dst
+        self._elites = (n_elites, None) if self._elites else None    # they rank another population than the one sampled last
+        return self._cem_blocks[dst]
+
+    def elites(self, n_elite: int):
+        """glgym_plan_elites on the last rollout: (elite_k [B, n_elite] i32 -- the admissible candidates by return, best first, ties to
+        the lower index, padded with -1 --, n_elite [B] i32).  Views of planner buffers, overwritten by the next call."""
+        E = int(n_elite)
+        if not 1 <= E <= self.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
+        self._cem_alloc()
+        e = self.env
+        a = L.make_plan_args(L.PlanElitesArgs, self.B, self.K, E, self.ret_t.data_ptr(), self.failed_t.data_ptr(), self.elite_k_t.data_ptr(),
+                             self.n_elite_t.data_ptr())
+        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
+        self._elites = (E, self._rolled if self._rolled == self._cem_cur else None)
+        return self.elite_k_t[:self.B * E].view(self.B, E), self.n_elite_t
+
+    def refit(self, mean_t, std_t, alpha: float, min_std: float):
+        """glgym_plan_refit, in place on mean_t / std_t [H, B, 6]: mean <- alpha*mean + (1-alpha)*(the elites' mean), std <-
+        max(alpha*std + (1-alpha)*(their standard deviation, ddof 0), min_std), over the elites() of the last rollout's actions.  A
+        greenhouse without an elite keeps its row."""
+        self._check_dist(mean_t, std_t)
+        if not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf"):
+            raise ValueError("min_std must be finite and >= 0")
+        if self._actions is None or self._elites is None:
+            raise ValueError("refit needs a rollout of actions_t and its elites()")
+        e = self.env
+        a = L.make_plan_args(L.PlanRefitArgs, self.B, self.K, self.H, self._elites[0], self._actions.data_ptr(), self.elite_k_t.data_ptr(),
+                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
+                             mean_t.data_ptr(), std_t.data_ptr())
+        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
+        return mean_t, std_t
+
+    def cem(self, n_iter: int, n_elite: int, init_std: float = 0.5, min_std: float = 0.05, alpha: float = 0.1, beta: float = 0.0,
+            carry: int = 0, seed: int = 0, mean_t=None, std_t=None) -> Dict[str, Any]:
+        """One receding-horizon decision by the cross-entropy method: n_iter x (sample -> rollout -> elites -> refit), then
+        select(sequence=True) on the last population.  mean_t None: start from zeros ("hold the controls"), spread init_std, nothing
+        carried into the first population; otherwise from mean_t / std_t [H, B, 6] (std_t None: init_std) -- the planner's own
+        cem_mean_t / cem_std_t after shift() for a warm start.  carry <= n_elite elites survive from one population into the next.
+        Every sample() takes the next draw index of the planner's lifetime.
+        Returns device tensors, planner buffers overwritten by the next call: mean_sequence, std_sequence [H, B, 6], best_sequence,
+        best_action, best_return, best_k (select()'s), elite_k [B, n_elite], n_elite [B].  No host synchronisation and, after the
+        first call, no allocation: a whole cem() can be captured in a graph (add n_iter to draw_base_t between replays for fresh
+        noise)."""
+        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
+        if n_iter < 1:
+            raise ValueError("n_iter must be at least 1")
+        if not 1 <= E <= self.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
+        if not 0 <= carry <= E:
+            raise ValueError("carry must be in 0 .. n_elite")
+        if not 0.0 <= float(beta) < 1.0 or not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha and beta must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
+            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
+        self._cem_alloc()
+        if mean_t is not None or std_t is not None:
+            self._check_dist(mean_t if mean_t is not None else std_t, std_t if std_t is not None else mean_t)
+        if mean_t is None:
+            self.cem_mean_t.zero_()
+            self._drop_carry()
+        elif mean_t.data_ptr() != self.cem_mean_t.data_ptr():
+            self.cem_mean_t.copy_(mean_t.view(self.H, self.B, L.NU))
+        if std_t is None:
+            self.cem_std_t.fill_(float(init_std))
+        elif std_t.data_ptr() != self.cem_std_t.data_ptr():
+            self.cem_std_t.copy_(std_t.view(self.H, self.B, L.NU))
+        for _ in range(n_iter):
+            block = self.sample(self.cem_mean_t, self.cem_std_t, beta=beta, seed=seed, draw_index=self._draw, carry=carry)
+            self._draw += 1
+            self.rollout(block)
+            elite_k, n_el = self.elites(E)
+            self.refit(self.cem_mean_t, self.cem_std_t, alpha, min_std)
+        sel = self.select(sequence=True)
+        return {"mean_sequence": self.cem_mean_t, "std_sequence": self.cem_std_t, "best_sequence": sel["best_sequence"],
+                "best_action": sel["best_action"], "best_return": sel["best_return"], "best_k": sel["best_k"], "elite_k": elite_k,
+                "n_elite": n_el}
+
+    def shift(self, fill_std: float):
+        """Receding-horizon warm start on cem()'s distribution: mean[h] <- mean[h+1], last row 0; std[h] <- std[h+1], last row
+        fill_std.  The carried elites belong to the unshifted horizon and are dropped."""
+        if self.cem_mean_t is None:
+            raise ValueError("shift() moves the distribution of a previous cem()")
+        if not 0.0 <= float(fill_std) < float("inf"):
+            raise ValueError("fill_std must be finite and >= 0")
+        for t, last in ((self.cem_mean_t, 0.0), (self.cem_std_t, float(fill_std))):
+            if self.H > 1:
+                t[:-1].copy_(t[1:].clone())
+            t[-1].fill_(last)
+        self._drop_carry()
+        return self.cem_mean_t, self.cem_std_t

@@ -30,6 +30,9 @@
  *                     (constants gl_gym/configs/agents/rule_based.yml; caller experiments/evaluate_baseline.py:22)
  *   glgym_weather  <- load_weather_data (array part)              gl_gym/environments/utils.py:48-125
  *   glgym_rhs      <- ODE(x,u,d,p) (test hook; no reference binding) gl_gym/environments/models/ode.hpp:6-124
+ *   glgym_plan_fork / _accumulate / _rollout / _select, glgym_plan_sample / _elites / _refit <- no counterpart (the reference's
+ *                     README lists MPC as a next step): sampling MPC on forked copies of the environments, one-shot (random
+ *                     shooting, MPPI) and iterated (the cross-entropy method: sample, rank the elites, refit), all on the device
  *
  * Layouts.  "SoA [n][ld]" = n planes of ld elements, element (i, b) at base[i*ld + b]; lane b of a
  * wavefront touches consecutive addresses.  Element type T is float (GLGYM_F32) or double (GLGYM_F64).
@@ -156,7 +159,8 @@ typedef struct {
 /* ABI version of this header; glgym_abi_version() returns the library's.  5: glgym_step_args starts with struct_size (round 5);
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
- * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset */
+ * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
+ * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -495,6 +499,72 @@ int glgym_plan_fork(glgym_handle h, const glgym_plan_fork_args* a, void* stream)
 int glgym_plan_accumulate(glgym_handle h, const glgym_plan_accumulate_args* a, void* stream);
 int glgym_plan_rollout(glgym_handle h, const glgym_plan_rollout_args* a, void* stream);
 int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* stream);
+
+/* ---- iterated sampling MPC: the cross-entropy method's stages between two rollouts (csrc/gl_cem.hpp, csrc/glgym_plan.hip) ------
+ * One CEM iteration is glgym_plan_sample -> glgym_plan_fork + glgym_plan_rollout -> glgym_plan_elites -> glgym_plan_refit: draw K
+ * candidate sequences per parent from a Gaussian per (horizon step, parent, actuator), simulate them, rank each parent's returns,
+ * refit mean and spread to the E best.  Same conventions as above: struct_size first, GLGYM_EINVAL before anything is launched,
+ * asynchronous on `stream`, no allocation, no host synchronisation (capturable), plain vector stores, no atomics.  Opt-in: no other
+ * entry point changes.  mean / std are [H][P][6] f32 (the layout of best_sequence), the action block [H][P*K][6] f32.
+ *
+ * glgym_plan_sample, one lane per child c = p*K + k.  Generator: Philox4x32-10; for child c, step h and D = draw_index + *draw_base
+ * the counter is (c, 2h + blk, lo32(D), hi32(D)) for blk = 0, 1 and the key (lo32(seed), hi32(seed) ^ 0x43454d31), which gives the
+ * words r0..r7.  In double, products and sums rounded separately: u_i = (r_i + 0.5) * 2^-32; e_2m = sqrt(-2 ln u_2m) cos(2 pi u_2m+1),
+ * e_2m+1 the same with sin, m = 0, 1, 2 (r6, r7 unused); coloured noise per actuator n_0 = e_0, n_h = beta n_{h-1} +
+ * sqrt(1 - beta^2) e_h; actions[h][c][j] = (float) clip(mean[h][p][j] + std[h][p][j] * n_h[j], -1, 1).  The words are exact; ln, cos
+ * and sin are the device library's (a few double ulps from another libm: at most one float32 ulp in the stored action).
+ * Reserved candidates: k = 0 is the clipped mean itself; with carry >= 1 candidate 1 <= k <= carry with k-1 < prev_n_elite[p] copies
+ * the sequence of the previous population's elite k-1 from prev_actions (which must not be `actions`: ping-pong two blocks). */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, H;
+    const float* mean;           /* [H][P][6] */
+    const float* std;            /* [H][P][6] */
+    double beta;                 /* 0 <= beta < 1: lag-1 correlation of the noise along the horizon */
+    uint64_t seed;
+    uint64_t draw_index;         /* which population this is: another value, other noise */
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL: a replayed graph advances it instead of repeating itself */
+    float* actions;              /* [H][P*K][6] out */
+    int32_t carry;               /* >= 0; > 0 needs the four prev_ members and carry <= prev_E */
+    int32_t prev_E;              /* row length of prev_elite_k */
+    const float* prev_actions;   /* [H][P*K][6]: the previous population */
+    const int32_t* prev_elite_k; /* [P][prev_E]: glgym_plan_elites of the previous population */
+    const int32_t* prev_n_elite; /* [P] */
+} glgym_plan_sample_args;
+
+/* Per parent: elite_k[p][0..n-1] = the candidates that have not failed and whose ret is finite (glgym_plan_select's rule), by return
+ * descending, ties to the lower k -- np.argsort(-ret, kind="stable") restricted to them -- cut at E; the rest of the row is -1;
+ * n_elite[p] = n = min(E, number of such candidates).  Rank by counting over tiles of 256 returns staged in LDS: exact, O(K^2) per
+ * parent, any K.  1 <= E <= K. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, E;
+    const double* ret;           /* [P*K] */
+    const uint8_t* failed;       /* [P*K] */
+    int32_t* elite_k;            /* [P][E] out */
+    int32_t* n_elite;            /* [P] out */
+} glgym_plan_elites_args;
+
+/* One wavefront per (parent, horizon step).  Over a = actions[h][p*K + elite_k[p][e]][j], e < n = n_elite[p]: m = (1/n) sum a,
+ * s = sqrt((1/n) sum (a - m)^2) (two passes, double); mean_out = (float)(alpha*mean + (1-alpha)*m), std_out =
+ * (float) max(alpha*std + (1-alpha)*s, min_std).  A parent with n = 0 (or an elite index outside 0..K-1) keeps its mean and std.
+ * mean_out / std_out may be mean / std.  0 <= alpha < 1, min_std >= 0, H <= 65 535. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, H, E;
+    const float* actions;        /* [H][P*K][6] */
+    const int32_t* elite_k;      /* [P][E] */
+    const int32_t* n_elite;      /* [P] */
+    double alpha, min_std;
+    const float* mean;           /* [H][P][6] */
+    const float* std;
+    float* mean_out;             /* [H][P][6] out */
+    float* std_out;
+} glgym_plan_refit_args;
+
+int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* stream);
+int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream);
+int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream);
 
 /* ---- rule-based controller (BASELINE config 1 "fixed rule-based actions") ------------------------------
  * u[6] = RuleBasedController.predict(x, weather[w_off + timestep], env clocks) for every env of the shard, written in the
