@@ -2506,6 +2506,103 @@ int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* strea
     return GLGYM_OK;
 }
 
+// robust planning (gl_scen.hpp).  The arguments are checked before the handle is looked at, so that a caller without a device gets the
+// refusal that names its mistake.
+static bool scenario_shape_ok(int32_t P, int32_t K, int32_t S, int32_t hold, double scale)
+{
+    return P >= 1 && K >= 1 && S >= 1 && S <= 256 && (int64_t)P * K * S <= INT32_MAX && (hold == 0 || hold == 1) && scale >= 0.0 &&
+           std::isfinite(scale);
+}
+
+int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_scenario: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_scenario", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || (int64_t)a->ld < (int64_t)a->P * a->K * a->S || a->h_step < 0 ||
+        a->h_step > 65535 || !a->crop || (!a->actions_in) != (!a->actions_out)) {
+        g_err = "glgym_plan_scenario: bad arguments (P, K, S < 1, S > 256, P*K*S > INT32_MAX, ld < P*K*S, h_step outside 0 .. 65 535, hold "
+                "not 0 | 1, scale negative or not finite, null crop, or one of actions_in / actions_out without the other)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_scenario: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->dtype == GLGYM_F32) HIPCHK(plan_scenario_launch<float>(*a, h->p0_crop_dev, st));
+    else HIPCHK(plan_scenario_launch<double>(*a, h->p0_crop_dev, st));
+    return GLGYM_OK;
+}
+
+int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_aggregate: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_aggregate", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->J < 1 || a->S < 1 || a->S > 256 || a->m < 1 || a->m > a->S || (int64_t)a->J * a->S > INT32_MAX || !a->ret || !a->failed ||
+        !a->ret_cand || !a->failed_cand || (a->viol_cand && (!a->viol || (int64_t)a->ld < (int64_t)a->J * a->S || a->ld_cand < a->J)) ||
+        (a->steps_cand && !a->n_steps)) {
+        g_err = "glgym_plan_aggregate: bad arguments (J, S < 1, S > 256, m outside 1 .. S, J*S > INT32_MAX, null pointer, or with viol_cand: "
+                "ld < J*S or ld_cand < J)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_aggregate: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    HIPCHK(plan_aggregate_launch(*a, (hipStream_t)stream));
+    return GLGYM_OK;
+}
+
+int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_rollout_scenarios: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_rollout_scenarios", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    const glgym_plan_rollout_args& r = a->rollout;
+    if (!plan_size_ok("glgym_plan_rollout_scenarios: rollout", r.struct_size, sizeof r)) return GLGYM_EINVAL;
+    if (r.controls) {
+        g_err = "glgym_plan_rollout_scenarios: raw-control scenario rollouts are not supported (rollout.controls must be NULL)";
+        return GLGYM_EINVAL;
+    }
+    glgym_step_args s = r.step;
+    if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || !a->staging || r.H < 1 || r.H > 65536 || !(r.gamma >= 0.0) ||
+        !std::isfinite(r.gamma) || !r.actions || (int64_t)s.B != (int64_t)a->P * a->K * a->S || s.ld < s.B || !s.crop_p || !s.reward ||
+        !s.info || !s.done || !r.ret || !r.viol || !r.n_steps || !r.alive || !r.failed) {
+        g_err = "glgym_plan_rollout_scenarios: bad arguments (P, K, S < 1, S > 256, hold not 0 | 1, scale negative or not finite, null "
+                "staging / actions / crop_p / reward / info / done / accumulators, H outside 1 .. 65 536, gamma, step.B != P*K*S, or ld < B)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_rollout_scenarios: null handle"; return GLGYM_EINVAL; }
+    s.metrics = nullptr;
+    s.action = a->staging;
+    s.control = nullptr;
+    // what glgym_step refuses without launching is refused by it, in its own words, before the first prologue is launched: a struct
+    // or pointer it checks itself, GLGYM_ODE_PIPE with a crop block (either step integrator), a BDF glgym_evalF setting on explicit steps
+    if (s.struct_size != (int32_t)sizeof s || !s.x || !s.u || !s.weather || !s.w_off || !s.timestep || s.weather_rows < 1 ||
+        h->variant == GLGYM_ODE_PIPE || (h->step_integrator != GLGYM_INTEGRATOR_BDF && h->integrator != GLGYM_INTEGRATOR_EXPLICIT)) {
+        const int rc = glgym_step(h, &s, stream);
+        if (rc != GLGYM_OK) return rc;
+        g_err = "glgym_plan_rollout_scenarios: glgym_step accepted a call it was expected to refuse";        // unreachable
+        return GLGYM_EINVAL;
+    }
+    glgym_plan_scenario_args sc;
+    sc.struct_size = (int32_t)sizeof sc;
+    sc.P = a->P; sc.K = a->K; sc.S = a->S; sc.ld = s.ld; sc.hold = a->hold; sc.scale = a->scale; sc.seed = a->seed;
+    sc.draw_index = a->draw_index; sc.draw_base = a->draw_base; sc.crop = (void*)s.crop_p; sc.actions_out = a->staging;
+    glgym_plan_accumulate_args acc;
+    acc.struct_size = (int32_t)sizeof acc;
+    acc.B = s.B; acc.ld = s.ld; acc.reward = s.reward; acc.info = s.info; acc.done = s.done; acc.step_flags = s.step_flags;
+    acc.ret = r.ret; acc.viol = r.viol; acc.n_steps = r.n_steps; acc.alive = r.alive; acc.failed = r.failed;
+    const size_t plane = (size_t)a->P * (size_t)a->K * NU;             // the candidates' action plane of one step
+    double w = 1.0;
+    for (int k = 0; k < r.H; ++k) {
+        sc.h_step = k;
+        sc.actions_in = r.actions + (size_t)k * plane;
+        int rc = glgym_plan_scenario(h, &sc, stream);
+        if (rc != GLGYM_OK) return rc;
+        if ((rc = glgym_step(h, &s, stream)) != GLGYM_OK) return rc;
+        acc.w = w;
+        if ((rc = glgym_plan_accumulate(h, &acc, stream)) != GLGYM_OK) return rc;
+        w = w * r.gamma;
+    }
+    return GLGYM_OK;
+}
+
 int glgym_rule_based(glgym_handle h, const glgym_rule_cfg* cfg, const glgym_rule_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);

@@ -17,3 +17,7 @@ hipError_t plan_select_launch(const glgym_plan_select_args& a, hipStream_t strea
 hipError_t plan_sample_launch(const glgym_plan_sample_args& a, hipStream_t stream);
 hipError_t plan_elites_launch(const glgym_plan_elites_args& a, hipStream_t stream);
 hipError_t plan_refit_launch(const glgym_plan_refit_args& a, hipStream_t stream);
+// Robust planning (gl_scen.hpp).  p0_crop: the handle's float32 p[128..161] on the device; a.P * a.K * a.S <= INT32_MAX.
+template <class T>
+hipError_t plan_scenario_launch(const glgym_plan_scenario_args& a, const float* p0_crop, hipStream_t stream);
+hipError_t plan_aggregate_launch(const glgym_plan_aggregate_args& a, hipStream_t stream);   // the returns are double: no T

@@ -19,10 +19,16 @@
 // broadcast) and each thread counts the candidates that come before its own -- the rank IS the output slot, so there is no sort
 // network and no atomic.  refit: one wavefront per (parent, horizon step), lanes stride over the elites, two passes over at most E
 // gathered rows.
+//
+// Robust planning (glgym_plan_scenario / _aggregate; scalar logic in gl_scen.hpp, instantiated on the host by
+// tests/scenhost/scenhost.cpp).  scenario: lane = child, the prologue of one env-step of a scenario rollout -- the child's crop block
+// for this step and its row of the expanded action plane.  aggregate: one wavefront per candidate, its S <= 256 scenario returns
+// ranked by counting in LDS and summed in rank order by one lane.
 #include "glgym_plan.h"
 
 #include "gl_cem.hpp"
 #include "gl_plan.hpp"
+#include "gl_scen.hpp"
 
 namespace {
 
@@ -240,7 +246,80 @@ __global__ __launch_bounds__(WAVE) void plan_refit_kernel(glgym_plan_refit_args 
         }
 }
 
+// grid = ceil(C / 256), lane = child c = (p*K + k)*S + s: nine Philox blocks keyed by (p*S + s, step) -- the S children of a candidate
+// draw S different futures, the K candidates of a greenhouse the same S -- then 34 plane stores, coalesced along c; with an action
+// plane, the candidate's row is copied to the child's row of the staging plane (6 consecutive floats per lane, 1 536 contiguous
+// bytes per wavefront; the S children of a candidate read one row, a broadcast).
+template <class T>
+__global__ __launch_bounds__(256) void plan_scenario_kernel(glgym_plan_scenario_args a, const float* p0, int n_children)
+{
+    const int64_t c64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // n_children may be INT32_MAX: the last block's tail is not
+    if (c64 >= n_children) return;
+    const int c = (int)c64;
+    uint32_t ps;
+    int cand;
+    glscen::split_child(c, a.K, a.S, &ps, &cand);
+    const uint64_t D = a.draw_index + (a.draw_base ? *a.draw_base : 0ull);
+    float v[glscen::NCROP];
+    glscen::crop_block(ps, a.h_step, a.hold, D, a.seed, a.scale, p0, v);
+    T* crop = (T*)a.crop;
+    const size_t ld = (size_t)a.ld;
+#pragma unroll
+    for (int i = 0; i < glscen::NCROP; ++i) crop[i * ld + c] = (T)v[i];
+    if (a.actions_in) {
+        const float* in = a.actions_in + (size_t)cand * NU;
+        float* out = a.actions_out + (size_t)c * NU;
+        for (int j = 0; j < NU; ++j) out[j] = in[j];
+    }
+}
+
+// grid = J, one wavefront per candidate.  Its S <= 256 returns are staged in LDS; every lane ranks its scenarios s = lane, lane + 64,
+// ... by counting over the staged row (each LDS read a broadcast) and puts them into their slot of the ascending row; lane 0 then sums
+// the first m slots in order.  Lanes 1..3 sum one violation row each in index order, lane 4 takes the minimum of the step counts.
+__global__ __launch_bounds__(WAVE) void plan_aggregate_kernel(glgym_plan_aggregate_args a)
+{
+    __shared__ double s_val[glscen::MAX_S], s_sorted[glscen::MAX_S];
+    const int lane = threadIdx.x;
+    const size_t j = blockIdx.x, first = j * (size_t)a.S;
+    bool is_bad = false;
+    for (int s = lane; s < a.S; s += WAVE) {
+        const double r = a.ret[first + s];
+        s_val[s] = r;
+        is_bad = is_bad || glscen::bad(r, a.failed[first + s]);
+    }
+    __syncthreads();
+    is_bad = __any(is_bad);                             // wave-uniform
+    if (!is_bad)
+        for (int s = lane; s < a.S; s += WAVE) s_sorted[glscen::rank_asc(s_val, a.S, s)] = s_val[s];
+    __syncthreads();
+    if (lane == 0) {
+        a.ret_cand[j] = is_bad ? glscen::nan_value() : glscen::tail_mean(s_sorted, a.m);
+        a.failed_cand[j] = is_bad ? 1 : 0;
+    } else if (lane <= 3) {
+        if (a.viol_cand) a.viol_cand[(size_t)(lane - 1) * a.ld_cand + j] = glscen::seq_mean(a.viol + (size_t)(lane - 1) * a.ld + first, a.S);
+    } else if (lane == 4) {
+        if (a.steps_cand) a.steps_cand[j] = glscen::min_steps(a.n_steps + first, a.S);
+    }
+}
+
 }  // namespace
+
+template <class T>
+hipError_t plan_scenario_launch(const glgym_plan_scenario_args& a, const float* p0_crop, hipStream_t stream)
+{
+    const int n_children = a.P * a.K * a.S;             // <= INT32_MAX: checked by the caller
+    hipLaunchKernelGGL(plan_scenario_kernel<T>, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, stream, a, p0_crop, n_children);
+    return hipGetLastError();
+}
+
+template hipError_t plan_scenario_launch<float>(const glgym_plan_scenario_args&, const float*, hipStream_t);
+template hipError_t plan_scenario_launch<double>(const glgym_plan_scenario_args&, const float*, hipStream_t);
+
+hipError_t plan_aggregate_launch(const glgym_plan_aggregate_args& a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(plan_aggregate_kernel, dim3((unsigned)a.J), dim3(WAVE), 0, stream, a);
+    return hipGetLastError();
+}
 
 hipError_t plan_sample_launch(const glgym_plan_sample_args& a, hipStream_t stream)
 {

@@ -188,6 +188,28 @@ class PlanRefitArgs(C.Structure):
                 ("min_std", C.c_double), ("mean", C.c_void_p), ("std", C.c_void_p), ("mean_out", C.c_void_p), ("std_out", C.c_void_p)]
 
 
+# robust planning (include/glgym.h glgym_plan_scenario / _rollout_scenarios / _aggregate)
+MAX_SCENARIOS = 256
+
+
+class PlanScenarioArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("ld", C.c_int32), ("h_step", C.c_int32),
+                ("hold", C.c_int32), ("scale", C.c_double), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p),
+                ("crop", C.c_void_p), ("actions_in", C.c_void_p), ("actions_out", C.c_void_p)]
+
+
+class PlanRolloutScenariosArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("hold", C.c_int32), ("scale", C.c_double),
+                ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p), ("staging", C.c_void_p),
+                ("rollout", PlanRolloutArgs)]
+
+
+class PlanAggregateArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("J", C.c_int32), ("S", C.c_int32), ("m", C.c_int32), ("ld", C.c_int32), ("ld_cand", C.c_int32),
+                ("ret", C.c_void_p), ("failed", C.c_void_p), ("viol", C.c_void_p), ("n_steps", C.c_void_p), ("ret_cand", C.c_void_p),
+                ("failed_cand", C.c_void_p), ("viol_cand", C.c_void_p), ("steps_cand", C.c_void_p)]
+
+
 def make_plan_args(cls, *args, **kw):
     """cls(...) of one of the Plan*Args structs without the leading struct_size, which is filled in here."""
     return cls(C.sizeof(cls), *args, **kw)
@@ -264,6 +286,9 @@ PROTOTYPES = {
     "glgym_plan_sample": (C.c_int, [C.c_void_p, C.POINTER(PlanSampleArgs), C.c_void_p]),
     "glgym_plan_elites": (C.c_int, [C.c_void_p, C.POINTER(PlanElitesArgs), C.c_void_p]),
     "glgym_plan_refit": (C.c_int, [C.c_void_p, C.POINTER(PlanRefitArgs), C.c_void_p]),
+    "glgym_plan_scenario": (C.c_int, [C.c_void_p, C.POINTER(PlanScenarioArgs), C.c_void_p]),
+    "glgym_plan_rollout_scenarios": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutScenariosArgs), C.c_void_p]),
+    "glgym_plan_aggregate": (C.c_int, [C.c_void_p, C.POINTER(PlanAggregateArgs), C.c_void_p]),
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),

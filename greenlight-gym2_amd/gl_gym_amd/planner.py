@@ -4,9 +4,17 @@ pick the best per greenhouse (random shooting) or the exponentially weighted mea
 its README lists MPC as a next step.
 
 What the planner sees: PERFECT-FORECAST MPC.  The children step on the true future rows of the environment's weather table -- the
-rows the observation's forecast module exposes -- clamped at the end of the table.  No noise is drawn inside the horizon: with
-crop="current" the parent's present crop block is held over the horizon, with "nominal" the handle's parameters are used.  No reset
-happens either: a child that reaches its season end stops accumulating (`alive`), the step that reports `done` being its last.
+rows the observation's forecast module exposes -- clamped at the end of the table.  Without n_scenarios no noise is drawn inside the
+horizon: with crop="current" the parent's present crop block is held over the horizon, with "nominal" the handle's parameters are
+used.  No reset happens either: a child that reaches its season end stops accumulating (`alive`), the step that reports `done` being
+its last.
+
+Robust planning (n_scenarios = S, glgym_plan_scenario / _rollout_scenarios / _aggregate): every candidate is simulated under S sampled
+futures of the 34 crop parameters -- the environment's own uncertainty_scale process, redrawn at every step (noise="step") or drawn
+once and held (noise="hold") -- and scored by the mean of its n_tail worst returns (n_tail = S: the mean; 1: the worst case).
+Scenario s of greenhouse b is the same future for all K candidates (common random numbers), and the scenarios stay the same from
+rollout to rollout until new_scenarios(): candidates, and the iterations of one cem(), are compared like with like.  select, elites,
+refit, sample, cem and shift work on the aggregated [B, K] scores as they do on plain returns.
 
 The parent environment is only read: its state, random streams, draw counter, episode counters, metrics() and step_flags_t are after
 a rollout what they were before.
@@ -23,9 +31,24 @@ from . import _lib as L
 
 
 class Planner:
-    def __init__(self, env, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal"):
+    def __init__(self, env, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal", n_scenarios: Optional[int] = None,
+                 noise_scale: Optional[float] = None, noise: str = "step", n_tail: Optional[int] = None, scenario_seed: int = 0):
         if int(n_candidates) < 1 or int(horizon) < 1:
             raise ValueError("n_candidates and horizon must be at least 1")
+        if n_scenarios is None:
+            if noise_scale is not None or n_tail is not None:
+                raise ValueError("noise_scale and n_tail belong to scenario rollouts: give n_scenarios")
+        else:
+            if not 1 <= int(n_scenarios) <= L.MAX_SCENARIOS:
+                raise ValueError(f"n_scenarios must be in 1 .. {L.MAX_SCENARIOS}")
+            if not 1 <= int(n_scenarios if n_tail is None else n_tail) <= int(n_scenarios):
+                raise ValueError("n_tail must be in 1 .. n_scenarios")
+            if noise_scale is not None and not 0.0 <= float(noise_scale) < float("inf"):
+                raise ValueError("noise_scale must be finite and >= 0")
+            if int(horizon) > 65536 or int(scenario_seed) < 0:
+                raise ValueError("scenario rollouts take horizon <= 65 536 and scenario_seed >= 0")
+        if noise not in ("step", "hold"):
+            raise ValueError("noise must be 'step' or 'hold'")
         if crop not in ("nominal", "current"):
             raise ValueError("crop must be 'nominal' or 'current'")
         if not (float(gamma) >= 0.0) or float(gamma) == float("inf"):
@@ -34,7 +57,11 @@ class Planner:
         self.env, self.torch = env, torch
         self.K, self.H, self.gamma, self.crop = int(n_candidates), int(horizon), float(gamma), crop
         self.B = env.B
-        self.C = self.B * self.K                                     # children
+        self.J = self.B * self.K                                     # candidates: rows of an action plane, entries of the scores
+        self.S = None if n_scenarios is None else int(n_scenarios)   # scenarios per candidate; None: one deterministic future
+        self.C = self.J * (self.S or 1)                              # children
+        if self.C > 2 ** 31 - 1:
+            raise ValueError("num_envs * n_candidates * n_scenarios must not exceed 2^31 - 1")
         self.ld = (self.C + 63) // 64 * 64
         dev, T = env.device, env.tdtype
         z = lambda *s, dtype=T: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
@@ -42,7 +69,7 @@ class Planner:
         self.x_T, self.u_T = z(L.NX, self.ld), z(L.NU, self.ld)
         self.timestep_t, self.w_off_t = z(self.C, dtype=torch.int32), z(self.C, dtype=torch.int32)
         self.start_day_t = z(self.C, dtype=torch.float32)
-        self.crop_T = z(L.NCROP, self.ld) if (crop == "current" and env.crop_T is not None) else None
+        self.crop_T = z(L.NCROP, self.ld) if (self.S or (crop == "current" and env.crop_T is not None)) else None
         self.reward_t, self.info_T = z(self.ld), z(L.NINFO, self.ld)
         self.done_t = z(self.C, dtype=torch.uint8)
         self.step_flags_t = z(self.C, dtype=torch.int32)
@@ -69,6 +96,22 @@ class Planner:
         self.elite_k_t = self.n_elite_t = self.cem_mean_t = self.cem_std_t = None
         self.draw_base_t = z(1, dtype=torch.int64)                   # device word added to every draw index: add to it between replays
         self._draw = 0                                               # draw index of cem()'s next population
+        # what select() and elites() score: the children's own returns, or with scenarios the candidates' aggregated ones
+        self._score_t, self._score_failed_t = self.ret_t, self.failed_t
+        if self.S:
+            self.noise_scale = float(env.uncertainty_scale if noise_scale is None else noise_scale)
+            self.noise, self.n_tail, self.scenario_seed = noise, int(self.S if n_tail is None else n_tail), int(scenario_seed)
+            self.ld_cand = (self.J + 63) // 64 * 64
+            self.stage_t = z(self.C, L.NU, dtype=torch.float32)      # ONE expanded action plane, rewritten before every step
+            self.ret_cand_t = z(self.J, dtype=torch.float64)
+            self.failed_cand_t, self.alive_cand_t = z(self.J, dtype=torch.uint8), z(self.J, dtype=torch.uint8)
+            self.viol_cand_T = z(3, self.ld_cand, dtype=torch.float64)
+            self.steps_cand_t = z(self.J, dtype=torch.int32)
+            self.scenario_base_t = z(1, dtype=torch.int64)           # device word added to the scenario draw index (apart from draw_base_t)
+            self._scen_draw = 0                                      # which set of scenarios: new_scenarios() takes the next
+            self._score_t, self._score_failed_t = self.ret_cand_t, self.failed_cand_t
+            self.scenario_returns = self.ret_t.view(self.B, self.K, self.S)       # per-scenario results of the last rollout
+            self.scenario_failed = self.failed_t.view(self.B, self.K, self.S)
         self.x, self.u = self.x_T[:, :self.C].t(), self.u_T[:, :self.C].t()
 
     def set_layout(self, layout: str):
@@ -79,15 +122,17 @@ class Planner:
     # ------------------------------------------------------------------------------------------------
     def fork(self, parent_t=None):
         """Copy the environment's current state into the children and zero their accumulators (rollout() calls this).  parent_t:
-        optional int32 [B*K] parent index per child; default child c <- environment c // K."""
+        optional int32 [B*K] parent index per child (with scenarios [B*K*S]); default child c <- environment c // K (c // (K*S))."""
         e = self.env
         if parent_t is not None and (parent_t.dtype != self.torch.int32 or parent_t.numel() != self.C or not parent_t.is_contiguous()):
             raise ValueError(f"parent_t must be a contiguous int32 tensor of {self.C} entries")
-        a = L.make_plan_args(L.PlanForkArgs, self.C, e.B, self.K, e.ld, self.ld, parent_t.data_ptr() if parent_t is not None else None,
+        fork_crop = self.crop_T is not None and not self.S           # scenario children get their block from the prologue of every step
+        a = L.make_plan_args(L.PlanForkArgs, self.C, e.B, self.K * (self.S or 1), e.ld, self.ld,
+                             parent_t.data_ptr() if parent_t is not None else None,
                              e.x_T.data_ptr(), e.u_T.data_ptr(), e.timestep_t.data_ptr(), e.w_off_t.data_ptr(), e.start_day_t.data_ptr(),
-                             e.crop_T.data_ptr() if self.crop_T is not None else None,
+                             e.crop_T.data_ptr() if fork_crop else None,
                              self.x_T.data_ptr(), self.u_T.data_ptr(), self.timestep_t.data_ptr(), self.w_off_t.data_ptr(),
-                             self.start_day_t.data_ptr(), self.crop_T.data_ptr() if self.crop_T is not None else None,
+                             self.start_day_t.data_ptr(), self.crop_T.data_ptr() if fork_crop else None,
                              self.ret_t.data_ptr(), self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.alive_t.data_ptr(),
                              self.failed_t.data_ptr())
         L.check(e._lib.glgym_plan_fork(e._h, C.byref(a), e._stream()), "glgym_plan_fork")
@@ -105,22 +150,27 @@ class Planner:
         environment's device is read in place.  controls_t [H, B*K, 6]: raw controls (step_raw_control).  Child b*K + k is candidate k
         of environment b.
         Returns device tensors (views of the planner's buffers, overwritten by the next rollout): returns [B, K] f64, alive [B, K] u8,
-        steps [B, K] i32, violations [3, B, K] f64 (co2, temp, rh), failed [B, K] u8."""
+        steps [B, K] i32, violations [3, B, K] f64 (co2, temp, rh), failed [B, K] u8.
+        With scenarios (actions_t only): every candidate runs under its S futures; returned per candidate are the mean of its n_tail
+        worst returns (NaN, with failed = 1, if a scenario failed or came back non-finite), alive = alive in every scenario, steps =
+        the fewest over the scenarios, the violations' means; scenario_returns / scenario_failed [B, K, S] hold the single runs."""
         if (actions_t is None) == (controls_t is None):
             raise ValueError("give exactly one of actions_t / controls_t")
+        if self.S and controls_t is not None:
+            raise ValueError("scenario rollouts take actions_t: raw controls are not supported")
         torch, e = self.torch, self.env
-        n = self.H * self.C * L.NU
+        n = self.H * self.J * L.NU
         act_ptr = ctl_ptr = None
         if actions_t is not None:
             if actions_t.numel() != n:
                 raise ValueError(f"actions_t must hold horizon x (num_envs * n_candidates) x 6 = {n} values, got {tuple(actions_t.shape)}")
             if actions_t.dtype == torch.float32 and actions_t.is_cuda and actions_t.device == e.device and actions_t.is_contiguous():
-                self._actions = actions_t.view(self.H, self.C, L.NU)
+                self._actions = actions_t.view(self.H, self.J, L.NU)
                 self._rolled = next((i for i, b in enumerate(self._cem_blocks or ()) if actions_t is b), None)
             else:
                 if self._actions_buf is None:
-                    self._actions_buf = torch.zeros(self.H, self.C, L.NU, dtype=torch.float32, device=e.device)
-                self._actions_buf.copy_(actions_t.reshape(self.H, self.C, L.NU))
+                    self._actions_buf = torch.zeros(self.H, self.J, L.NU, dtype=torch.float32, device=e.device)
+                self._actions_buf.copy_(actions_t.reshape(self.H, self.J, L.NU))
                 self._actions, self._rolled = self._actions_buf, None
             act_ptr = self._actions.data_ptr()
         else:
@@ -134,10 +184,28 @@ class Planner:
         self.fork()
         a = L.make_plan_args(L.PlanRolloutArgs, self.H, self.gamma, self._step_args(), act_ptr, ctl_ptr, self.ret_t.data_ptr(),
                              self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.alive_t.data_ptr(), self.failed_t.data_ptr())
-        L.check(e._lib.glgym_plan_rollout(e._h, C.byref(a), e._stream()), "glgym_plan_rollout")
         B, K = self.B, self.K
+        if self.S:
+            sc = L.make_plan_args(L.PlanRolloutScenariosArgs, B, K, self.S, 1 if self.noise == "hold" else 0, self.noise_scale,
+                                  self.scenario_seed & (2 ** 64 - 1), self._scen_draw, self.scenario_base_t.data_ptr(), self.stage_t.data_ptr(), a)
+            L.check(e._lib.glgym_plan_rollout_scenarios(e._h, C.byref(sc), e._stream()), "glgym_plan_rollout_scenarios")
+            g = L.make_plan_args(L.PlanAggregateArgs, self.J, self.S, self.n_tail, self.ld, self.ld_cand, self.ret_t.data_ptr(),
+                                 self.failed_t.data_ptr(), self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.ret_cand_t.data_ptr(),
+                                 self.failed_cand_t.data_ptr(), self.viol_cand_T.data_ptr(), self.steps_cand_t.data_ptr())
+            L.check(e._lib.glgym_plan_aggregate(e._h, C.byref(g), e._stream()), "glgym_plan_aggregate")
+            torch.amin(self.alive_t.view(self.J, self.S), dim=1, out=self.alive_cand_t)
+            return (self.ret_cand_t.view(B, K), self.alive_cand_t.view(B, K), self.steps_cand_t.view(B, K),
+                    self.viol_cand_T[:, :self.J].view(3, B, K), self.failed_cand_t.view(B, K))
+        L.check(e._lib.glgym_plan_rollout(e._h, C.byref(a), e._stream()), "glgym_plan_rollout")
         return (self.ret_t.view(B, K), self.alive_t.view(B, K), self.n_steps_t.view(B, K), self.viol_T[:, :self.C].view(3, B, K),
                 self.failed_t.view(B, K))
+
+    def new_scenarios(self):
+        """Draw other futures from the next scenario rollout on: the scenario draw index moves by one.  (A replayed graph carries the index it
+        was captured with: add to scenario_base_t instead.)"""
+        if not self.S:
+            raise ValueError("new_scenarios() belongs to a planner built with n_scenarios")
+        self._scen_draw += 1
 
     def select(self, temperature: Optional[float] = None, sequence: bool = False) -> Dict[str, Any]:
         """Best candidate per environment from the last rollout: {"best_k" [B] i32 (-1: every candidate failed or came back
@@ -151,7 +219,7 @@ class Planner:
             raise ValueError("best_sequence / mean_sequence need a rollout of actions_t")
         if temperature is not None and not float(temperature) > 0.0:
             raise ValueError("temperature must be > 0")
-        a = L.make_plan_args(L.PlanSelectArgs, self.B, self.K, self.H, self.ret_t.data_ptr(), self.failed_t.data_ptr(),
+        a = L.make_plan_args(L.PlanSelectArgs, self.B, self.K, self.H, self._score_t.data_ptr(), self._score_failed_t.data_ptr(),
                              self._actions.data_ptr() if has_a else None, self.best_k_t.data_ptr(), self.best_ret_t.data_ptr(),
                              self.best_action_t.data_ptr() if has_a else None, self.best_sequence_t.data_ptr() if sequence else None,
                              float(temperature) if temperature is not None else 0.0,
@@ -170,8 +238,8 @@ class Planner:
     def _cem_alloc(self):
         if self._cem_blocks is None:
             torch, dev = self.torch, self.env.device
-            self._cem_blocks = [torch.zeros(self.H, self.C, L.NU, dtype=torch.float32, device=dev) for _ in range(2)]
-            self.elite_k_t = torch.full((self.C,), -1, dtype=torch.int32, device=dev)       # rows of E <= K entries: [B, E] is a view
+            self._cem_blocks = [torch.zeros(self.H, self.J, L.NU, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.elite_k_t = torch.full((self.J,), -1, dtype=torch.int32, device=dev)       # rows of E <= K entries: [B, E] is a view
             self.n_elite_t = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self.cem_mean_t = torch.zeros(self.H, self.B, L.NU, dtype=torch.float32, device=dev)
             self.cem_std_t = torch.zeros(self.H, self.B, L.NU, dtype=torch.float32, device=dev)
@@ -222,7 +290,7 @@ class Planner:
             raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
         self._cem_alloc()
         e = self.env
-        a = L.make_plan_args(L.PlanElitesArgs, self.B, self.K, E, self.ret_t.data_ptr(), self.failed_t.data_ptr(), self.elite_k_t.data_ptr(),
+        a = L.make_plan_args(L.PlanElitesArgs, self.B, self.K, E, self._score_t.data_ptr(), self._score_failed_t.data_ptr(), self.elite_k_t.data_ptr(),
                              self.n_elite_t.data_ptr())
         L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
         self._elites = (E, self._rolled if self._rolled == self._cem_cur else None)
@@ -256,7 +324,8 @@ class Planner:
         Returns device tensors, planner buffers overwritten by the next call: mean_sequence, std_sequence [H, B, 6], best_sequence,
         best_action, best_return, best_k (select()'s), elite_k [B, n_elite], n_elite [B].  No host synchronisation and, after the
         first call, no allocation: a whole cem() can be captured in a graph (add n_iter to draw_base_t between replays for fresh
-        noise)."""
+        noise).  With scenarios every iteration scores its population on the SAME futures (a carried elite keeps its score); call
+        new_scenarios(), or add to scenario_base_t between replays, for other ones."""
         n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
         if n_iter < 1:
             raise ValueError("n_iter must be at least 1")

@@ -447,13 +447,15 @@ class TomatoVecEnv:
                 getattr(self, k).copy_(state[k])
         self._draw, self.seed_value = int(state["_draw"]), int(state["seed_value"])
 
-    def planner(self, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal"):
+    def planner(self, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal", **scenarios):
         """A gl_gym_amd.planner.Planner for this environment: n_candidates control sequences per environment, simulated over `horizon`
         env-steps on forked copies (buffers allocated once, here), scored and selected on the device.  crop="current" forks this
         environment's per-env crop block (uncertainty_scale > 0) and holds it over the horizon; "nominal" plans with the handle's
-        parameters."""
+        parameters.  Robust planning, keyword-only: n_scenarios=S simulates every candidate under S sampled futures of the crop block
+        (noise_scale, default this environment's uncertainty_scale; noise="step" | "hold") and scores it by the mean of its n_tail
+        worst returns (default S: the mean); scenario_seed keys the futures."""
         from .planner import Planner
-        return Planner(self, n_candidates, horizon, gamma=gamma, crop=crop)
+        return Planner(self, n_candidates, horizon, gamma=gamma, crop=crop, **scenarios)
 
     def _launch_reset(self, mask_t):
         """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).

@@ -33,6 +33,8 @@
  *   glgym_plan_fork / _accumulate / _rollout / _select, glgym_plan_sample / _elites / _refit <- no counterpart (the reference's
  *                     README lists MPC as a next step): sampling MPC on forked copies of the environments, one-shot (random
  *                     shooting, MPPI) and iterated (the cross-entropy method: sample, rank the elites, refit), all on the device
+ *   glgym_plan_scenario / _rollout_scenarios / _aggregate <- the draw of noise.py:3-23 (parametric_crop_uncertainty) inside the
+ *                     planning horizon, with common random numbers across candidates, and a risk score over the sampled futures
  *
  * Layouts.  "SoA [n][ld]" = n planes of ld elements, element (i, b) at base[i*ld + b]; lane b of a
  * wavefront touches consecutive addresses.  Element type T is float (GLGYM_F32) or double (GLGYM_F64).
@@ -160,7 +162,7 @@ typedef struct {
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
- * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit */
+ * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -459,8 +461,9 @@ typedef struct {
 /* H env-steps of the children in one call: for k = 0 .. H-1 glgym_step(step with the action / control of step k, metrics = NULL),
  * then glgym_plan_accumulate with w_0 = 1, w_{k+1} = w_k * gamma (a running product in double).  The handle's settings apply as
  * they do to glgym_step (parameters, reward, scheme, n_sub, verify mode, explicit or BDF step integrator, GLGYM_ODE_PIPE with raw
- * controls); the handle's metric accumulators are not touched.  No reset and no noise draw happens: a child past its season end keeps
- * stepping on weather rows clamped to the table and is ignored through alive.  Exactly one of actions / controls is non-null. */
+ * controls); the handle's metric accumulators are not touched.  No reset and no noise draw happens (a per-env crop block is held over
+ * the horizon; glgym_plan_rollout_scenarios below is the rollout that draws): a child past its season end keeps stepping on weather
+ * rows clamped to the table and is ignored through alive.  Exactly one of actions / controls is non-null. */
 typedef struct {
     int32_t struct_size;
     int32_t H;                   /* env-steps (>= 1) */
@@ -565,6 +568,78 @@ typedef struct {
 int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* stream);
 int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream);
 int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream);
+
+/* ---- robust planning: scenario rollouts under crop noise, risk-aware scores (csrc/gl_scen.hpp, csrc/glgym_plan.hip) ----------
+ * With uncertainty_scale > 0 the environment multiplies the 34 crop parameters p[128..161] by 1 + U(-scale/2, scale/2) at every
+ * env-step (glgym_crop_noise).  Here every one of the P*K candidates is simulated under S sampled futures of that block -- children
+ * c = (p*K + k)*S + s, C = P*K*S of them -- and scored by a risk measure over its S returns, which glgym_plan_select / _elites /
+ * _refit then take as the candidate's return.  Same conventions as above: struct_size first, GLGYM_EINVAL before anything is
+ * launched, asynchronous on `stream`, no allocation, no host synchronisation (capturable), plain vector stores, no atomics.  Opt-in:
+ * no other entry point changes.
+ *
+ * Scenario crop block of child c at horizon step h.  D = draw_index + *draw_base, hh = hold ? 0 : h.  For blk = 0..8 the words
+ * r[4*blk .. 4*blk+3] are Philox4x32-10 of the counter (p*S + s, lo32(D), hi32(D), 16*hh + blk) under the key (lo32(seed),
+ * hi32(seed) ^ 0x5343454e).  The candidate k is NOT in the counter: scenario s of greenhouse p is the same future for all K
+ * candidates (common random numbers), so that their scores differ by their actions alone.  For i < 34, with p_i the handle's
+ * float32 p[128+i], in double with products and sums rounded separately: u = (r[i] + 0.5) * 2^-32, z = (u - 0.5) * scale,
+ * t = z * p_i, v_i = (float)(p_i + t); then v[16] = v[13] / v[14] in float32 (cLeafMax = laiMax / sla, as glgym_crop_noise); stored as
+ * T.  hold = 1: one parametric draw held over the horizon; hold = 0: a fresh draw at every step, the environment's own process. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, S;             /* greenhouses, candidates per greenhouse, scenarios per candidate (S <= 256); P*K*S <= INT32_MAX */
+    int32_t ld;                  /* leading dimension of crop (>= P*K*S) */
+    int32_t h_step;              /* horizon step h, 0 .. 65 535 */
+    int32_t hold;                /* 0 | 1 */
+    double scale;                /* finite, >= 0 */
+    uint64_t seed;
+    uint64_t draw_index;         /* which set of scenarios this is: another value, other futures */
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    void* crop;                  /* SoA [34][ld] T out (required) */
+    const float* actions_in;     /* [P*K][6] f32: the candidates' action plane of this step, or NULL */
+    float* actions_out;          /* [P*K*S][6] f32 out: row c = actions_in row c / S; NULL exactly when actions_in is */
+} glgym_plan_scenario_args;
+
+/* H env-steps of the C = P*K*S children: for h = 0 .. H-1 glgym_plan_scenario(h) into rollout.step.crop_p and `staging`, glgym_step
+ * with action = staging and metrics = NULL, glgym_plan_accumulate with the running-product weight -- glgym_plan_rollout's loop with
+ * the prologue in front of every step.  rollout.step.B must be P*K*S and rollout.step.crop_p is required; rollout.actions is the
+ * CANDIDATES' block [H][P*K][6] (one plane is expanded per step, never H of them); rollout.controls must be NULL.  What glgym_step
+ * refuses with a crop block (GLGYM_ODE_PIPE) is refused here with glgym_step's own error, before anything is launched. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, S;
+    int32_t hold;
+    double scale;
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;
+    float* staging;              /* [P*K*S][6] f32: caller-owned staging plane of the expanded actions */
+    glgym_plan_rollout_args rollout;
+} glgym_plan_rollout_scenarios_args;
+
+/* One wavefront per candidate j over its S scenario returns r_s = ret[j*S + s].  If any failed[j*S + s] != 0 or any r_s is not
+ * finite: ret_cand[j] = NaN, failed_cand[j] = 1.  Otherwise failed_cand[j] = 0 and, with a the returns in ascending order,
+ * ret_cand[j] = (((0.0 + a_0) + a_1) + ... + a_{m-1}) / (double)m: m = S the mean, m = 1 the worst case, between them the mean of
+ * the worst m (a CVaR-style tail mean).  viol_cand[i][j] = (sum over s in index order, from 0.0, of viol[i][j*S + s]) / (double)S;
+ * steps_cand[j] = min over s of n_steps[j*S + s].  The returns are staged in LDS and ranked by counting (as glgym_plan_elites); one
+ * lane then sums in rank order, so the result is the sequential sum above bit for bit.  Independent of the handle's dtype. */
+typedef struct {
+    int32_t struct_size;
+    int32_t J, S, m;             /* candidates, scenarios per candidate (1 .. 256), tail length (1 .. S) */
+    int32_t ld;                  /* leading dimension of viol (>= J*S) */
+    int32_t ld_cand;             /* leading dimension of viol_cand (>= J) */
+    const double* ret;           /* [J*S] */
+    const uint8_t* failed;       /* [J*S] */
+    const double* viol;          /* SoA [3][ld]; required with viol_cand */
+    const int32_t* n_steps;      /* [J*S]; required with steps_cand */
+    double* ret_cand;            /* [J] out */
+    uint8_t* failed_cand;        /* [J] out */
+    double* viol_cand;           /* SoA [3][ld_cand] out, or NULL */
+    int32_t* steps_cand;         /* [J] out, or NULL */
+} glgym_plan_aggregate_args;
+
+int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void* stream);
+int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream);
+int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream);
 
 /* ---- rule-based controller (BASELINE config 1 "fixed rule-based actions") ------------------------------
  * u[6] = RuleBasedController.predict(x, weather[w_off + timestep], env clocks) for every env of the shard, written in the
