@@ -2603,6 +2603,28 @@ int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenar
     return GLGYM_OK;
 }
 
+// weather-forecast scenarios (gl_wscen.hpp): checked before the handle is looked at, like the entry points above
+int glgym_plan_weather(glgym_handle h, const glgym_plan_weather_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_weather: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_weather", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    bool sigma_ok = true;
+    for (int j = 0; j < 7; ++j) sigma_ok = sigma_ok && a->sigma[j] >= 0.0 && std::isfinite(a->sigma[j]);
+    if (a->P < 1 || a->K < 1 || a->S < 1 || a->S > 256 || a->H < 1 || a->H > 65536 || (int64_t)a->P * a->S * a->H > INT32_MAX ||
+        (int64_t)a->P * a->K * a->S > INT32_MAX || a->weather_rows < 1 || !sigma_ok || !(a->phi >= 0.0 && a->phi < 1.0) || !a->weather ||
+        !a->w_off_parent || !a->timestep_parent || !a->window) {
+        g_err = "glgym_plan_weather: bad arguments (P, K, S, H < 1, S > 256, H > 65 536, P*S*H or P*K*S > INT32_MAX, weather_rows < 1, a sigma "
+                "negative or not finite, phi outside [0, 1), or a null weather / w_off_parent / timestep_parent / window)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_weather: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->dtype == GLGYM_F32) HIPCHK(plan_weather_launch<float>(*a, h->nd, st));
+    else HIPCHK(plan_weather_launch<double>(*a, h->nd, st));
+    return GLGYM_OK;
+}
+
 int glgym_rule_based(glgym_handle h, const glgym_rule_cfg* cfg, const glgym_rule_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);

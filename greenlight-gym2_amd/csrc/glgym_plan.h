@@ -21,3 +21,7 @@ hipError_t plan_refit_launch(const glgym_plan_refit_args& a, hipStream_t stream)
 template <class T>
 hipError_t plan_scenario_launch(const glgym_plan_scenario_args& a, const float* p0_crop, hipStream_t stream);
 hipError_t plan_aggregate_launch(const glgym_plan_aggregate_args& a, hipStream_t stream);   // the returns are double: no T
+// Weather-forecast scenarios (gl_wscen.hpp).  nd: the handle's column count; sqrt(1 - phi^2) is taken on the host here; the shape
+// has been checked (a.P * a.S * a.H and a.P * a.K * a.S <= INT32_MAX).  Two launches: the window, then (if asked for) the child offsets.
+template <class T>
+hipError_t plan_weather_launch(const glgym_plan_weather_args& a, int nd, hipStream_t stream);

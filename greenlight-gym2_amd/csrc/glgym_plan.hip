@@ -24,11 +24,19 @@
 // tests/scenhost/scenhost.cpp).  scenario: lane = child, the prologue of one env-step of a scenario rollout -- the child's crop block
 // for this step and its row of the expanded action plane.  aggregate: one wavefront per candidate, its S <= 256 scenario returns
 // ranked by counting in LDS and summed in rank order by one lane.
+//
+// Weather-forecast scenarios (glgym_plan_weather; scalar logic in gl_wscen.hpp, instantiated on the host by
+// tests/wscenhost/wscenhost.cpp).  window: lane = (greenhouse-scenario ps, j') with j' < 8 fastest; lanes 0..6 run their column's
+// error recurrence over the horizon -- sequential in h by its nature, one Philox block per step --, lane 7 copies the columns the
+// model leaves alone, so that eight adjacent lanes write one contiguous row of nd values per step and a wavefront eight rows.  The
+// source rows are shared by the S scenarios of a greenhouse (L2 hits).  No LDS: nothing is exchanged between lanes.  The child
+// offsets are a second launch, lane = child.
 #include "glgym_plan.h"
 
 #include "gl_cem.hpp"
 #include "gl_plan.hpp"
 #include "gl_scen.hpp"
+#include "gl_wscen.hpp"
 
 namespace {
 
@@ -302,7 +310,48 @@ __global__ __launch_bounds__(WAVE) void plan_aggregate_kernel(glgym_plan_aggrega
     }
 }
 
+// grid = ceil(P*S*8 / 256), lane = ps*8 + j'.  P*S*8 may pass 2^31: the index is taken in 64 bits, the last block's tail does nothing.
+template <class T>
+__global__ __launch_bounds__(256) void plan_weather_kernel(glgym_plan_weather_args a, int nd, double innov, int64_t n_lanes)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_lanes) return;
+    const uint32_t ps = (uint32_t)(t / glwscen::LANES);
+    const int jj = (int)(t - (int64_t)ps * glwscen::LANES);
+    const uint64_t D = a.draw_index + (a.draw_base ? *a.draw_base : 0ull);
+    glwscen::window_lane<T>(ps, jj, a.S, a.H, nd, (const T*)a.weather, a.weather_rows, a.w_off_parent, a.timestep_parent, a.sigma, a.phi, innov,
+                            D, a.seed, (T*)a.window);
+}
+
+// grid = ceil(C / 256), lane = child c = (p*K + k)*S + s
+__global__ __launch_bounds__(256) void plan_weather_offsets_kernel(glgym_plan_weather_args a, int n_children)
+{
+    const int64_t c64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c64 >= n_children) return;
+    const int c = (int)c64;
+    uint32_t ps;
+    int cand;
+    glscen::split_child(c, a.K, a.S, &ps, &cand);
+    a.w_off_child[c] = glwscen::child_offset(ps, a.H, a.timestep_parent[cand / a.K]);
+}
+
 }  // namespace
+
+template <class T>
+hipError_t plan_weather_launch(const glgym_plan_weather_args& a, int nd, hipStream_t stream)
+{
+    const double innov = glwscen::innov_of(a.phi);       // the one square root, on the host
+    const int64_t n_lanes = (int64_t)a.P * a.S * glwscen::LANES;
+    hipLaunchKernelGGL(plan_weather_kernel<T>, dim3((unsigned)((n_lanes + 255) / 256)), dim3(256), 0, stream, a, nd, innov, n_lanes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !a.w_off_child) return e;
+    const int n_children = a.P * a.K * a.S;
+    hipLaunchKernelGGL(plan_weather_offsets_kernel, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, stream, a, n_children);
+    return hipGetLastError();
+}
+
+template hipError_t plan_weather_launch<float>(const glgym_plan_weather_args&, int, hipStream_t);
+template hipError_t plan_weather_launch<double>(const glgym_plan_weather_args&, int, hipStream_t);
 
 template <class T>
 hipError_t plan_scenario_launch(const glgym_plan_scenario_args& a, const float* p0_crop, hipStream_t stream)

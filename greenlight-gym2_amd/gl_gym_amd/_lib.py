@@ -210,6 +210,17 @@ class PlanAggregateArgs(C.Structure):
                 ("failed_cand", C.c_void_p), ("viol_cand", C.c_void_p), ("steps_cand", C.c_void_p)]
 
 
+# weather-forecast scenarios (include/glgym.h glgym_plan_weather)
+WEATHER_COLUMNS = ("iGlob", "tOut", "vpOut", "co2Out", "wind", "tSky", "tSoOut")
+
+
+class PlanWeatherArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("weather_rows", C.c_int32),
+                ("weather", C.c_void_p), ("w_off_parent", C.c_void_p), ("timestep_parent", C.c_void_p), ("sigma", C.c_double * 7),
+                ("phi", C.c_double), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p), ("window", C.c_void_p),
+                ("w_off_child", C.c_void_p)]
+
+
 def make_plan_args(cls, *args, **kw):
     """cls(...) of one of the Plan*Args structs without the leading struct_size, which is filled in here."""
     return cls(C.sizeof(cls), *args, **kw)
@@ -289,6 +300,7 @@ PROTOTYPES = {
     "glgym_plan_scenario": (C.c_int, [C.c_void_p, C.POINTER(PlanScenarioArgs), C.c_void_p]),
     "glgym_plan_rollout_scenarios": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutScenariosArgs), C.c_void_p]),
     "glgym_plan_aggregate": (C.c_int, [C.c_void_p, C.POINTER(PlanAggregateArgs), C.c_void_p]),
+    "glgym_plan_weather": (C.c_int, [C.c_void_p, C.POINTER(PlanWeatherArgs), C.c_void_p]),
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),

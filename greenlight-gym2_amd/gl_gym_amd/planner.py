@@ -3,11 +3,11 @@ greenhouses, simulate K candidate control sequences over H env-steps on forked c
 pick the best per greenhouse (random shooting) or the exponentially weighted mean sequence (MPPI).  The reference has no counterpart;
 its README lists MPC as a next step.
 
-What the planner sees: PERFECT-FORECAST MPC.  The children step on the true future rows of the environment's weather table -- the
-rows the observation's forecast module exposes -- clamped at the end of the table.  Without n_scenarios no noise is drawn inside the
-horizon: with crop="current" the parent's present crop block is held over the horizon, with "nominal" the handle's parameters are
-used.  No reset happens either: a child that reaches its season end stops accumulating (`alive`), the step that reports `done` being
-its last.
+What the planner sees.  By default the children step on the true future rows of the environment's weather table -- the rows the
+observation's forecast module exposes -- clamped at the end of the table: perfect foresight of the weather.  With weather_sigma (below)
+every scenario steps on its own, wrong forecast instead.  Without n_scenarios no noise is drawn inside the horizon: with crop="current"
+the parent's present crop block is held over the horizon, with "nominal" the handle's parameters are used.  No reset happens either: a
+child that reaches its season end stops accumulating (`alive`), the step that reports `done` being its last.
 
 Robust planning (n_scenarios = S, glgym_plan_scenario / _rollout_scenarios / _aggregate): every candidate is simulated under S sampled
 futures of the 34 crop parameters -- the environment's own uncertainty_scale process, redrawn at every step (noise="step") or drawn
@@ -15,6 +15,15 @@ once and held (noise="hold") -- and scored by the mean of its n_tail worst retur
 Scenario s of greenhouse b is the same future for all K candidates (common random numbers), and the scenarios stay the same from
 rollout to rollout until new_scenarios(): candidates, and the iterations of one cem(), are compared like with like.  select, elites,
 refit, sample, cem and shift work on the aggregated [B, K] scores as they do on plain returns.
+
+Weather-forecast uncertainty (n_scenarios = S with weather_sigma, glgym_plan_weather): scenario s of greenhouse b gets a private window
+of H weather rows, the parent's coming rows with a forecast error on the seven columns the model reads -- zero at the row being
+integrated now, lag-1 correlated along the horizon (weather_phi), saturating at weather_sigma: additive [K] on tOut, tSky and tSoOut,
+relative and floored at 0 on iGlob, vpOut, co2Out and wind.  The futures are keyed like the crop scenarios' (scenario_seed, the same
+draw index: new_scenarios() and scenario_base_t move both) and shared by the K candidates.  noise_scale=0.0 gives weather-only
+scenarios: the prologue of every step then writes the nominal crop block, and the steps still run the per-env-crop build.  S = 1 is
+certainty-equivalent MPC on one wrong forecast.  The environment's own table is only read; dli and the day flags are not re-derived
+from the perturbed radiation, and vapour pressure, not relative humidity, is what stays put when tOut moves.
 
 The parent environment is only read: its state, random streams, draw counter, episode counters, metrics() and step_flags_t are after
 a rollout what they were before.
@@ -30,14 +39,35 @@ from typing import Any, Dict, Optional
 from . import _lib as L
 
 
+def _weather_sigma(weather_sigma, weather_phi):
+    """weather_sigma as the seven floats of include/glgym.h glgym_plan_weather_args.sigma; ValueError on anything else."""
+    if isinstance(weather_sigma, dict):
+        unknown = sorted(set(weather_sigma) - set(L.WEATHER_COLUMNS))
+        if unknown:
+            raise ValueError(f"weather_sigma: unknown columns {unknown}; the keys are {L.WEATHER_COLUMNS}")
+        weather_sigma = [weather_sigma.get(k, 0.0) for k in L.WEATHER_COLUMNS]
+    try:
+        sigma = [float(v) for v in weather_sigma]
+    except TypeError:
+        raise ValueError("weather_sigma must be a sequence of 7 floats or a dict keyed by column name") from None
+    if len(sigma) != len(L.WEATHER_COLUMNS) or not all(0.0 <= v < float("inf") for v in sigma):
+        raise ValueError(f"weather_sigma must hold 7 finite values >= 0, in the order {L.WEATHER_COLUMNS}")
+    if not 0.0 <= float(weather_phi) < 1.0:
+        raise ValueError("weather_phi must be in [0, 1)")
+    return sigma
+
+
 class Planner:
     def __init__(self, env, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal", n_scenarios: Optional[int] = None,
-                 noise_scale: Optional[float] = None, noise: str = "step", n_tail: Optional[int] = None, scenario_seed: int = 0):
+                 noise_scale: Optional[float] = None, noise: str = "step", n_tail: Optional[int] = None, scenario_seed: int = 0,
+                 weather_sigma=None, weather_phi: float = 0.0):
         if int(n_candidates) < 1 or int(horizon) < 1:
             raise ValueError("n_candidates and horizon must be at least 1")
         if n_scenarios is None:
             if noise_scale is not None or n_tail is not None:
                 raise ValueError("noise_scale and n_tail belong to scenario rollouts: give n_scenarios")
+            if weather_sigma is not None:
+                raise ValueError("weather_sigma belongs to scenario rollouts: give n_scenarios")
         else:
             if not 1 <= int(n_scenarios) <= L.MAX_SCENARIOS:
                 raise ValueError(f"n_scenarios must be in 1 .. {L.MAX_SCENARIOS}")
@@ -49,6 +79,9 @@ class Planner:
                 raise ValueError("scenario rollouts take horizon <= 65 536 and scenario_seed >= 0")
         if noise not in ("step", "hold"):
             raise ValueError("noise must be 'step' or 'hold'")
+        sigma = None if weather_sigma is None else _weather_sigma(weather_sigma, weather_phi)
+        if sigma is not None and env.B * int(n_scenarios) * int(horizon) > 2 ** 31 - 1:
+            raise ValueError("num_envs * n_scenarios * horizon (the rows of the weather windows) must not exceed 2^31 - 1")
         if crop not in ("nominal", "current"):
             raise ValueError("crop must be 'nominal' or 'current'")
         if not (float(gamma) >= 0.0) or float(gamma) == float("inf"):
@@ -112,6 +145,11 @@ class Planner:
             self._score_t, self._score_failed_t = self.ret_cand_t, self.failed_cand_t
             self.scenario_returns = self.ret_t.view(self.B, self.K, self.S)       # per-scenario results of the last rollout
             self.scenario_failed = self.failed_t.view(self.B, self.K, self.S)
+        self.weather_sigma, self.weather_phi = sigma, float(weather_phi)
+        self.weather_window_t = self.weather_window = None
+        if sigma is not None:
+            self.weather_window_t = z(self.B * self.S * self.H, env.nd)       # row (b*S + s)*H + h: scenario s of greenhouse b at horizon step h
+            self.weather_window = self.weather_window_t.view(self.B, self.S, self.H, env.nd)
         self.x, self.u = self.x_T[:, :self.C].t(), self.u_T[:, :self.C].t()
 
     def set_layout(self, layout: str):
@@ -139,10 +177,21 @@ class Planner:
 
     def _step_args(self):
         e = self.env
-        return L.make_step_args(self.C, self.ld, self.x_T.data_ptr(), self.u_T.data_ptr(), None, None, e.weather_t.data_ptr(),
-                                e.weather_rows, self.w_off_t.data_ptr(), self.timestep_t.data_ptr(),
+        table, rows = (e.weather_t, e.weather_rows) if self.weather_window_t is None else (self.weather_window_t, self.B * self.S * self.H)
+        return L.make_step_args(self.C, self.ld, self.x_T.data_ptr(), self.u_T.data_ptr(), None, None, table.data_ptr(),
+                                rows, self.w_off_t.data_ptr(), self.timestep_t.data_ptr(),
                                 self.crop_T.data_ptr() if self.crop_T is not None else None, e.N, self.reward_t.data_ptr(),
                                 self.info_T.data_ptr(), self.done_t.data_ptr(), None, self.step_flags_t.data_ptr())
+
+    def _weather(self):
+        """glgym_plan_weather: the scenarios' windows from the parents' coming rows, and the children's offsets into them (after fork(),
+        whose w_off they replace).  Reads the parents' w_off / timestep on the device: a replayed graph follows the environment."""
+        e = self.env
+        a = L.make_plan_args(L.PlanWeatherArgs, self.B, self.K, self.S, self.H, e.weather_rows, e.weather_t.data_ptr(), e.w_off_t.data_ptr(),
+                             e.timestep_t.data_ptr(), (C.c_double * 7)(*self.weather_sigma), self.weather_phi,
+                             self.scenario_seed & (2 ** 64 - 1), self._scen_draw, self.scenario_base_t.data_ptr(),
+                             self.weather_window_t.data_ptr(), self.w_off_t.data_ptr())
+        L.check(e._lib.glgym_plan_weather(e._h, C.byref(a), e._stream()), "glgym_plan_weather")
 
     def rollout(self, actions_t=None, controls_t=None):
         """Fork from the environment's current state and run the H-step rollout of every candidate.
@@ -153,7 +202,9 @@ class Planner:
         steps [B, K] i32, violations [3, B, K] f64 (co2, temp, rh), failed [B, K] u8.
         With scenarios (actions_t only): every candidate runs under its S futures; returned per candidate are the mean of its n_tail
         worst returns (NaN, with failed = 1, if a scenario failed or came back non-finite), alive = alive in every scenario, steps =
-        the fewest over the scenarios, the violations' means; scenario_returns / scenario_failed [B, K, S] hold the single runs."""
+        the fewest over the scenarios, the violations' means; scenario_returns / scenario_failed [B, K, S] hold the single runs.
+        With weather_sigma the scenarios' weather windows are rebuilt from the environment's present position first (weather_window
+        [B, S, H, nd] holds them afterwards)."""
         if (actions_t is None) == (controls_t is None):
             raise ValueError("give exactly one of actions_t / controls_t")
         if self.S and controls_t is not None:
@@ -182,6 +233,8 @@ class Planner:
             self._actions = self._rolled = None
             ctl_ptr = self._controls_T.data_ptr()
         self.fork()
+        if self.weather_window_t is not None:
+            self._weather()
         a = L.make_plan_args(L.PlanRolloutArgs, self.H, self.gamma, self._step_args(), act_ptr, ctl_ptr, self.ret_t.data_ptr(),
                              self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.alive_t.data_ptr(), self.failed_t.data_ptr())
         B, K = self.B, self.K
@@ -201,8 +254,8 @@ class Planner:
                 self.failed_t.view(B, K))
 
     def new_scenarios(self):
-        """Draw other futures from the next scenario rollout on: the scenario draw index moves by one.  (A replayed graph carries the index it
-        was captured with: add to scenario_base_t instead.)"""
+        """Draw other futures (crop and weather alike) from the next scenario rollout on: the scenario draw index moves by one.  (A replayed
+        graph carries the index it was captured with: add to scenario_base_t instead.)"""
         if not self.S:
             raise ValueError("new_scenarios() belongs to a planner built with n_scenarios")
         self._scen_draw += 1

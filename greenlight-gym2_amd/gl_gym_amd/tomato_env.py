@@ -453,7 +453,8 @@ class TomatoVecEnv:
         environment's per-env crop block (uncertainty_scale > 0) and holds it over the horizon; "nominal" plans with the handle's
         parameters.  Robust planning, keyword-only: n_scenarios=S simulates every candidate under S sampled futures of the crop block
         (noise_scale, default this environment's uncertainty_scale; noise="step" | "hold") and scores it by the mean of its n_tail
-        worst returns (default S: the mean); scenario_seed keys the futures."""
+        worst returns (default S: the mean); scenario_seed keys the futures.  weather_sigma (7 floats or a dict by column name) with
+        weather_phi gives every scenario its own wrong weather forecast as well (planner.py)."""
         from .planner import Planner
         return Planner(self, n_candidates, horizon, gamma=gamma, crop=crop, **scenarios)
 

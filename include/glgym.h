@@ -162,7 +162,8 @@ typedef struct {
  * 7: glgym_set_integrator / glgym_set_tolerances / glgym_get_solver_stats; later, still 7 (an added entry point, backward
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
- * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate */
+ * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
+ * glgym_plan_weather */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -640,6 +641,46 @@ typedef struct {
 int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void* stream);
 int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream);
 int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream);
+
+/* ---- weather-forecast uncertainty in scenario rollouts (csrc/gl_wscen.hpp, csrc/glgym_plan.hip) ------------------------------
+ * A rollout's children step on the true future rows of the weather table: perfect foresight.  glgym_plan_weather gives scenario s of
+ * greenhouse p (ps = p*S + s) its own, wrong forecast instead: a private window of H rows -- row ps*H + h of `window`, the parent's
+ * row at horizon step h with a forecast error on the seven columns the right-hand side reads (iGlob, tOut, vpOut, co2Out, wind,
+ * tSky, tSoOut) -- and child offsets that point into it.  The step kernels read one row per env-step, clamp(w_off + timestep, 0,
+ * weather_rows - 1): with step.weather = window, step.weather_rows = P*S*H and step.w_off = w_off_child a scenario rollout
+ * (glgym_plan_rollout_scenarios, which is unchanged) integrates the children on their windows.  Same conventions as above:
+ * struct_size first, GLGYM_EINVAL before anything is launched, asynchronous on `stream`, no allocation, no host synchronisation
+ * (capturable), plain vector stores, no atomics.  Opt-in: no other entry point changes.
+ *
+ * Source row of (p, h): clamp(w_off_parent[p] + timestep_parent[p] + h, 0, weather_rows - 1), the row a plain child reads.
+ * Innovation of (ps, h, column j < 7): r[0..3] = Philox4x32-10 of the counter (ps, lo32(D), hi32(D), 8*h + j) under the key
+ * (lo32(seed), hi32(seed) ^ 0x5753434e), D = draw_index + *draw_base -- the scenario draw index of glgym_plan_scenario under another
+ * key tag, so that one index moves both kinds of future.  In double, products and sums rounded separately: c_i = (r[i] + 0.5) * 2^-32
+ * - 0.5; eps = (((c_0 + c_1) + c_2) + c_3) * 1.7320508075688772: four centred uniforms scaled to unit variance, |eps| < 3.47.
+ * Error: e_0 = 0 (the row being integrated now is a measurement); e_h = phi*e_{h-1} + g_j*eps_h for h >= 1 (two products, one sum),
+ * g_j = sqrt(1 - phi*phi) * sigma[j] with the root taken once on the host: lag-1 correlation phi, standard deviation sigma_j
+ * sqrt(1 - phi^(2h)), saturating with the lead time.  The candidate k is not involved (common random numbers).
+ * Value from the source value w (T): columns 1, 5, 6 (temperatures) v = (T)((double)w + e); columns 0, 2, 3, 4 t = e*(double)w,
+ * v0 = (double)w + t, v = (T)(v0 < 0 ? 0 : v0).  sigma[j] = 0 gives the source value.  Columns 7 .. nd-1 are copied.
+ * w_off_child[(p*K + k)*S + s] = ps*H - timestep_parent[p] (may be negative; only the clamped sum is used): the child keeps the
+ * parent's timestep, hence its clock and its season end. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, S, H;          /* greenhouses, candidates, scenarios (<= 256), horizon (<= 65 536); P*S*H and P*K*S <= INT32_MAX */
+    int32_t weather_rows;        /* rows of `weather` (>= 1) */
+    const void* weather;         /* [weather_rows][nd] T: the parents' table (nd: the handle's) */
+    const int32_t* w_off_parent;      /* [P] */
+    const int32_t* timestep_parent;   /* [P] */
+    double sigma[7];             /* finite, >= 0: [K] for columns 1, 5, 6, relative for columns 0, 2, 3, 4 */
+    double phi;                  /* 0 <= phi < 1 */
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    void* window;                /* [P*S*H][nd] T out */
+    int32_t* w_off_child;        /* [P*K*S] out, or NULL */
+} glgym_plan_weather_args;
+
+int glgym_plan_weather(glgym_handle h, const glgym_plan_weather_args* a, void* stream);
 
 /* ---- rule-based controller (BASELINE config 1 "fixed rule-based actions") ------------------------------
  * u[6] = RuleBasedController.predict(x, weather[w_off + timestep], env clocks) for every env of the shard, written in the
