@@ -1175,6 +1175,11 @@ __global__ void crop_noise_kernel(T* crop_p, int B, int ld, const float* p0, flo
 // accumulator block (merged by vecnorm_merge_kernel): 1 024 blocks x 526 fp64 atomics onto the 33 cache lines of a single
 // block serialise in the L2 -- that, not the read, was most of the pass.
 constexpr int VN_REP = 16;
+// The sums are taken about a pivot, the column's value in row 0: sum(x - p) and sum((x - p)^2).  The merge forms the batch
+// variance as E[d^2] - E[d]^2, which cancels (mean / spread)^2 of the fp64 mantissa when taken about zero: a column of mean
+// 35 040 and spread 3e-3 came out 4e-3 off at B = 65 536, and on warm statistics that reached the normalised rows
+// (profiles/vecnorm_moments_cost.txt).  About a value of the column itself the two terms are of the size of the spread; the
+// difference of two float32 is exact in fp64.
 __global__ __launch_bounds__(1024) void vecnorm_moments_kernel(const float* __restrict__ obs, int B, int dim,
                                                                double* __restrict__ acc_all)
 {
@@ -1182,6 +1187,7 @@ __global__ __launch_bounds__(1024) void vecnorm_moments_kernel(const float* __re
     const int rows_per_block = (B + gridDim.x - 1) / gridDim.x;
     const int r0 = blockIdx.x * rows_per_block, r1 = min(B, r0 + rows_per_block);
     for (int c = threadIdx.x; c < dim; c += blockDim.x) {       // blockDim >= dim in practice: one column per thread
+        const double p = (double)obs[c];
         double s0 = 0.0, q0 = 0.0, s1 = 0.0, q1 = 0.0;
         int r = r0;
         for (; r + 7 < r1; r += 8) {
@@ -1190,11 +1196,11 @@ __global__ __launch_bounds__(1024) void vecnorm_moments_kernel(const float* __re
             for (int j = 0; j < 8; ++j) v[j] = obs[(size_t)(r + j) * dim + c];
 #pragma unroll
             for (int j = 0; j < 8; j += 2) {
-                const double a = (double)v[j], b = (double)v[j + 1];
+                const double a = (double)v[j] - p, b = (double)v[j + 1] - p;
                 s0 += a; q0 += a * a; s1 += b; q1 += b * b;
             }
         }
-        for (; r < r1; ++r) { const double v = (double)obs[(size_t)r * dim + c]; s0 += v; q0 += v * v; }
+        for (; r < r1; ++r) { const double v = (double)obs[(size_t)r * dim + c] - p; s0 += v; q0 += v * v; }
         if (r1 > r0) { atomicAdd(acc + c, s0 + s1); atomicAdd(acc + dim + c, q0 + q1); }
     }
 }
@@ -1224,8 +1230,9 @@ __global__ __launch_bounds__(256) void vecnorm_returns_kernel(const T* __restric
 // per-column 1/sqrt(var + eps) (fp64, so that pass 2 is two fp64 ops per element) -- ONE block: the count every column
 // reads is updated after a barrier, and scale[c] may overwrite acc[c], which only column c's own thread has read.
 __global__ __launch_bounds__(1024) void vecnorm_merge_kernel(double* mean, double* var, double* count, const double* acc, int dim,
-                                                            int B, double* ret_stats, const double* acc2, int do_obs,
-                                                            int do_ret, double eps, double* scale)
+                                                            int B, const float* __restrict__ obs, double* ret_stats,
+                                                            const double* acc2, int do_obs, int do_ret, double eps,
+                                                            double* scale)
 {
     const double n = (double)B;
     const double cnt = *count;
@@ -1233,7 +1240,8 @@ __global__ __launch_bounds__(1024) void vecnorm_merge_kernel(double* mean, doubl
         if (do_obs) {
             double sum = 0.0, sq = 0.0;
             for (int r = 0; r < VN_REP; ++r) { sum += acc[(size_t)r * 2 * dim + c]; sq += acc[(size_t)r * 2 * dim + dim + c]; }
-            const double bm = sum / n, bv = fmax(sq / n - bm * bm, 0.0);
+            const double dm = sum / n, bv = fmax(sq / n - dm * dm, 0.0);      // moments about the pivot obs[0][c]
+            const double bm = (double)obs[c] + dm;
             const double tot = cnt + n, delta = bm - mean[c];
             const double m2 = var[c] * cnt + bv * n + delta * delta * cnt * n / tot;
             mean[c] += delta * n / tot;
@@ -1410,7 +1418,13 @@ __global__ void pchip_eval_kernel(int n, int n_col, int n_out, int nd, const dou
     if (i >= n_out || col >= n_col) return;
     const double start = x[0], stop = x[n - 1];
     const double stepo = n_out > 1 ? (stop - start) / (double)(n_out - 1) : 0.0;
-    const double t = (i == n_out - 1 && n_out > 1) ? stop : (double)i * stepo + start;
+    double t = stop;
+    if (i < n_out - 1 || n_out == 1) {
+        // numpy's linspace rounds i * step before it adds start; fused into one FMA the point moves by an ulp of t (2e-9 s at
+        // day 100), which a zig-zag column with knots 300 s apart turns into 6e-12 of its range
+#pragma clang fp contract(off)
+        t = (double)i * stepo + start;
+    }
     int lo = 0, hi = n - 1;                         // last k with x[k] <= t, clipped to n - 2
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (x[mid] <= t) lo = mid; else hi = mid; }
     const int k = lo > n - 2 ? n - 2 : lo;
@@ -2192,7 +2206,7 @@ extern "C" int glgym_vecnorm(glgym_handle h, const glgym_vecnorm_args* a, void* 
     double* scale = acc;                           // the moment accumulators are dead once their column is merged
     if (do_obs || do_ret || a->norm_obs)
         hipLaunchKernelGGL(vecnorm_merge_kernel, dim3(1), dim3(1024), 0, st, a->obs_mean, a->obs_var, a->obs_count, acc, dim, B,
-                           a->ret_stats, acc2, do_obs, do_ret, a->epsilon, a->norm_obs ? scale : nullptr);
+                           a->obs, a->ret_stats, acc2, do_obs, do_ret, a->epsilon, a->norm_obs ? scale : nullptr);
     const size_t total = (size_t)B * dim;
     if (a->norm_obs) {
         int blocks = (B + 15) / 16;
