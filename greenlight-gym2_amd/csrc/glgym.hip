@@ -2234,15 +2234,15 @@ extern "C" {
 
 static bool obs_args_ok(glgym_handle h, const glgym_obs_args* a)
 {
-    return h && a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->weather && a->w_off && a->timestep && a->start_day && a->obs &&
-           a->Np >= 0 && a->Np <= OBS_MAX_NP;
+    return h && a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->weather && a->weather_rows >= 1 && a->w_off && a->timestep &&
+           a->start_day && a->obs && a->Np >= 0 && a->Np <= OBS_MAX_NP;      // weather_rows < 1: the row clamp would yield row -1
 }
 
 int glgym_obs(glgym_handle h, const glgym_obs_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);
     if (!obs_args_ok(h, a)) {
-        g_err = "glgym_obs: bad arguments (null pointer, ld < B, or Np outside 0..128)";
+        g_err = "glgym_obs: bad arguments (null pointer, ld < B, weather_rows < 1, or Np outside 0..128)";
         return GLGYM_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -2254,7 +2254,7 @@ int glgym_step_obs(glgym_handle h, const glgym_step_args* a, const glgym_obs_arg
     if (!h || !a || !oa) { g_err = "glgym_step_obs: null handle / arguments"; return GLGYM_EINVAL; }
     if (oa->mask) { g_err = "glgym_step_obs: full-mode observations only (glgym_obs_args.mask must be NULL)"; return GLGYM_EINVAL; }
     if (!obs_args_ok(h, oa)) {         // before the step is launched: nothing runs on bad arguments
-        g_err = "glgym_step_obs: bad observation arguments (null pointer, ld < B, or Np outside 0..128)";
+        g_err = "glgym_step_obs: bad observation arguments (null pointer, ld < B, weather_rows < 1, or Np outside 0..128)";
         return GLGYM_EINVAL;
     }
     int fused = 0;
@@ -2289,14 +2289,14 @@ int glgym_obs_dim(glgym_handle h, int Np)
 
 static bool reset_args_ok(const glgym_reset_args* a)
 {
-    return a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->timestep && a->weather && a->w_off;
+    return a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->timestep && a->weather && a->weather_rows >= 1 && a->w_off;
 }
 
 int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream)
 {
     DeviceGuard dev_guard(h);
     if (!h || !reset_args_ok(a)) {
-        g_err = "glgym_reset: bad arguments";
+        g_err = "glgym_reset: bad arguments (null handle or pointer, B < 1, ld < B, or weather_rows < 1)";
         return GLGYM_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -2325,7 +2325,7 @@ int glgym_step_obs_reset(glgym_handle h, const glgym_step_args* a, const glgym_o
         return GLGYM_EINVAL;
     }
     if (!obs_args_ok(h, oa) || !reset_args_ok(ra)) {
-        g_err = "glgym_step_obs_reset: bad observation or reset arguments";      // before the step is launched: nothing runs on bad arguments
+        g_err = "glgym_step_obs_reset: bad observation or reset arguments (null pointer, ld < B, weather_rows < 1, or Np outside 0..128)";      // before the step is launched: nothing runs on bad arguments
         return GLGYM_EINVAL;
     }
     glgym_obs_args full = *oa, masked = *oa;

@@ -206,7 +206,11 @@ typedef struct {
  * factorisations go to metric slots GLGYM_METRIC_BDF..+3. */
 #define GLGYM_SF_BDF 2048                  /* the env-step was integrated by the BDF integrator */
 
-/* Device-pointer arguments of observation assembly (row-major output, what SB3 / Gymnasium consume). */
+/* Device-pointer arguments of observation assembly (row-major output, what SB3 / Gymnasium consume).
+ * Weather rows: env b shows row w_off[b] + k, k = max(timestep[b] - 1, 0), and its forecast block rows w_off[b] + k + 1 .. + Np.
+ * Every row index is clamped to [0, weather_rows - 1] on its own: a window that runs past the table repeats the last row, a negative
+ * w_off reads row 0 (the reference would raise an IndexError, or wrap around for a negative index).  weather_rows < 1 is refused
+ * (GLGYM_EINVAL), here and in glgym_step_obs / glgym_step_obs_reset. */
 typedef struct {
     int32_t B, ld;
     const void* x;             /* SoA [28][ld] T */
@@ -235,7 +239,11 @@ typedef struct {
     int32_t* w_off;            /* [B] in/out: first weather row of the episode.  With a start table (below) the kernel
                                   draws the new episode's start itself, otherwise it uses the value found here */
     /* optional start table (TomatoEnv.reset picks (growth_year, start_day) at random, tomato_env.py:236-244):
-       entry j = Philox4x32-10(key = seed, counter = (env, episode[b])) mod n_starts; episode[b] is then incremented */
+       entry j = R[0] mod n_starts (unsigned), R = Philox4x32-10(counter = {b, (uint32)episode[b], 0x5eed, 0}, key = {seed low
+       word, seed high word}), b the env's index in the batch; episode[b] (taken as 0 where `episode` is NULL) is then incremented.
+       The draw of env b depends on (b, episode[b], seed) alone -- not on B, the mask or the launch geometry.  The third counter
+       word 0x5eed keeps the stream apart from glgym_crop_noise's, whose counter is {b, draw low, draw high, block 0..8}.
+       The state comes from row clamp(w_off[b], 0, weather_rows - 1); weather_rows < 1 is refused (GLGYM_EINVAL). */
     const int32_t* start_rows; /* [n_starts] or NULL */
     const float* start_days;   /* [n_starts] day of year of each start row */
     int32_t n_starts;

@@ -265,6 +265,77 @@ def g_controller():
     print("controller_kat: u range", np.min(Uo), np.max(Uo))
 
 
+CONTROLLER_CONFIGS = dict(
+    defaults={},
+    # all 29 constants pairwise distinct (the defaults share rh_max = rhMax and three bands of -1): a swap of two fields shows
+    distinct=dict(lamps_on=2, lamps_off=17, lamps_day_start=-1.5, lamps_day_stop=366.5, lamps_off_sun=410, lamp_rad_sum_limit=11,
+                  temp_setpoint_day=20.5, temp_setpoint_night=16, heat_correction=0.75, heat_deadzone=4.5, co2_day=820,
+                  vent_heat_Pband=3.5, rh_max=84, mech_dehumid_Pband=2.5, vent_rh_Pband=5.5, t_vent_off=1.25,
+                  vent_cold_Pband=-1.1, thScrSpDay=6, thScrSpNight=9, thScrPband=-0.9, thScrDeadZone=3, thScrRh=-2.25,
+                  thScrRhPband=1.75, lampExtraHeat=2.75, blScrExtraRh=90, rhMax=87, tHeatBand=-1.3, co2Band=-110, useBlScr=0.7),
+    lamps_overnight=dict(lamps_on=20, lamps_off=6),
+    lamps_never=dict(lamps_on=8, lamps_off=8),
+    lamps_winter=dict(lamps_day_start=300, lamps_day_stop=60),
+    no_blackout=dict(useBlScr=0, heat_correction=1.5))
+CONTROLLER_N = 64
+
+
+def g_controller_configs():
+    """The reference RuleBasedController.predict under six constructor configs on 64 tuples (drawn like g_controller), with the
+    clocks placed on the rules' edges: tuples 0..9 carry hours on, within 1e-9 of, and one hour before and after lamps_on and
+    lamps_off, tuples 10..15 days on and within 1e-9 of lamps_day_start / lamps_day_stop.  Every tuple also has a (timestep,
+    start_day) pair; U_hd[a][b] is the answer with the hour explicit (a = 0: `hour`) or derived from the timestep at dt = 900 s
+    (a = 1: `hour_d` = timestep/4 mod 24) and the day likewise (b = 0: `doy`, b = 1: `doy_d` = start_day + timestep/96) -- the
+    four combinations glgym_rule_based offers."""
+    w = weather_10day()
+    x0 = init_state(w[0])
+    rng = np.random.default_rng(1100)
+    n = CONTROLLER_N
+    X = np.empty((n, 28)); D = np.empty((n, 10))                                       # one set of states / weather rows for all configs
+    for i in range(n):
+        x = x0 * (1 + 0.05 * rng.standard_normal(28))
+        x[2] = rng.uniform(10, 30); x[15] = rng.uniform(0.4, 1.0) * satVp(x[2]); x[0] = rng.uniform(400, 2000)
+        X[i], D[i] = x, w[int(rng.integers(0, 1056))]
+    out = dict(names=np.array(list(CONTROLLER_CONFIGS)), fields=np.array(list(RULE_BASED)), X=X, D=D)
+    for ci, (name, kw) in enumerate(CONTROLLER_CONFIGS.items()):
+        cfg = dict(RULE_BASED, **kw)
+        vals = [float(cfg[k]) for k in RULE_BASED]
+        if name == "distinct":
+            assert len(set(vals)) == 29
+        assert all(abs(cfg[k]) >= 0.5 for k in cfg if k.lower().endswith("band"))
+        ctrl = RuleBasedController(**cfg)
+        rng = np.random.default_rng(1101 + ci)
+        hour, doy = rng.uniform(0, 24, n), rng.uniform(0, 365, n)
+        ts = rng.integers(0, 960, n)
+        sday = rng.uniform(0, 364, n).astype(np.float32)
+        offs = (0.0, -1e-9, 1e-9, -1.0, 1.0)
+        for j, t in enumerate((cfg["lamps_on"], cfg["lamps_off"])):
+            for q, off in enumerate(offs):
+                i = 5 * j + q
+                hour[i] = (t + off) % 24.0
+                ts[i] = int(round(4 * ((t + off) % 24.0))) % 96 + 96 * (i % 7)          # the derived hour sits on the same edge
+        for j, t in enumerate((cfg["lamps_day_start"], cfg["lamps_day_stop"])):
+            for q, off in enumerate(offs[:3]):
+                i = 10 + 3 * j + q
+                doy[i] = min(max(t + off, 0.0), 366.0)
+                sday[i] = np.float32(min(max(t, 0.0), 364.0))
+                ts[i] = (0, 0, 96)[q] if 0 <= t <= 364 else ts[i]                       # derived: on the day, and one day later
+        hour_d = (ts * (900.0 / 3600.0)) % 24.0
+        doy_d = sday.astype(np.float64) + ts * ((900.0 / 86400.0) % 365)
+        U = np.empty((2, 2, n, 6))
+        for a, hh in enumerate((hour, hour_d)):
+            for b, dd in enumerate((doy, doy_d)):
+                for i in range(n):
+                    env = SimpleNamespace(nu=6, hour_of_day=float(hh[i]), day_of_year=float(dd[i]))
+                    U[a, b, i] = ctrl.predict(X[i], D[i], env)
+        out.update({f"{name}_cfg": np.array(vals), f"{name}_hour": hour, f"{name}_doy": doy,
+                    f"{name}_timestep": ts.astype(np.int32), f"{name}_start_day": sday, f"{name}_hour_d": hour_d,
+                    f"{name}_doy_d": doy_d, f"{name}_U_hd": U})
+        print("controller_kat_configs %-16s lamps on in %2d / %2d / %2d / %2d of %d tuples" %
+              ((name,) + tuple(int((U[a, b, :, 4] > 0.5).sum()) for a in (0, 1) for b in (0, 1)) + (n,)))
+    np.savez_compressed(HERE / "controller_kat_configs.npz", **out)
+
+
 def g_rollout_summer():
     """3-day / 289-step rollout on the synthetic weather generator's midsummer-like window (700 W/m2 peaks): the
     regime the Bleiswijk autumn fixture does not reach (strong photosynthesis, open vents, high temperatures)."""
@@ -898,7 +969,7 @@ def g_refenv_day60():
 
 ALL = dict(weather_csv=g_weather_csv, refenv_day60=g_refenv_day60, holdout_noisy=g_holdout_noisy, holdout_random=g_holdout_random, holdout_rulebased=g_holdout_rulebased, holdout_runtime=g_holdout_runtime,
            holdout_season=g_holdout_season, jump=g_jump, refobs=g_refobs, refenv=g_refenv, storm=g_storm, helpers2=g_helpers2, pipe=g_pipe, rollout_summer=g_rollout_summer, params=g_params, weather=g_weather, rhs=g_rhs, step=g_step, reward=g_reward, noise=g_noise,
-           controller=g_controller, env=g_env, rollout=g_rollout)
+           controller=g_controller, controller_configs=g_controller_configs, env=g_env, rollout=g_rollout)
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(ALL)
