@@ -2468,6 +2468,11 @@ int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* str
                 "without a finite temperature > 0)";
         return GLGYM_EINVAL;
     }
+    // the kernel multiplies by 1 / temperature: at 2^-1024 and below that is +inf and the best candidate's own (ret - max) * inf = 0 * inf a NaN
+    if (a->mean_sequence && !std::isfinite(1.0 / a->temperature)) {
+        g_err = "glgym_plan_select: temperature is too small (1 / temperature is not finite: it must be above 2^-1024, about 5.6e-309)";
+        return GLGYM_EINVAL;
+    }
     DeviceGuard dev_guard(h);
     HIPCHK(plan_select_launch(*a, (hipStream_t)stream));
     return GLGYM_OK;

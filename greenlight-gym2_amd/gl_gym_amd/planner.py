@@ -57,6 +57,17 @@ def _weather_sigma(weather_sigma, weather_phi):
     return sigma
 
 
+def _select_temperature(temperature) -> float:
+    """The MPPI temperature as glgym_plan_select takes it: > 0 with a finite reciprocal (the kernel multiplies by 1 / temperature; at
+    2^-1024 and below that is +inf, and the best candidate's own 0 * inf a NaN); ValueError on anything else."""
+    t = float(temperature)
+    if not t > 0.0:
+        raise ValueError("temperature must be > 0")
+    if 1.0 / t == float("inf"):
+        raise ValueError("temperature must have a finite reciprocal (above 2^-1024, about 5.6e-309): 1 / temperature overflows")
+    return t
+
+
 class Planner:
     def __init__(self, env, n_candidates: int, horizon: int, gamma: float = 1.0, crop: str = "nominal", n_scenarios: Optional[int] = None,
                  noise_scale: Optional[float] = None, noise: str = "step", n_tail: Optional[int] = None, scenario_seed: int = 0,
@@ -270,8 +281,8 @@ class Planner:
         has_a = self._actions is not None
         if not has_a and (sequence or temperature is not None):
             raise ValueError("best_sequence / mean_sequence need a rollout of actions_t")
-        if temperature is not None and not float(temperature) > 0.0:
-            raise ValueError("temperature must be > 0")
+        if temperature is not None:
+            _select_temperature(temperature)
         a = L.make_plan_args(L.PlanSelectArgs, self.B, self.K, self.H, self._score_t.data_ptr(), self._score_failed_t.data_ptr(),
                              self._actions.data_ptr() if has_a else None, self.best_k_t.data_ptr(), self.best_ret_t.data_ptr(),
                              self.best_action_t.data_ptr() if has_a else None, self.best_sequence_t.data_ptr() if sequence else None,

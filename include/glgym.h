@@ -503,7 +503,8 @@ typedef struct {
     double* best_ret;            /* [P] out */
     float* best_action;          /* [P][6] out = actions[0][p*K + best_k], or NULL */
     float* best_sequence;        /* [H][P][6] out or NULL */
-    double temperature;          /* > 0 with mean_sequence; ignored otherwise */
+    double temperature;          /* finite and > 0 with a finite 1 / temperature (above 2^-1024) with mean_sequence, else GLGYM_EINVAL;
+                                    ignored otherwise */
     float* mean_sequence;        /* [H][P][6] out or NULL */
 } glgym_plan_select_args;
 
