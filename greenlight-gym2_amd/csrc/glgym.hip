@@ -1,13 +1,18 @@
-// glgym.hip -- gfx950 kernels + the C ABI declared in include/glgym.h.
+// glgym.hip -- the integrating gfx950 kernels and the part of the C ABI (include/glgym.h) that launches them.  ONLY what instantiates an
+// integrating kernel lives here: every other kernel and its entry points have a translation unit of their own (glgym_env.hip,
+// glgym_ancillary.hip, glgym_plan.hip, glgym_rng.hip, glgym_bdf.hip), so that an edit over there neither recompiles nor can change
+// the kernels below.  A change to this file owes their instruction-for-instruction comparison (tools/isa_compare.py).
 //
 // Kernels (one lane = one environment; a 64-lane wavefront = one workgroup = 64 environments):
 //   step_kernel   fused TomatoEnv.step(): action->control, weather-row gather, tier-2 precompute,
 //                 n_sub x RK4 of the GreenLight ODE (gl_model.hpp), failure check, reward / violation /
 //                 info epilogue, terminal test, wave-level metric reduction.   [VALU/transcendental bound]
-//                 OBS builds (glgym_step_obs): the same, and each wavefront then also writes the observation rows of its 64 environments.
-//   obs_kernel    row-major observation assembly incl. the weather-forecast gather.      [HBM-write bound]
-//   reset_kernel  masked init_state().        crop_noise_kernel  Philox4x32-10 parameter noise.
-//   evalf_kernel / rhs_kernel                 row-major double I/O for the reference-compatible evalF and tests.
+//                 OBS builds (glgym_step_obs): the same, and each wavefront then also writes the observation rows of its 64 environments
+//                 (and, behind them, resets its finished ones: glgym_step_obs_reset) with gl_envlayer.hpp's device functions.
+//   step_kernel_quad                          the same step, four lanes per environment (gl_model_quad.hpp).
+//   evalf_kernel* / rhs_kernel                row-major double I/O for the reference-compatible evalF and tests.
+// Host side: the default-constant image, handle create / destroy / setters, glgym_evalF, glgym_rhs, glgym_step, glgym_step_obs,
+// glgym_step_obs_reset, the timer, and the definition of the error string (glgym_internal.h).
 // No MFMA anywhere: the path is elementwise + transcendental, not a contraction.
 #include <hip/hip_runtime.h>
 
@@ -26,23 +31,15 @@
 #include "gl_reward.hpp"
 #include "gl_step_select.hpp"
 #include "glgym_bdf.h"
-#include "glgym_rng.h"
-#include "glgym_plan.h"
+#include "glgym_internal.h"
+#include "gl_envlayer.hpp"
 
 using namespace glm;
+using namespace glenv;
+
+thread_local std::string g_err;      // glgym_last_error's string; every TU's entry points write it (glgym_internal.h)
 
 namespace {
-
-thread_local std::string g_err;
-
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
-            return GLGYM_EHIP;                                                                         \
-        }                                                                                              \
-    } while (0)
 
 constexpr int WAVE = 64;
 
@@ -98,105 +95,6 @@ template <class T> __device__ __forceinline__ T wave_sum(T v)
     return v;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// the 23 core observation features (observations.py:70-161), shared by obs_kernel and the observation epilogue of step_kernel
-// ---------------------------------------------------------------------------------------------------
-// j: 0 co2_ppm(x0,x2) 1 x2 2 RH(x15,x2) 3 x9 | 4 x21 5 x25 6 x26 | 7..12 u | 13 d0 14 d1 15 RH(d2,d1)
-//    16 co2_ppm(d3,d1) 17 d4 | 18 timestep 19..22 sin/cos clocks
-// prim: the feature's own input (x, u or weather column; unused from j = 18), aux: tAir (j < 13) or tOut.  ts: the env's timestep AFTER
-// the step's increment; the row / "timestep" the reference shows is the pre-increment one, k = ts - 1 (0 for a freshly reset env).
-// Straight-line selects: with a run-time j (obs_kernel) no branch per feature, with a compile-time j (step_kernel) everything but the
-// feature's own arithmetic folds away.  ONE definition, so that both kernels produce the same bits.
-constexpr int OBS_NCORE = 23;
-__device__ __forceinline__ float obs_core_feature(int j, float prim, float aux, float sday, int ts, double doy_inc, double hod_inc)
-{
-    // No implicit contraction in here: which products the compiler fuses into a following add depends on the caller -- with a
-    // compile-time j it turned rev - floor(rev) into fma(t, c, -floor(t * c)), which is not 0 where rev is a whole number (step 96 of
-    // an episode), with a run-time j it did not.  The one fused operation obs_kernel has always had is written out.
-#pragma clang fp contract(off)
-    const float kPpm = (float)(8.3144598 / (101325.0 * 44.01e-3));
-    const int k = ts > 0 ? ts - 1 : 0;
-    // fp32 hardware transcendentals: the observation block is float32 (observation_space dtype)
-    const float sat = 610.78f * __builtin_amdgcn_exp2f(1.44269504f * 17.2694f * aux * __builtin_amdgcn_rcpf(aux + 238.3f));
-    const float rh = fminf(fmaxf(100.0f * prim * __builtin_amdgcn_rcpf(sat), 0.0f), 100.0f);
-    const float ppm = kPpm * (aux + 273.15f) * prim;
-    // v_sin_f32 / v_cos_f32 take revolutions: sin(2*pi*x)   (tomato_env.py:126-128)
-    const int c = j - 18;
-    const double rev = (c <= 2) ? __builtin_fma((double)ts, doy_inc, (double)sday) * (1.0 / 365.0)
-                                : (double)ts * hod_inc * (1.0 / 24.0);
-    const float fr = (float)(rev - floor(rev));
-    const float clk = (c == 1 || c == 3) ? __builtin_amdgcn_sinf(fr) : __builtin_amdgcn_cosf(fr);
-    float v = prim;
-    v = (j == 0 || j == 16) ? ppm : v;
-    v = (j == 2 || j == 15) ? rh : v;
-    v = (j == 18) ? (float)k : v;
-    v = (j > 18) ? clk : v;
-    return v;
-}
-// module (GLGYM_OBS_*) and column inside it of core feature j
-__device__ __forceinline__ constexpr int obs_core_module(int j) { return j < 4 ? 0 : j < 7 ? 1 : j < 13 ? 2 : j < 18 ? 3 : 4; }
-__device__ __forceinline__ constexpr int obs_core_col(int j) { return j < 4 ? j : j < 7 ? j - 4 : j < 13 ? j - 7 : j < 18 ? j - 13 : j - 18; }
-
-// counter-based generator shared by the reset (episode start draw) and crop-noise kernels
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned* out)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// one environment's reset: the episode start draw and init_state (utils.py:13-46) -- reset_kernel's body, shared with the auto-reset
-// epilogue of step_kernel.  ONE definition, so that both produce the same bits.
-// ---------------------------------------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ void reset_env(int b, int ld, T* x, T* u, int* timestep, const T* weather, int weather_rows, int* w_off,
-                                          const int* start_rows, const float* start_days, int n_starts, float* start_day, int* episode,
-                                          unsigned long long seed, int nd)
-{
-    // No implicit contraction in here (obs_core_feature): the two fused operations reset_kernel has always had are written out.
-#pragma clang fp contract(off)
-    if (start_rows && n_starts > 0) {            // draw this episode's start (tomato_env.py:236-244)
-        const int ep = episode ? episode[b] : 0;
-        unsigned rnd[4];
-        philox4x32_10((unsigned)b, (unsigned)ep, 0x5eedu, 0u, (unsigned)seed, (unsigned)(seed >> 32), rnd);
-        const int j = (int)(rnd[0] % (unsigned)n_starts);
-        w_off[b] = start_rows[j];
-        if (start_day && start_days) start_day[b] = start_days[j];
-        if (episode) episode[b] = ep + 1;
-    }
-    int r = w_off[b];
-    r = r < 0 ? 0 : (r >= weather_rows ? weather_rows - 1 : r);
-    const double co2Out = (double)weather[(size_t)r * nd + 3], tSoOut = (double)weather[(size_t)r * nd + 6];
-    const double tAir = 16.5;
-    double xi[NX];
-    xi[0] = xi[1] = co2Out;
-    for (int i = 2; i <= 10; ++i) xi[i] = tAir;
-    xi[4] = tAir + 4;
-    xi[11] = 0.25 * (3.0 * tAir + tSoOut);
-    xi[12] = 0.25 * __builtin_fma(2.0, tSoOut, 2.0 * tAir);
-    xi[13] = 0.25 * __builtin_fma(3.0, tSoOut, tAir);
-    xi[14] = tSoOut;
-    xi[15] = xi[16] = 90.0 / 100.0 * (610.78 * exp(17.2694 * tAir / (tAir + 238.3)));
-    xi[17] = xi[18] = xi[19] = xi[20] = tAir;
-    xi[21] = xi[4];
-    xi[22] = 0.0; xi[23] = 9.5283e4; xi[24] = 2.5107e5; xi[25] = 5.5338e4; xi[26] = 3.0978e3; xi[27] = 0.0;
-    for (int i = 0; i < NX; ++i) x[(size_t)i * ld + b] = T(xi[i]);
-    for (int j = 0; j < NU; ++j) u[(size_t)j * ld + b] = T(0);
-    timestep[b] = 0;
-}
-
-#ifndef GL_OBS_ROWS
-#define GL_OBS_ROWS 16
-#endif
-constexpr int OBS_ROWS = GL_OBS_ROWS, OBS_MAX_NP = 128;     // obs_kernel's LDS span = rows * (23 + 5 Np) floats <= 42 KB
 // what step_kernel's OBS build needs beyond StepArgsT to write the observation rows of its 64 environments (obs_kernel's arguments
 // that the step does not have already)
 struct StepObsArgs {
@@ -952,543 +850,7 @@ __global__ __launch_bounds__(WAVE) void evalf_kernel(const double* x, const doub
     if (failed) atomicAdd(n_failed, 1);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// observations: [B][23 + 5*Np] f32 row-major (observations.py:59-182).  One wavefront per env row so the
-// 1 KB row is written with consecutive lanes on consecutive addresses.
-// ---------------------------------------------------------------------------------------------------
-template <class T> struct ObsArgsT {
-    int B, ld;
-    const T* x; const T* u; const T* weather; int weather_rows;
-    const int* w_off; const int* timestep; const float* start_day;
-    int Np; float* obs; double doy_inc, hod_inc;     // (dt/86400) mod 365 [days], dt/3600 [h] per env-step
-    const unsigned char* mask; float* term_obs;
-    int nd;                                          // weather row stride
-    int moff[6], dim;                                // first column of each observation module (-1 = absent), row width
-};
-
-// OBS_ROWS (16) consecutive env rows = one contiguous, 32-byte aligned span of the row-major output.  The span is
-// assembled in LDS and streamed out with 16-byte stores, lane t writing float4 t, t+256, ... (fully coalesced).
-// The kernel is latency-, not bandwidth-bound (a block's chain is: scalar loads of the rows' clocks -> gathers -> LDS ->
-// barrier -> stores), so everything is arranged to keep many independent loads in flight per lane: the 16 window bases
-// are loaded up front, the 23 state / current-weather / clock features are straight-line code (pointer selects instead
-// of a branch per feature: 3 loads in flight), and each lane gathers one forecast element for all 16 rows at once from
-// the L2-resident weather table.  Measured at B = 65 536, Np = 48: 44 us (first LDS version) -> 33 (independent gathers)
-// -> 26 (branch-free features) -> 24 us (16 rows per block) = 2.9 TB/s written; a plain fill of the buffer takes 11.6 us.
-// Masked mode (auto-reset) copies only the finished rows, after saving their previous content as SB3's
-// terminal_observation.
-template <class T> __global__ __launch_bounds__(256) void obs_kernel(ObsArgsT<T> a)
-{
-    constexpr int ROWS = OBS_ROWS, NCORE = OBS_NCORE;
-    extern __shared__ float4 span4[];               // ROWS * dim floats (dynamic: 8.4 KB at Np = 48), 16-byte aligned
-    float* span = reinterpret_cast<float*>(span4);
-    const int tid = threadIdx.x;
-    const int dim = a.dim;
-    for (int rb = blockIdx.x * ROWS; rb < a.B; rb += gridDim.x * ROWS) {
-        const int nrows = min(ROWS, a.B - rb);
-        if (a.mask) {                                 // masked mode: skip strips without a finished env
-            int any = 0;
-            for (int r = 0; r < nrows; ++r) any |= a.mask[rb + r];
-            if (!any) continue;                       // block-uniform
-        }
-        // first weather row of each env's window (the row / "timestep" the reference shows is the pre-increment one):
-        // block-uniform addresses -> scalar loads, all eight issued before anything depends on them
-        int base_r[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            const int b = rb + (r < nrows ? r : 0);
-            const int ts = a.timestep[b];
-            base_r[r] = a.w_off[b] + (ts > 0 ? ts - 1 : 0);
-        }
-        for (int e = tid; e < ROWS * NCORE; e += 256) {
-            // straight-line code for all 23 features: two pointer selects, three loads in flight, arithmetic selects --
-            // a branch per feature would serialise one memory round trip per branch inside the wave
-            const int r = e / NCORE, j = e - r * NCORE;
-            const int b = rb + (r < nrows ? r : 0);
-            const int ts = a.timestep[b];
-            int base = 0;
-#pragma unroll
-            for (int rr = 0; rr < ROWS; ++rr) base = (rr == r) ? base_r[rr] : base;
-            base = base >= a.weather_rows ? a.weather_rows - 1 : (base < 0 ? 0 : base);
-            const T* wrow = a.weather + (size_t)base * a.nd;
-            // (the features and their inputs: obs_core_feature)
-            const int xi = j == 0 ? 0 : j == 1 ? 2 : j == 2 ? 15 : j == 3 ? 9 : j == 4 ? 21 : j == 5 ? 25 : 26;
-            const T* p1 = j < 7 ? a.x + (size_t)xi * a.ld + b
-                                : (j < 13 ? a.u + (size_t)(j - 7) * a.ld + b : wrow + (j < 18 ? j - 13 : 0));
-            const T* p2 = j < 13 ? a.x + (size_t)2 * a.ld + b : wrow + 1;        // tAir or tOut
-            const float prim = (float)*p1, aux = (float)*p2, sday = a.start_day[b];
-            const float v = obs_core_feature(j, prim, aux, sday, ts, a.doy_inc, a.hod_inc);
-            // column of feature j in the configured module order (TomatoEnv._get_obs concatenates the modules in
-            // the order of the yml list, tomato_env.py:193-198)
-            const int mo = j < 4 ? a.moff[0] : j < 7 ? a.moff[1] : j < 13 ? a.moff[2] : j < 18 ? a.moff[3] : a.moff[4];
-            const int jl = j < 4 ? j : j < 7 ? j - 4 : j < 13 ? j - 7 : j < 18 ? j - 13 : j - 18;
-            if (r < nrows && mo >= 0) span[r * dim + mo + jl] = v;
-        }
-        // raw forecast rows, no unit conversion (:175-182): element q of the block = weather[base+1 + q/5][q%5]
-        const int nf = a.moff[5] >= 0 ? 5 * a.Np : 0;
-        for (int q = tid; q < nf; q += 256) {
-            const int i = q / 5, c = q - i * 5;              // division by a constant: mul + shift
-            float v[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {                 // eight independent gathers in flight per lane
-                int row = base_r[r] + 1 + i;
-                row = row >= a.weather_rows ? a.weather_rows - 1 : (row < 0 ? 0 : row);
-                v[r] = (float)a.weather[(size_t)row * a.nd + c];
-            }
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r)
-                if (r < nrows) span[r * dim + a.moff[5] + q] = v[r];
-        }
-        __syncthreads();
-        float* out = a.obs + (size_t)rb * dim;
-        if (!a.mask && nrows == ROWS) {                      // full span: 16-byte stores (rb*dim*4 is a multiple of 32)
-            const int n4 = (ROWS * dim) >> 2;                // ROWS multiple of 8 -> exact
-            float4* out4 = reinterpret_cast<float4*>(out);
-            typedef float v4f __attribute__((ext_vector_type(4)));
-            const v4f* src4 = reinterpret_cast<const v4f*>(span4);
-            v4f* dst4 = reinterpret_cast<v4f*>(out4);
-            for (int e = tid; e < n4; e += 256) __builtin_nontemporal_store(src4[e], &dst4[e]);      // 69 MB per call, read by nobody on the device before the next step kernel has run
-        } else {
-            for (int r = 0; r < nrows; ++r) {
-                if (a.mask && !a.mask[rb + r]) continue;
-                for (int jj = tid; jj < dim; jj += 256) {
-                    const size_t e = (size_t)r * dim + jj;
-                    if (a.mask && a.term_obs) a.term_obs[(size_t)rb * dim + e] = out[e];     // SB3 terminal_observation
-                    out[e] = span[e];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// rule-based controller (baseline.py:68-227), one thread per env, fp64 throughout
-// ---------------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void rule_based_kernel(glgym_rule_cfg c, int B, int ld, const T* __restrict__ x,
-                                                         const T* __restrict__ weather, int weather_rows,
-                                                         const int* __restrict__ w_off, const int* __restrict__ timestep,
-                                                         const float* __restrict__ start_day, const double* hour,
-                                                         const double* doy_in, double doy_inc, double hod_inc,
-                                                         T* __restrict__ control, int nd)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int ts = timestep[b];
-    int row = w_off[b] + ts;
-    row = row >= weather_rows ? weather_rows - 1 : (row < 0 ? 0 : row);
-    const T* w = weather + (size_t)row * nd;
-    const double iGlob = (double)w[0], tOut = (double)w[1], dli = (double)w[7], isDay = (double)w[8],
-                 isDaySmooth = (double)w[9];
-    const double co2Air = (double)x[b], tAir = (double)x[(size_t)2 * ld + b], vpAir = (double)x[(size_t)15 * ld + b];
-    const double hod = hour ? hour[b] : fmod((double)ts * hod_inc, 24.0);
-    const double doy = doy_in ? doy_in[b] : (double)start_day[b] + (double)ts * doy_inc;
-    // proportional band: lo + (hi-lo) / (1 + exp(-2/pBand * ln(100) * (v - setPt - pBand/2)))   (:226-227)
-    auto pband = [](double v, double sp, double band, double lo, double hi) {
-        return lo + (hi - lo) * (1.0 / (1.0 + exp(-2.0 / band * 4.605170185988092 * (v - sp - band * 0.5))));
-    };
-    const double tod = c.lamps_on <= c.lamps_off ? (double)(c.lamps_on < hod && hod < c.lamps_off)
-                                                 : (double)(c.lamps_on < hod || hod < c.lamps_off);              // :76-77
-    const double doy_ok = c.lamps_day_start <= c.lamps_day_stop
-                              ? (double)(c.lamps_day_start < doy && doy < c.lamps_day_stop)
-                              : (double)(c.lamps_day_start < doy || doy < c.lamps_day_stop);                   // :85-86
-    const double below_dli = (double)(dli < c.lamp_rad_sum_limit);
-    const double lamp_no_cons = (double)(iGlob < c.lamps_off_sun) * below_dli * tod * doy_ok;                   // :98
-    const double sw_on = fmax(0.0, fmin(1.0, hod - c.lamps_on + 1.0));                                          // :107
-    const double sw_off = fmax(0.0, fmin(1.0, c.lamps_off - hod + 1.0));                                        // :113
-    const double both = c.lamps_on == c.lamps_off ? 0.0
-                        : (c.lamps_on < c.lamps_off ? fmin(sw_on, sw_off) : fmax(sw_on, sw_off));               // :119-120
-    const double smooth_lamp = both * below_dli * doy_ok;                                                       // :128
-    const double day_inside = fmax(smooth_lamp, isDay);                                                         // :133
-    const double heat_sp = day_inside * c.temp_setpoint_day + (1.0 - day_inside) * c.temp_setpoint_night +
-                           c.heat_correction * lamp_no_cons;                                                    // :136
-    const double heat_max = heat_sp + c.heat_deadzone;
-    const double co2_sp = day_inside * c.co2_day;
-    const double co2_ppm = 1e6 * 8.3144598 * (tAir + 273.15) * (1e-6 * co2Air) / (101325.0 * 44.01e-3);         // :145
-    const double rh_in = 100.0 * vpAir / (610.78 * exp(17.2694 * tAir / (tAir + 238.3)));                       // :151
-    const double vent_heat = pband(tAir, heat_max, c.vent_heat_Pband, 0, 1);
-    const double vent_rh = pband(rh_in, c.rh_max + 0.0 * c.mech_dehumid_Pband, c.vent_rh_Pband, 0, 1);
-    const double vent_cold = pband(tAir, heat_sp - c.t_vent_off, c.vent_cold_Pband, 1, 0);
-    const double th_sp = isDay * c.thScrSpDay + (1.0 - isDay) * c.thScrSpNight;
-    const double th_cold = pband(tOut, th_sp, c.thScrPband, 0, 1);
-    const double th_heat = pband(tAir, heat_sp + c.thScrDeadZone, -c.thScrPband, 1, 0);
-    const double th_rh = fmax(pband(rh_in, c.rhMax + c.thScrRh, c.thScrRhPband, 1, 0), 1.0 - vent_cold);
-    const double lamp_on = lamp_no_cons * pband(tAir, heat_max + c.lampExtraHeat, -0.5, 0, 1) *
-                           (isDaySmooth + (1.0 - isDaySmooth)) *
-                           fmax(pband(rh_in, c.rhMax + c.blScrExtraRh, -0.5, 0, 1), 1.0 - vent_cold);           // :189-191
-    control[b] = (T)pband(tAir, heat_sp, c.tHeatBand, 0, 1);
-    control[(size_t)1 * ld + b] = (T)pband(co2_ppm, co2_sp, c.co2Band, 0, 1);
-    control[(size_t)2 * ld + b] = (T)fmin(th_cold, fmax(th_heat, th_rh));
-    control[(size_t)3 * ld + b] = (T)fmin(vent_cold, fmax(vent_heat, vent_rh));
-    control[(size_t)4 * ld + b] = (T)lamp_on;
-    control[(size_t)5 * ld + b] = (T)(c.useBlScr * (1.0 - isDaySmooth) * lamp_on);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// masked reset: init_state (utils.py:13-46)
-// ---------------------------------------------------------------------------------------------------
-template <class T>
-__global__ void reset_kernel(int B, int ld, const unsigned char* mask, T* x, T* u, int* timestep, const T* weather,
-                             int weather_rows, int* w_off, const int* start_rows, const float* start_days, int n_starts,
-                             float* start_day, int* episode, unsigned long long seed, int nd)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B || (mask && !mask[b])) return;
-    reset_env<T>(b, ld, x, u, timestep, weather, weather_rows, w_off, start_rows, start_days, n_starts, start_day, episode, seed, nd);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// crop-parameter noise (noise.py:3-23) with a counter-based generator: Philox4x32-10
-// ---------------------------------------------------------------------------------------------------
-template <class T>
-__global__ void crop_noise_kernel(T* crop_p, int B, int ld, const float* p0, float scale, unsigned long long seed,
-                                  unsigned long long draw)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    float pn[NCROP + 2];
-    for (int blk = 0; blk < 9; ++blk) {
-        unsigned r[4];
-        philox4x32_10((unsigned)b, (unsigned)draw, (unsigned)(draw >> 32), (unsigned)blk, (unsigned)seed,
-                      (unsigned)(seed >> 32), r);
-        for (int q = 0; q < 4; ++q) {
-            const int i = blk * 4 + q;
-            if (i < NCROP) {
-                const float un = ((float)(r[q] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1), 24 bits
-                const float noise = (un - 0.5f) * scale;
-                pn[i] = p0[i] + noise * p0[i];
-            }
-        }
-    }
-    pn[144 - CROP0] = pn[141 - CROP0] / pn[142 - CROP0];            // cLeafMax = laiMax / sla (noise.py:22)
-    for (int i = 0; i < NCROP; ++i) crop_p[(size_t)i * ld + b] = T(pn[i]);
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// VecNormalize on the device (HBM-bound: one read pass for the moments, one read + write pass to normalise)
-// ---------------------------------------------------------------------------------------------------
-// pass 1: per-feature sum and sum of squares over the batch.  Thread t owns columns t, t+256, ... (consecutive lanes ->
-// consecutive addresses of a row), walks a strip of rows in registers (fp64), then one atomic pair per column.  Eight row
-// loads are issued before the first is consumed: with two in flight the pass ran at 1.7 TB/s (41.6 us for 69 MB), the
-// latency-bandwidth product of the chip wants ~60 KB in flight per CU.  The atomics go to one of VN_REP replicas of the
-// accumulator block (merged by vecnorm_merge_kernel): 1 024 blocks x 526 fp64 atomics onto the 33 cache lines of a single
-// block serialise in the L2 -- that, not the read, was most of the pass.
-constexpr int VN_REP = 16;
-// The sums are taken about a pivot, the column's value in row 0: sum(x - p) and sum((x - p)^2).  The merge forms the batch
-// variance as E[d^2] - E[d]^2, which cancels (mean / spread)^2 of the fp64 mantissa when taken about zero: a column of mean
-// 35 040 and spread 3e-3 came out 4e-3 off at B = 65 536, and on warm statistics that reached the normalised rows
-// (profiles/vecnorm_moments_cost.txt).  About a value of the column itself the two terms are of the size of the spread; the
-// difference of two float32 is exact in fp64.
-__global__ __launch_bounds__(1024) void vecnorm_moments_kernel(const float* __restrict__ obs, int B, int dim,
-                                                               double* __restrict__ acc_all)
-{
-    double* acc = acc_all + (size_t)(blockIdx.x % VN_REP) * 2 * dim;
-    const int rows_per_block = (B + gridDim.x - 1) / gridDim.x;
-    const int r0 = blockIdx.x * rows_per_block, r1 = min(B, r0 + rows_per_block);
-    for (int c = threadIdx.x; c < dim; c += blockDim.x) {       // blockDim >= dim in practice: one column per thread
-        const double p = (double)obs[c];
-        double s0 = 0.0, q0 = 0.0, s1 = 0.0, q1 = 0.0;
-        int r = r0;
-        for (; r + 7 < r1; r += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = obs[(size_t)(r + j) * dim + c];
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                const double a = (double)v[j] - p, b = (double)v[j + 1] - p;
-                s0 += a; q0 += a * a; s1 += b; q1 += b * b;
-            }
-        }
-        for (; r < r1; ++r) { const double v = (double)obs[(size_t)r * dim + c] - p; s0 += v; q0 += v * v; }
-        if (r1 > r0) { atomicAdd(acc + c, s0 + s1); atomicAdd(acc + dim + c, q0 + q1); }
-    }
-}
-
-// discounted returns + their batch moments (wave reduction, one atomic pair per wave)
-template <class T>
-__global__ __launch_bounds__(256) void vecnorm_returns_kernel(const T* __restrict__ reward, double* __restrict__ returns,
-                                                              int B, double gamma, double* __restrict__ acc2)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    double v = 0.0;
-    if (b < B) { v = returns[b] * gamma + (double)reward[b]; returns[b] = v; }
-    double s = v, q = v * v;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, WAVE); q += __shfl_xor(q, o, WAVE); }
-    __shared__ double part[2][4];
-    const int wv = threadIdx.x / WAVE;
-    if ((threadIdx.x & (WAVE - 1)) == 0) { part[0][wv] = s; part[1][wv] = q; }
-    __syncthreads();
-    if (threadIdx.x == 0) {                                   // one atomic pair per 256-env block
-        atomicAdd(acc2, part[0][0] + part[0][1] + part[0][2] + part[0][3]);
-        atomicAdd(acc2 + 1, part[1][0] + part[1][1] + part[1][2] + part[1][3]);
-    }
-}
-
-// RunningMeanStd.update_from_moments for every feature (and for the scalar return statistics), then the batch count, then
-// per-column 1/sqrt(var + eps) (fp64, so that pass 2 is two fp64 ops per element) -- ONE block: the count every column
-// reads is updated after a barrier, and scale[c] may overwrite acc[c], which only column c's own thread has read.
-__global__ __launch_bounds__(1024) void vecnorm_merge_kernel(double* mean, double* var, double* count, const double* acc, int dim,
-                                                            int B, const float* __restrict__ obs, double* ret_stats,
-                                                            const double* acc2, int do_obs, int do_ret, double eps,
-                                                            double* scale)
-{
-    const double n = (double)B;
-    const double cnt = *count;
-    for (int c = threadIdx.x; c < dim; c += blockDim.x) {
-        if (do_obs) {
-            double sum = 0.0, sq = 0.0;
-            for (int r = 0; r < VN_REP; ++r) { sum += acc[(size_t)r * 2 * dim + c]; sq += acc[(size_t)r * 2 * dim + dim + c]; }
-            const double dm = sum / n, bv = fmax(sq / n - dm * dm, 0.0);      // moments about the pivot obs[0][c]
-            const double bm = (double)obs[c] + dm;
-            const double tot = cnt + n, delta = bm - mean[c];
-            const double m2 = var[c] * cnt + bv * n + delta * delta * cnt * n / tot;
-            mean[c] += delta * n / tot;
-            var[c] = m2 / tot;
-        }
-        if (scale) scale[c] = 1.0 / sqrt(var[c] + eps);
-    }
-    if (do_ret && threadIdx.x == 0) {
-        const double bm = acc2[0] / n, bv = fmax(acc2[1] / n - bm * bm, 0.0);
-        const double rc = ret_stats[2], tot = rc + n, delta = bm - ret_stats[0];
-        const double m2 = ret_stats[1] * rc + bv * n + delta * delta * rc * n / tot;
-        ret_stats[0] += delta * n / tot;
-        ret_stats[1] = m2 / tot;
-        ret_stats[2] = tot;
-    }
-    __syncthreads();
-    if (do_obs && threadIdx.x == 0) *count = cnt + n;
-}
-
-// pass 2: clip((x - mean) * scale).  The subtraction stays in fp64 like SB3 (float32 obs - float64 mean): for
-// near-constant features a ~1e-8 difference is divided by sqrt(eps).  Lane i handles element i (coalesced).
-__global__ __launch_bounds__(1024) void vecnorm_apply_kernel(const float* __restrict__ obs, float* __restrict__ out,
-                                                            int B, int dim, const double* __restrict__ mean,
-                                                            const double* __restrict__ scale, float clip)
-{
-    const int rows_per_block = (B + gridDim.x - 1) / gridDim.x;
-    const int r0 = blockIdx.x * rows_per_block, r1 = min(B, r0 + rows_per_block);
-    for (int c = threadIdx.x; c < dim; c += blockDim.x) {
-        const double mu = mean[c], sc = scale[c];
-        for (int r = r0; r < r1; ++r) {
-            const size_t i = (size_t)r * dim + c;
-            const float v = (float)(((double)obs[i] - mu) * sc);
-            out[i] = fminf(fmaxf(v, -clip), clip);
-        }
-    }
-}
-
-template <class T>
-__global__ void vecnorm_reward_kernel(const T* __restrict__ reward, float* __restrict__ out, double* __restrict__ returns,
-                                      const unsigned char* __restrict__ done, int B, const double* ret_stats, double eps,
-                                      float clip, int norm_reward)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    float r = (float)reward[b];
-    if (norm_reward) r = fminf(fmaxf((float)((double)reward[b] / sqrt(ret_stats[1] + eps)), -clip), clip);
-    out[b] = r;
-    if (done && done[b]) returns[b] = 0.0;
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// Weather pipeline on the device (gl_gym/environments/utils.py:48-125): raw 300-s samples -> unit
-// conversions -> daily light sum / daylight flags -> PCHIP resample to the env's grid.  fp64 throughout (it runs once per
-// season table, not per step); the result is written in the handle's dtype.  Mirrors gl_gym_amd/utils.py
-// (weather_from_raw), itself checked bit for bit against the reference's loader.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double w_sat_vp(double t) { return 610.78 * exp(17.2694 * t / (t + 238.3)); }
-
-// columns 0..6 of the raw-grid table W[10][n] (SoA)
-__global__ void weather_convert_kernel(int n, const double* __restrict__ time, const double* __restrict__ i_glob,
-                                       const double* __restrict__ t_out, const double* __restrict__ rh,
-                                       const double* __restrict__ wind, const double* __restrict__ t_sky, double co2_ppm,
-                                       double* __restrict__ W)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const double R = 8.3144598, C2K = 273.15, M_CO2 = 44.01e-3, M_H2O = 18.01528e-3, P_ATM = 101325.0;
-    const double t = t_out[k];
-    const double rho_v = (rh[k] / 100.0) * w_sat_vp(t) * M_H2O / (R * (t + C2K));              // rh2vaporDens
-    const double rho_sat = (100.0 / 100.0) * w_sat_vp(t) * M_H2O / (R * (t + C2K));
-    W[0 * (size_t)n + k] = i_glob[k];
-    W[1 * (size_t)n + k] = t;
-    W[2 * (size_t)n + k] = w_sat_vp(t) * (rho_v / rho_sat);                                    // vaporDens2pres
-    W[3 * (size_t)n + k] = (P_ATM * 1e-6 * co2_ppm * M_CO2 / (R * (t + C2K))) * 1e6;           // co2ppm2dens * 1e6
-    W[4 * (size_t)n + k] = wind[k];
-    W[5 * (size_t)n + k] = t_sky[k];
-    const double year = 3600.0 * 24.0 * 365.0;
-    W[6 * (size_t)n + k] = 10.0 + 5.0 * sin(2.0 * 3.14159265358979323846 * (time[k] + 0.625 * year) / year);   // soilTempNl
-}
-
-// columns 7..9: the two sequential passes of the loader (dailLightSum: utils.py:216-250; computeisDay: :177-214, whose
-// later tests see the ramps written by earlier ones).  One lane: O(n) work, n ~ 3e4.
-__global__ void weather_scan_kernel(int n, const double* __restrict__ time, double* __restrict__ W)
-{
-    if (blockIdx.x != 0 || threadIdx.x != 0 || n < 2) return;
-    const double* rad = W;
-    double* dli = W + 7 * (size_t)n;
-    double* is_day = W + 8 * (size_t)n;
-    double* smooth = W + 9 * (size_t)n;
-    const double c = 86400.0, interval = time[1] - time[0];
-    auto next_jump = [&](int from) {
-        for (int k = from < 0 ? 0 : from; k + 1 < n; ++k)
-            if (floor(time[k + 1] / c) - floor(time[k] / c) == 1.0) return k;
-        return -1;
-    };
-    int before = 0, j = next_jump(0), after = j >= 0 ? j + 1 : n, i = 0;
-    while (i < n) {
-        const int seg_end = after < n ? after : n;
-        double sum = 0.0;
-        for (int k = before; k <= after && k < n; ++k) sum += rad[k];
-        for (int k = i; k < seg_end; ++k) dli[k] = sum * interval * 1e-6;
-        i = seg_end;
-        if (i >= n) break;
-        before = after;
-        j = next_jump(before + 2);
-        after = j >= 0 ? j : n;
-    }
-    double dt_mean = (time[n - 1] - time[0]) / (double)(n - 1);
-    for (int k = 0; k < n; ++k) { is_day[k] = rad[k] > 0.0 ? 1.0 : 0.0; smooth[k] = is_day[k]; }
-    const int n_tr = (int)(3600.0 / dt_mean), half = n_tr / 2;
-    if (n_tr < 2) return;
-    const double step = 1.0 / (double)(n_tr - 1);
-    bool in_sunset = false;
-    for (int k = n_tr; k < n - n_tr; ++k) {
-        const double cur = is_day[k], nxt = is_day[k + 1];
-        if (cur == 0.0) {
-            in_sunset = false;
-            if (nxt == 1.0)
-                for (int q = 0; q < 2 * half && q < n_tr; ++q) {
-                    const double r = (q == n_tr - 1) ? 1.0 : (double)q * step;
-                    is_day[k - half + q] = r;
-                    smooth[k - half + q] = 1.0 / (1.0 + exp(-10.0 * (r - 0.5)));
-                }
-        } else if (cur == 1.0 && nxt == 0.0 && !in_sunset) {
-            for (int q = 0; q < 2 * half && q < n_tr; ++q) {
-                const double r = (q == n_tr - 1) ? 1.0 : (double)q * step;
-                is_day[k - half + q] = 1.0 - r;
-                smooth[k - half + q] = 1.0 - 1.0 / (1.0 + exp(-10.0 * (r - 0.5)));
-            }
-            in_sunset = true;
-        }
-    }
-}
-
-// PCHIP slopes (Fritsch-Carlson as scipy.interpolate.PchipInterpolator): D[c][k]
-__device__ __forceinline__ double w_sign(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
-__device__ __forceinline__ double pchip_edge(double h0, double h1, double m0, double m1)
-{
-    double d = ((2.0 * h0 + h1) * m0 - h0 * m1) / (h0 + h1);
-    if (w_sign(d) != w_sign(m0)) d = 0.0;
-    else if (w_sign(m0) != w_sign(m1) && fabs(d) > 3.0 * fabs(m0)) d = 3.0 * m0;
-    return d;
-}
-__global__ void pchip_slopes_kernel(int n, int n_col, const double* __restrict__ x, const double* __restrict__ W,
-                                    double* __restrict__ D)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
-    if (k >= n || col >= n_col) return;
-    const double* y = W + (size_t)col * n;
-    auto h = [&](int i) { return x[i + 1] - x[i]; };
-    auto m = [&](int i) { return (y[i + 1] - y[i]) / h(i); };
-    double d;
-    if (n == 2) d = m(0);
-    else if (k == 0) d = pchip_edge(h(0), h(1), m(0), m(1));
-    else if (k == n - 1) d = pchip_edge(h(n - 2), h(n - 3), m(n - 2), m(n - 3));
-    else {
-        const double m0 = m(k - 1), m1 = m(k), h0 = h(k - 1), h1 = h(k);
-        if (w_sign(m0) != w_sign(m1) || m0 == 0.0 || m1 == 0.0) d = 0.0;
-        else {
-            const double w1 = 2.0 * h1 + h0, w2 = h1 + 2.0 * h0;
-            d = 1.0 / ((w1 / m0 + w2 / m1) / (w1 + w2));
-        }
-    }
-    D[(size_t)col * n + k] = d;
-}
-
-// evaluation on linspace(x[0], x[n-1], n_out) in the power-series order of scipy's PPoly; iGlob < 1e-10 -> 0
-template <class T>
-__global__ void pchip_eval_kernel(int n, int n_col, int n_out, int nd, const double* __restrict__ x,
-                                  const double* __restrict__ W, const double* __restrict__ D, T* __restrict__ out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
-    if (i >= n_out || col >= n_col) return;
-    const double start = x[0], stop = x[n - 1];
-    const double stepo = n_out > 1 ? (stop - start) / (double)(n_out - 1) : 0.0;
-    double t = stop;
-    if (i < n_out - 1 || n_out == 1) {
-        // numpy's linspace rounds i * step before it adds start; fused into one FMA the point moves by an ulp of t (2e-9 s at
-        // day 100), which a zig-zag column with knots 300 s apart turns into 6e-12 of its range
-#pragma clang fp contract(off)
-        t = (double)i * stepo + start;
-    }
-    int lo = 0, hi = n - 1;                         // last k with x[k] <= t, clipped to n - 2
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (x[mid] <= t) lo = mid; else hi = mid; }
-    const int k = lo > n - 2 ? n - 2 : lo;
-    const double* y = W + (size_t)col * n;
-    const double* d = D + (size_t)col * n;
-    const double dx = x[k + 1] - x[k], slope = (y[k + 1] - y[k]) / dx;
-    const double tt = (d[k] + d[k + 1] - 2.0 * slope) / dx;
-    const double c0 = tt / dx, c1 = (slope - d[k]) / dx - tt, c2 = d[k], c3 = y[k];
-    const double sdx = t - x[k];
-    double res = 0.0, z = 1.0;
-    res += c3 * z; z *= sdx;
-    res += c2 * z; z *= sdx;
-    res += c1 * z; z *= sdx;
-    res += c0 * z;
-    if (col == 0 && res < 1e-10) res = 0.0;
-    out[(size_t)i * nd + col] = T(res);
-}
-
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------------
-// handle
-// ---------------------------------------------------------------------------------------------------
-struct glgym_handle_s {
-    int device = 0;
-    int dtype = GLGYM_F32;
-    int n_sub = 256;
-    double dt = 900.0;
-    double p[NP];
-    ModelConst<float> mf;
-    ModelConst<double> md;
-    glgym_reward_cfg rcfg;
-    RewardConst<float> rf;
-    RewardConst<double> rd;
-    double max_profit = 0, min_profit = 0, fixed_costs = 0;
-    float* p0_crop_dev = nullptr;       // shared p[128..161] as f32 (noise kernel input)
-    int* fail_dev = nullptr;            // glgym_evalF: number of rows whose integration failed
-    int nd = ND;                        // weather / disturbance row stride: 10, or up to 16 (ODE_pipe reads columns 10, 12)
-    int variant = GLGYM_ODE;            // GLGYM_ODE | GLGYM_ODE_PIPE
-    int scheme = GLGYM_SCHEME_RK4;      // GLGYM_SCHEME_RK4 | GLGYM_SCHEME_RK2 | GLGYM_SCHEME_RK3
-    int verify_mode = GLGYM_VERIFY_AUTO;   // glgym_set_verify
-    int use_specialised = 1;            // GLGYM_GENERIC=1 in the environment forces the generic kernels (A/B tests)
-    int window = 0;                     // glgym_set_window: 0 = the scheme's own
-    int layout = GLGYM_LAYOUT_AUTO;     // glgym_set_layout (fp32); initial value from GLGYM_LAYOUT at glgym_create
-    int occupancy = 0;                  // glgym_set_occupancy (one-lane fp32 kernel): 0 = by batch size; initial value from GLGYM_OCC at glgym_create
-    int ladder_parallel = 1;            // glgym_set_ladder_parallel: verified glgym_evalF calls may run two rungs of the ladder side by side
-    int n_simd = 1024;                  // SIMDs of the device (4 per CU)
-    float du = 0.1f, u_min[NU] = {0, 0, 0, 0, 0, 0}, u_max[NU] = {1, 1, 1, 1, 1, 1};   // glgym_set_control_limits
-    int obs_modules[6] = {0, 1, 2, 3, 4, 5};   // observation modules in output order (glgym_set_obs_modules)
-    int n_obs_modules = 6;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // glgym_evalF's integrator (glgym_set_integrator / glgym_set_tolerances) and the per-row statistics of its last BDF call
-    int integrator = GLGYM_INTEGRATOR_EXPLICIT;
-    int step_integrator = GLGYM_INTEGRATOR_EXPLICIT;     // glgym_step's (glgym_set_step_integrator); the tolerances are shared
-    double rtol = 1e-6, atol = 1e-6;
-    int max_steps = 10000;
-    int32_t* stats_dev = nullptr;
-    int stats_cap = 0;
-    std::vector<int32_t> stats;         // [stats_rows][GLGYM_NSOLVER_STAT]
-    int stats_rows = 0;
-    // scratch for the host-pointer entry points
-    double* scratch = nullptr;
-    size_t scratch_elems = 0;
-};
 
 static void default_reward(glgym_reward_cfg& c)
 {
@@ -1511,22 +873,6 @@ static int refresh(glgym_handle h)
     HIPCHK(hipMemcpy(h->p0_crop_dev, pc, sizeof pc, hipMemcpyHostToDevice));
     return GLGYM_OK;
 }
-
-// The device-pointer entry points launch on the CALLER's stream; HIP wants the calling thread's current device to be the stream's.
-// One process per GPU (the layout this library is built for) never notices; a process that holds handles on several devices does:
-// bind the handle's device for the duration of the call and put the caller's back (a no-op when it already is current).
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    // a null handle binds nothing (the entry point then returns GLGYM_EINVAL without having created a context on any device)
-    explicit DeviceGuard(const glgym_handle_s* h)
-    {
-        if (h && hipGetDevice(&prev) == hipSuccess && prev != h->device) switched = hipSetDevice(h->device) == hipSuccess;
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 extern "C" {
 
@@ -1780,6 +1126,11 @@ template <class F> static void with_scheme(int scheme, F&& f)
     else if (scheme == GLGYM_SCHEME_LS5) f(std::integral_constant<int, GLGYM_SCHEME_LS5>{});
     else f(std::integral_constant<int, GLGYM_SCHEME_RK4>{});
 }
+// the handle's constants in the precision of with_dtype's tag (glgym_internal.h)
+static const ModelConst<float>& model_const(glgym_handle h, float) { return h->mf; }
+static const ModelConst<double>& model_const(glgym_handle h, double) { return h->md; }
+static const RewardConstBase<float>& reward_const(glgym_handle h, float) { return h->rf; }
+static const RewardConstBase<double>& reward_const(glgym_handle h, double) { return h->rd; }
 
 template <class T, int SCH>
 static void launch_evalf_sch(glgym_handle h, const ModelConst<T>& m, const double* p_used, const double* dx, const double* du,
@@ -1902,14 +1253,13 @@ static int evalf_impl(glgym_handle h, const double* x, const double* u, const do
         h->stats.resize((size_t)B * GLGYM_NSOLVER_STAT);
         HIPCHK(hipMemcpy(h->stats.data(), h->stats_dev, h->stats.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         h->stats_rows = B;
-    } else if (h->dtype == GLGYM_F32) {
-        ModelConst<float> m = h->mf;
-        if (p) make_model_const<float>(p_used, m);
-        rc = run_evalf<float>(h, m, p_used, dx, du, dd, dcrop, B, dout, rhs_only);
     } else {
-        ModelConst<double> m = h->md;
-        if (p) make_model_const<double>(p_used, m);
-        rc = run_evalf<double>(h, m, p_used, dx, du, dd, dcrop, B, dout, rhs_only);
+        rc = with_dtype(h->dtype, [&](auto t) {
+            using T = decltype(t);
+            ModelConst<T> m = model_const(h, t);
+            if (p) make_model_const<T>(p_used, m);
+            return run_evalf<T>(h, m, p_used, dx, du, dd, dcrop, B, dout, rhs_only);
+        });
     }
     if (rc != GLGYM_OK) return rc;
     HIPCHK(hipMemcpy(out, dout, (size_t)B * NX * sizeof(double), hipMemcpyDeviceToHost));
@@ -1952,23 +1302,6 @@ int glgym_rhs(glgym_handle h, const double* x, const double* u, const double* d,
 }  // extern "C"
 
 // ---- device-pointer hot path ----------------------------------------------------------------------
-static const int OBS_MODULE_SIZE[6] = {4, 3, 6, 5, 5, 0};      // observations.py:64,84,102,123,143; forecast = 5 * Np (:168)
-// first column of each observation module in the handle's module order (-1 = absent) and the row width
-static void obs_layout(glgym_handle h, int Np, int moff[6], int* dim)
-{
-    for (int m = 0; m < 6; ++m) moff[m] = -1;
-    *dim = 0;
-    for (int i = 0; i < h->n_obs_modules; ++i) {
-        const int m = h->obs_modules[i];
-        moff[m] = *dim;
-        *dim += m == GLGYM_OBS_FORECAST ? 5 * Np : OBS_MODULE_SIZE[m];
-    }
-}
-static void obs_clock_increments(glgym_handle h, double* doy_inc, double* hod_inc)
-{
-    *doy_inc = std::fmod(h->dt / 86400.0, 365.0);
-    *hod_inc = h->dt / 3600.0;
-}
 // the observation block of a glgym_step_obs call names the step's own buffers, in full mode, with rows the epilogue's float4 stores can take
 static bool obs_same_buffers(const glgym_step_args* a, const glgym_obs_args* oa)
 {
@@ -1999,9 +1332,10 @@ template <int EPI> static typename StepObsSel<EPI>::type epilogue_args(const Ste
 // (No fp64 build with the default block compiled in: measured without the scheduler flag that used to break it -- csrc/Makefile --
 // it buys 0.7 % over the LDS-staged block, 1.379e6 against 1.369e6 env-steps/s at config 2, for six more 500-register kernels.)
 template <class T>
-static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelConst<T>& m, const RewardConst<T>& rw,
+static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelConst<T>& m, const RewardConstBase<T>& rw_base,
                        hipStream_t st, const glgym_obs_args* oa = nullptr, int* fused = nullptr, const glgym_reset_args* ra = nullptr)
 {
+    const RewardConst<T> rw{rw_base};       // the kernels' own argument type (their names carry it); the handle stores the base
     StepArgsT<T> k;
     k.B = a->B; k.ld = a->ld;
     k.x = (T*)a->x; k.u = (T*)a->u; k.action = a->action; k.control = (const T*)a->control;
@@ -2071,7 +1405,7 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
 
 // glgym_set_step_integrator(h, GLGYM_INTEGRATOR_BDF): one wavefront per environment in glgym_bdf.hip, fp64 integration for either dtype
 template <class T>
-static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const RewardConst<T>& rw, hipStream_t st)
+static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const RewardConstBase<T>& rw, hipStream_t st)
 {
     if (h->variant == GLGYM_ODE_PIPE) {
         g_err = "glgym_step: GLGYM_INTEGRATOR_BDF does not support GLGYM_ODE_PIPE";
@@ -2107,8 +1441,7 @@ static int step_impl(glgym_handle h, const glgym_step_args* a, void* stream, con
     }
     if (h->step_integrator == GLGYM_INTEGRATOR_BDF) {
         DeviceGuard dev_guard(h);
-        return h->dtype == GLGYM_F32 ? launch_step_bdf<float>(h, a, h->rf, (hipStream_t)stream)
-                                     : launch_step_bdf<double>(h, a, h->rd, (hipStream_t)stream);
+        return with_dtype(h->dtype, [&](auto t) { return launch_step_bdf<decltype(t)>(h, a, reward_const(h, t), (hipStream_t)stream); });
     }
     if (h->integrator != GLGYM_INTEGRATOR_EXPLICIT) {
         g_err = "glgym_step: GLGYM_INTEGRATOR_BDF is available to glgym_evalF only; set GLGYM_INTEGRATOR_EXPLICIT for env-steps";
@@ -2125,129 +1458,7 @@ extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream
     return step_impl(h, a, stream, nullptr, nullptr);
 }
 
-template <class T> static int launch_obs(glgym_handle h, const glgym_obs_args* a, hipStream_t st)
-{
-    ObsArgsT<T> k;
-    k.B = a->B; k.ld = a->ld; k.x = (const T*)a->x; k.u = (const T*)a->u; k.weather = (const T*)a->weather;
-    k.weather_rows = a->weather_rows; k.w_off = a->w_off; k.timestep = a->timestep; k.start_day = a->start_day;
-    k.Np = a->Np; k.obs = a->obs; k.mask = a->mask; k.term_obs = a->term_obs; k.nd = h->nd;
-    obs_clock_increments(h, &k.doy_inc, &k.hod_inc);
-    int blocks = (a->B + OBS_ROWS - 1) / OBS_ROWS;   // OBS_ROWS env rows per block-iteration
-    static const int cap = [] { const char* e = std::getenv("GLGYM_OBS_BLOCKS"); return e ? std::atoi(e) : 4096; }();
-    if (blocks > cap) blocks = cap;              // grid-stride beyond that
-    obs_layout(h, a->Np, k.moff, &k.dim);
-    const size_t lds = (size_t)OBS_ROWS * k.dim * sizeof(float);
-    hipLaunchKernelGGL((obs_kernel<T>), dim3(blocks), dim3(256), lds, st, k);
-    HIPCHK(hipGetLastError());
-    return GLGYM_OK;
-}
-
-
-
-extern "C" int glgym_weather(glgym_handle h, const glgym_weather_args* a, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !a || a->n_raw < 3 || a->n_out < 1 || a->nd < ND || !a->time || !a->i_glob || !a->t_out || !a->rh || !a->wind ||
-        !a->t_sky || !a->out || !a->workspace) {
-        g_err = "glgym_weather: bad arguments (>= 3 raw samples, nd >= 10, non-null device pointers)";
-        return GLGYM_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int n = a->n_raw;
-    double* W = a->workspace;                       // [10][n] converted columns on the raw grid
-    double* D = a->workspace + (size_t)10 * n;      // [10][n] PCHIP slopes
-    hipLaunchKernelGGL(weather_convert_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, a->time, a->i_glob, a->t_out,
-                       a->rh, a->wind, a->t_sky, a->co2_ppm, W);
-    hipLaunchKernelGGL(weather_scan_kernel, dim3(1), dim3(64), 0, st, n, a->time, W);
-    hipLaunchKernelGGL(pchip_slopes_kernel, dim3((n + 255) / 256, 10), dim3(256), 0, st, n, 10, a->time, W, D);
-    if (a->nd > ND) {                               // extra columns (ODE_pipe rows) are the caller's: start from zero
-        HIPCHK(hipMemsetAsync(a->out, 0, (size_t)a->n_out * a->nd * (h->dtype == GLGYM_F32 ? 4 : 8), st));
-    }
-    const dim3 grid((a->n_out + 255) / 256, 10);
-    if (h->dtype == GLGYM_F32)
-        hipLaunchKernelGGL((pchip_eval_kernel<float>), grid, dim3(256), 0, st, n, 10, a->n_out, a->nd, a->time, W, D,
-                           (float*)a->out);
-    else
-        hipLaunchKernelGGL((pchip_eval_kernel<double>), grid, dim3(256), 0, st, n, 10, a->n_out, a->nd, a->time, W, D,
-                           (double*)a->out);
-    HIPCHK(hipGetLastError());
-    return GLGYM_OK;
-}
-
-extern "C" int glgym_vecnorm(glgym_handle h, const glgym_vecnorm_args* a, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !a || a->B < 1 || a->dim < 1 || !a->obs || !a->obs_out || !a->obs_mean || !a->obs_var || !a->obs_count ||
-        !a->workspace || (a->reward && (!a->reward_out || !a->ret_stats || !a->returns))) {
-        g_err = "glgym_vecnorm: bad arguments";
-        return GLGYM_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int B = a->B, dim = a->dim;
-    double* acc = a->workspace;
-    double* acc2 = a->workspace + (size_t)VN_REP * 2 * dim;
-    HIPCHK(hipMemsetAsync(a->workspace, 0, ((size_t)VN_REP * 2 * dim + 2) * sizeof(double), st));
-    const int do_obs = a->training && a->norm_obs, do_ret = a->training && a->reward != nullptr;
-    int col_threads = (dim + WAVE - 1) / WAVE * WAVE;       // one thread per observation column
-    if (col_threads > 1024) col_threads = 1024;
-    if (do_obs) {
-        int blocks = (B + 63) / 64;                 // 64-row strips: <= 1024 blocks x 2*dim fp64 atomics
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(vecnorm_moments_kernel, dim3(blocks), dim3(col_threads), 0, st, a->obs, B, dim, acc);
-    }
-    if (do_ret) {
-        if (h->dtype == GLGYM_F32)
-            hipLaunchKernelGGL((vecnorm_returns_kernel<float>), dim3((B + 255) / 256), dim3(256), 0, st,
-                               (const float*)a->reward, a->returns, B, a->gamma, acc2);
-        else
-            hipLaunchKernelGGL((vecnorm_returns_kernel<double>), dim3((B + 255) / 256), dim3(256), 0, st,
-                               (const double*)a->reward, a->returns, B, a->gamma, acc2);
-    }
-    double* scale = acc;                           // the moment accumulators are dead once their column is merged
-    if (do_obs || do_ret || a->norm_obs)
-        hipLaunchKernelGGL(vecnorm_merge_kernel, dim3(1), dim3(1024), 0, st, a->obs_mean, a->obs_var, a->obs_count, acc, dim, B,
-                           a->obs, a->ret_stats, acc2, do_obs, do_ret, a->epsilon, a->norm_obs ? scale : nullptr);
-    const size_t total = (size_t)B * dim;
-    if (a->norm_obs) {
-        int blocks = (B + 15) / 16;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(vecnorm_apply_kernel, dim3(blocks), dim3(col_threads), 0, st, a->obs, a->obs_out, B, dim,
-                           a->obs_mean, scale, a->clip_obs);
-    } else if (a->obs_out != a->obs) {
-        HIPCHK(hipMemcpyAsync(a->obs_out, a->obs, total * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    if (a->reward) {
-        if (h->dtype == GLGYM_F32)
-            hipLaunchKernelGGL((vecnorm_reward_kernel<float>), dim3((B + 255) / 256), dim3(256), 0, st,
-                               (const float*)a->reward, a->reward_out, a->returns, a->done, B, a->ret_stats, a->epsilon,
-                               a->clip_reward, a->norm_reward);
-        else
-            hipLaunchKernelGGL((vecnorm_reward_kernel<double>), dim3((B + 255) / 256), dim3(256), 0, st,
-                               (const double*)a->reward, a->reward_out, a->returns, a->done, B, a->ret_stats, a->epsilon,
-                               a->clip_reward, a->norm_reward);
-    }
-    HIPCHK(hipGetLastError());
-    return GLGYM_OK;
-}
-
 extern "C" {
-
-static bool obs_args_ok(glgym_handle h, const glgym_obs_args* a)
-{
-    return h && a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->weather && a->weather_rows >= 1 && a->w_off && a->timestep &&
-           a->start_day && a->obs && a->Np >= 0 && a->Np <= OBS_MAX_NP;      // weather_rows < 1: the row clamp would yield row -1
-}
-
-int glgym_obs(glgym_handle h, const glgym_obs_args* a, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!obs_args_ok(h, a)) {
-        g_err = "glgym_obs: bad arguments (null pointer, ld < B, weather_rows < 1, or Np outside 0..128)";
-        return GLGYM_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    return h->dtype == GLGYM_F32 ? launch_obs<float>(h, a, st) : launch_obs<double>(h, a, st);
-}
 
 int glgym_step_obs(glgym_handle h, const glgym_step_args* a, const glgym_obs_args* oa, void* stream)
 {
@@ -2261,57 +1472,6 @@ int glgym_step_obs(glgym_handle h, const glgym_step_args* a, const glgym_obs_arg
     const int rc = step_impl(h, a, stream, oa, &fused);
     if (rc != GLGYM_OK || fused) return rc;
     return glgym_obs(h, oa, stream);
-}
-
-int glgym_set_obs_modules(glgym_handle h, const int32_t* modules, int n)
-{
-    if (!h || !modules || n < 1 || n > 6) { g_err = "glgym_set_obs_modules: 1..6 module ids expected"; return GLGYM_EINVAL; }
-    int seen = 0;
-    for (int i = 0; i < n; ++i) {
-        if (modules[i] < 0 || modules[i] > 5 || (seen >> modules[i] & 1)) {
-            g_err = "glgym_set_obs_modules: ids must be distinct GLGYM_OBS_* values";
-            return GLGYM_EINVAL;
-        }
-        seen |= 1 << modules[i];
-    }
-    for (int i = 0; i < n; ++i) h->obs_modules[i] = modules[i];
-    h->n_obs_modules = n;
-    return GLGYM_OK;
-}
-
-int glgym_obs_dim(glgym_handle h, int Np)
-{
-    if (!h || Np < 0 || Np > OBS_MAX_NP) return GLGYM_EINVAL;
-    int moff[6], dim;
-    obs_layout(h, Np, moff, &dim);
-    return dim;
-}
-
-static bool reset_args_ok(const glgym_reset_args* a)
-{
-    return a && a->B >= 1 && a->ld >= a->B && a->x && a->u && a->timestep && a->weather && a->weather_rows >= 1 && a->w_off;
-}
-
-int glgym_reset(glgym_handle h, const glgym_reset_args* a, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !reset_args_ok(a)) {
-        g_err = "glgym_reset: bad arguments (null handle or pointer, B < 1, ld < B, or weather_rows < 1)";
-        return GLGYM_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((a->B + 255) / 256), block(256);
-    if (h->dtype == GLGYM_F32)
-        hipLaunchKernelGGL((reset_kernel<float>), grid, block, 0, st, a->B, a->ld, a->mask, (float*)a->x, (float*)a->u,
-                           a->timestep, (const float*)a->weather, a->weather_rows, a->w_off, a->start_rows, a->start_days,
-                           a->n_starts, a->start_day, a->episode, (unsigned long long)a->seed, h->nd);
-    else
-        hipLaunchKernelGGL((reset_kernel<double>), grid, block, 0, st, a->B, a->ld, a->mask, (double*)a->x,
-                           (double*)a->u, a->timestep, (const double*)a->weather, a->weather_rows, a->w_off,
-                           a->start_rows, a->start_days, a->n_starts, a->start_day, a->episode,
-                           (unsigned long long)a->seed, h->nd);
-    HIPCHK(hipGetLastError());
-    return GLGYM_OK;
 }
 
 int glgym_step_obs_reset(glgym_handle h, const glgym_step_args* a, const glgym_obs_args* oa, const glgym_reset_args* ra, void* stream,
@@ -2340,333 +1500,6 @@ int glgym_step_obs_reset(glgym_handle h, const glgym_step_args* a, const glgym_o
     if (!fused && (rc = glgym_obs(h, &full, stream)) != GLGYM_OK) return rc;
     if ((rc = glgym_reset(h, &rst, stream)) != GLGYM_OK) return rc;
     return glgym_obs(h, &masked, stream);
-}
-
-int glgym_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t seed, uint64_t draw_index,
-                     void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !crop_p || B < 1 || ld < B) return GLGYM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((B + 255) / 256), block(256);
-    if (h->dtype == GLGYM_F32)
-        hipLaunchKernelGGL((crop_noise_kernel<float>), grid, block, 0, st, (float*)crop_p, B, ld, h->p0_crop_dev,
-                           (float)scale, (unsigned long long)seed, (unsigned long long)draw_index);
-    else
-        hipLaunchKernelGGL((crop_noise_kernel<double>), grid, block, 0, st, (double*)crop_p, B, ld, h->p0_crop_dev,
-                           (float)scale, (unsigned long long)seed, (unsigned long long)draw_index);
-    HIPCHK(hipGetLastError());
-    return GLGYM_OK;
-}
-
-int glgym_rng_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t* rng_state, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !rng_state || B < 1 || ld < B || !(scale >= 0.0)) {
-        g_err = "glgym_rng_crop_noise: bad arguments (null handle or stream buffer, ld < B, or a negative scale)";
-        return GLGYM_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (h->dtype == GLGYM_F32) HIPCHK(rng_crop_noise_launch<float>((float*)crop_p, B, ld, h->p0_crop_dev, scale, rng_state, st));
-    else HIPCHK(rng_crop_noise_launch<double>((double*)crop_p, B, ld, h->p0_crop_dev, scale, rng_state, st));
-    return GLGYM_OK;
-}
-
-int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
-                         const int32_t* start_rows, const float* start_days, int32_t* w_off, float* start_day, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !rng_state || B < 1 || ld < B || n_years < 1 || n_days < 1 || !start_rows || !w_off) {
-        g_err = "glgym_rng_reset_draw: bad arguments (null pointer, ld < B, or an empty start grid)";
-        return GLGYM_EINVAL;
-    }
-    HIPCHK(rng_reset_draw_launch(B, ld, mask, rng_state, n_years, n_days, start_rows, start_days, w_off, start_day, (hipStream_t)stream));
-    return GLGYM_OK;
-}
-
-// ---- device-side planning (glgym_plan.hip): host side only -- argument checks, and glgym_plan_rollout's loop over glgym_step ----
-static bool plan_size_ok(const char* who, int32_t got, size_t want)
-{
-    if (got == (int32_t)want) return true;
-    g_err = std::string(who) + ": struct_size is " + std::to_string(got) + ", this library expects " + std::to_string(want) +
-            " (ABI " + std::to_string(GLGYM_ABI_VERSION) + "): rebuild against include/glgym.h";
-    return false;
-}
-
-int glgym_plan_fork(glgym_handle h, const glgym_plan_fork_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_fork: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_fork", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->n_children < 1 || a->n_parents < 1 || a->ld_parent < a->n_parents || a->ld_child < a->n_children ||
-        (!a->parent && (a->K < 1 || (int64_t)a->n_parents * a->K < a->n_children)) ||
-        !a->x_parent || !a->u_parent || !a->timestep_parent || !a->w_off_parent || !a->x || !a->u || !a->timestep || !a->w_off ||
-        !a->ret || !a->viol || !a->n_steps || !a->alive || !a->failed) {
-        g_err = "glgym_plan_fork: bad arguments (null pointer, ld < batch, or without a parent table K < 1 or fewer than C = P * K slots)";
-        return GLGYM_EINVAL;
-    }
-    DeviceGuard dev_guard(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (h->dtype == GLGYM_F32) HIPCHK(plan_fork_launch<float>(*a, st));
-    else HIPCHK(plan_fork_launch<double>(*a, st));
-    return GLGYM_OK;
-}
-
-int glgym_plan_accumulate(glgym_handle h, const glgym_plan_accumulate_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_accumulate: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_accumulate", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->B < 1 || a->ld < a->B || !a->reward || !a->info || !a->done || !a->ret || !a->viol || !a->n_steps || !a->alive || !a->failed) {
-        g_err = "glgym_plan_accumulate: bad arguments (null pointer or ld < B)";
-        return GLGYM_EINVAL;
-    }
-    DeviceGuard dev_guard(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (h->dtype == GLGYM_F32) HIPCHK(plan_accumulate_launch<float>(*a, st));
-    else HIPCHK(plan_accumulate_launch<double>(*a, st));
-    return GLGYM_OK;
-}
-
-int glgym_plan_rollout(glgym_handle h, const glgym_plan_rollout_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_rollout: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_rollout", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->H < 1 || !(a->gamma >= 0.0) || !std::isfinite(a->gamma) || (!a->actions) == (!a->controls) || a->step.B < 1 ||
-        a->step.ld < a->step.B || !a->step.reward || !a->step.info || !a->step.done || !a->ret || !a->viol || !a->n_steps ||
-        !a->alive || !a->failed) {
-        g_err = "glgym_plan_rollout: bad arguments (H < 1, gamma, exactly one of actions / controls, ld >= B, non-null reward / info / done / accumulators)";
-        return GLGYM_EINVAL;
-    }
-    glgym_step_args s = a->step;                 // glgym_step checks its struct_size and the remaining members
-    s.metrics = nullptr;
-    glgym_plan_accumulate_args acc;
-    acc.struct_size = (int32_t)sizeof acc;
-    acc.B = s.B; acc.ld = s.ld; acc.reward = s.reward; acc.info = s.info; acc.done = s.done; acc.step_flags = s.step_flags;
-    acc.ret = a->ret; acc.viol = a->viol; acc.n_steps = a->n_steps; acc.alive = a->alive; acc.failed = a->failed;
-    const size_t plane = (size_t)NU * (size_t)s.ld * (h->dtype == GLGYM_F32 ? sizeof(float) : sizeof(double));
-    double w = 1.0;
-    for (int k = 0; k < a->H; ++k) {
-        s.action = a->actions ? a->actions + (size_t)k * (size_t)s.B * NU : nullptr;
-        s.control = a->controls ? (const void*)((const char*)a->controls + (size_t)k * plane) : nullptr;
-        const int rc = glgym_step(h, &s, stream);
-        if (rc != GLGYM_OK) return rc;
-        acc.w = w;
-        const int ra = glgym_plan_accumulate(h, &acc, stream);
-        if (ra != GLGYM_OK) return ra;
-        w = w * a->gamma;
-    }
-    return GLGYM_OK;
-}
-
-int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_select: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_select", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    const bool wants_actions = a->best_action || a->best_sequence || a->mean_sequence;
-    if (a->P < 1 || a->K < 1 || a->H < 1 || a->H > 65535 || (int64_t)a->P * a->K > INT32_MAX || !a->ret || !a->failed || !a->best_k ||
-        !a->best_ret || (wants_actions && !a->actions) || (a->mean_sequence && !(a->temperature > 0.0 && std::isfinite(a->temperature)))) {
-        g_err = "glgym_plan_select: bad arguments (P, K, H < 1, H > 65 535, null pointer, action outputs without actions, or mean_sequence "
-                "without a finite temperature > 0)";
-        return GLGYM_EINVAL;
-    }
-    // the kernel multiplies by 1 / temperature: at 2^-1024 and below that is +inf and the best candidate's own (ret - max) * inf = 0 * inf a NaN
-    if (a->mean_sequence && !std::isfinite(1.0 / a->temperature)) {
-        g_err = "glgym_plan_select: temperature is too small (1 / temperature is not finite: it must be above 2^-1024, about 5.6e-309)";
-        return GLGYM_EINVAL;
-    }
-    DeviceGuard dev_guard(h);
-    HIPCHK(plan_select_launch(*a, (hipStream_t)stream));
-    return GLGYM_OK;
-}
-
-// the cross-entropy method's stages (gl_cem.hpp): every check that needs no device memory happens here, before anything is launched
-int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_sample: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_sample", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->P < 1 || a->K < 1 || a->H < 1 || (int64_t)a->P * a->K > INT32_MAX - 255 || !a->mean || !a->std || !a->actions ||
-        !(a->beta >= 0.0 && a->beta < 1.0) || a->carry < 0 ||
-        (a->carry > 0 && (!a->prev_actions || !a->prev_elite_k || !a->prev_n_elite || a->prev_E < a->carry || a->prev_actions == a->actions))) {
-        g_err = "glgym_plan_sample: bad arguments (P, K, H < 1, null pointer, beta outside [0, 1), carry < 0, or with carry > 0: a missing "
-                "prev_ member, carry > prev_E, or prev_actions == actions -- sample into the other of two blocks)";
-        return GLGYM_EINVAL;
-    }
-    DeviceGuard dev_guard(h);
-    HIPCHK(plan_sample_launch(*a, (hipStream_t)stream));
-    return GLGYM_OK;
-}
-
-int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_elites: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_elites", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->P < 1 || a->K < 1 || a->E < 1 || a->E > a->K || (int64_t)a->P * a->K > INT32_MAX - 255 || !a->ret || !a->failed || !a->elite_k ||
-        !a->n_elite) {
-        g_err = "glgym_plan_elites: bad arguments (P, K < 1, E outside 1..K, or null pointer)";
-        return GLGYM_EINVAL;
-    }
-    DeviceGuard dev_guard(h);
-    HIPCHK(plan_elites_launch(*a, (hipStream_t)stream));
-    return GLGYM_OK;
-}
-
-int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream)
-{
-    if (!h || !a) { g_err = "glgym_plan_refit: null handle / arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_refit", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->P < 1 || a->K < 1 || a->H < 1 || a->H > 65535 || a->E < 1 || a->E > a->K || (int64_t)a->P * a->K > INT32_MAX - 255 ||
-        !a->actions || !a->elite_k || !a->n_elite || !a->mean || !a->std || !a->mean_out || !a->std_out ||
-        !(a->alpha >= 0.0 && a->alpha < 1.0) || !(a->min_std >= 0.0 && std::isfinite(a->min_std))) {
-        g_err = "glgym_plan_refit: bad arguments (P, K, H < 1, H > 65 535, E outside 1..K, null pointer, alpha outside [0, 1), or min_std "
-                "negative or not finite)";
-        return GLGYM_EINVAL;
-    }
-    DeviceGuard dev_guard(h);
-    HIPCHK(plan_refit_launch(*a, (hipStream_t)stream));
-    return GLGYM_OK;
-}
-
-// robust planning (gl_scen.hpp).  The arguments are checked before the handle is looked at, so that a caller without a device gets the
-// refusal that names its mistake.
-static bool scenario_shape_ok(int32_t P, int32_t K, int32_t S, int32_t hold, double scale)
-{
-    return P >= 1 && K >= 1 && S >= 1 && S <= 256 && (int64_t)P * K * S <= INT32_MAX && (hold == 0 || hold == 1) && scale >= 0.0 &&
-           std::isfinite(scale);
-}
-
-int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void* stream)
-{
-    if (!a) { g_err = "glgym_plan_scenario: null arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_scenario", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || (int64_t)a->ld < (int64_t)a->P * a->K * a->S || a->h_step < 0 ||
-        a->h_step > 65535 || !a->crop || (!a->actions_in) != (!a->actions_out)) {
-        g_err = "glgym_plan_scenario: bad arguments (P, K, S < 1, S > 256, P*K*S > INT32_MAX, ld < P*K*S, h_step outside 0 .. 65 535, hold "
-                "not 0 | 1, scale negative or not finite, null crop, or one of actions_in / actions_out without the other)";
-        return GLGYM_EINVAL;
-    }
-    if (!h) { g_err = "glgym_plan_scenario: null handle"; return GLGYM_EINVAL; }
-    DeviceGuard dev_guard(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (h->dtype == GLGYM_F32) HIPCHK(plan_scenario_launch<float>(*a, h->p0_crop_dev, st));
-    else HIPCHK(plan_scenario_launch<double>(*a, h->p0_crop_dev, st));
-    return GLGYM_OK;
-}
-
-int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream)
-{
-    if (!a) { g_err = "glgym_plan_aggregate: null arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_aggregate", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    if (a->J < 1 || a->S < 1 || a->S > 256 || a->m < 1 || a->m > a->S || (int64_t)a->J * a->S > INT32_MAX || !a->ret || !a->failed ||
-        !a->ret_cand || !a->failed_cand || (a->viol_cand && (!a->viol || (int64_t)a->ld < (int64_t)a->J * a->S || a->ld_cand < a->J)) ||
-        (a->steps_cand && !a->n_steps)) {
-        g_err = "glgym_plan_aggregate: bad arguments (J, S < 1, S > 256, m outside 1 .. S, J*S > INT32_MAX, null pointer, or with viol_cand: "
-                "ld < J*S or ld_cand < J)";
-        return GLGYM_EINVAL;
-    }
-    if (!h) { g_err = "glgym_plan_aggregate: null handle"; return GLGYM_EINVAL; }
-    DeviceGuard dev_guard(h);
-    HIPCHK(plan_aggregate_launch(*a, (hipStream_t)stream));
-    return GLGYM_OK;
-}
-
-int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream)
-{
-    if (!a) { g_err = "glgym_plan_rollout_scenarios: null arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_rollout_scenarios", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    const glgym_plan_rollout_args& r = a->rollout;
-    if (!plan_size_ok("glgym_plan_rollout_scenarios: rollout", r.struct_size, sizeof r)) return GLGYM_EINVAL;
-    if (r.controls) {
-        g_err = "glgym_plan_rollout_scenarios: raw-control scenario rollouts are not supported (rollout.controls must be NULL)";
-        return GLGYM_EINVAL;
-    }
-    glgym_step_args s = r.step;
-    if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || !a->staging || r.H < 1 || r.H > 65536 || !(r.gamma >= 0.0) ||
-        !std::isfinite(r.gamma) || !r.actions || (int64_t)s.B != (int64_t)a->P * a->K * a->S || s.ld < s.B || !s.crop_p || !s.reward ||
-        !s.info || !s.done || !r.ret || !r.viol || !r.n_steps || !r.alive || !r.failed) {
-        g_err = "glgym_plan_rollout_scenarios: bad arguments (P, K, S < 1, S > 256, hold not 0 | 1, scale negative or not finite, null "
-                "staging / actions / crop_p / reward / info / done / accumulators, H outside 1 .. 65 536, gamma, step.B != P*K*S, or ld < B)";
-        return GLGYM_EINVAL;
-    }
-    if (!h) { g_err = "glgym_plan_rollout_scenarios: null handle"; return GLGYM_EINVAL; }
-    s.metrics = nullptr;
-    s.action = a->staging;
-    s.control = nullptr;
-    // what glgym_step refuses without launching is refused by it, in its own words, before the first prologue is launched: a struct
-    // or pointer it checks itself, GLGYM_ODE_PIPE with a crop block (either step integrator), a BDF glgym_evalF setting on explicit steps
-    if (s.struct_size != (int32_t)sizeof s || !s.x || !s.u || !s.weather || !s.w_off || !s.timestep || s.weather_rows < 1 ||
-        h->variant == GLGYM_ODE_PIPE || (h->step_integrator != GLGYM_INTEGRATOR_BDF && h->integrator != GLGYM_INTEGRATOR_EXPLICIT)) {
-        const int rc = glgym_step(h, &s, stream);
-        if (rc != GLGYM_OK) return rc;
-        g_err = "glgym_plan_rollout_scenarios: glgym_step accepted a call it was expected to refuse";        // unreachable
-        return GLGYM_EINVAL;
-    }
-    glgym_plan_scenario_args sc;
-    sc.struct_size = (int32_t)sizeof sc;
-    sc.P = a->P; sc.K = a->K; sc.S = a->S; sc.ld = s.ld; sc.hold = a->hold; sc.scale = a->scale; sc.seed = a->seed;
-    sc.draw_index = a->draw_index; sc.draw_base = a->draw_base; sc.crop = (void*)s.crop_p; sc.actions_out = a->staging;
-    glgym_plan_accumulate_args acc;
-    acc.struct_size = (int32_t)sizeof acc;
-    acc.B = s.B; acc.ld = s.ld; acc.reward = s.reward; acc.info = s.info; acc.done = s.done; acc.step_flags = s.step_flags;
-    acc.ret = r.ret; acc.viol = r.viol; acc.n_steps = r.n_steps; acc.alive = r.alive; acc.failed = r.failed;
-    const size_t plane = (size_t)a->P * (size_t)a->K * NU;             // the candidates' action plane of one step
-    double w = 1.0;
-    for (int k = 0; k < r.H; ++k) {
-        sc.h_step = k;
-        sc.actions_in = r.actions + (size_t)k * plane;
-        int rc = glgym_plan_scenario(h, &sc, stream);
-        if (rc != GLGYM_OK) return rc;
-        if ((rc = glgym_step(h, &s, stream)) != GLGYM_OK) return rc;
-        acc.w = w;
-        if ((rc = glgym_plan_accumulate(h, &acc, stream)) != GLGYM_OK) return rc;
-        w = w * r.gamma;
-    }
-    return GLGYM_OK;
-}
-
-// weather-forecast scenarios (gl_wscen.hpp): checked before the handle is looked at, like the entry points above
-int glgym_plan_weather(glgym_handle h, const glgym_plan_weather_args* a, void* stream)
-{
-    if (!a) { g_err = "glgym_plan_weather: null arguments"; return GLGYM_EINVAL; }
-    if (!plan_size_ok("glgym_plan_weather", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
-    bool sigma_ok = true;
-    for (int j = 0; j < 7; ++j) sigma_ok = sigma_ok && a->sigma[j] >= 0.0 && std::isfinite(a->sigma[j]);
-    if (a->P < 1 || a->K < 1 || a->S < 1 || a->S > 256 || a->H < 1 || a->H > 65536 || (int64_t)a->P * a->S * a->H > INT32_MAX ||
-        (int64_t)a->P * a->K * a->S > INT32_MAX || a->weather_rows < 1 || !sigma_ok || !(a->phi >= 0.0 && a->phi < 1.0) || !a->weather ||
-        !a->w_off_parent || !a->timestep_parent || !a->window) {
-        g_err = "glgym_plan_weather: bad arguments (P, K, S, H < 1, S > 256, H > 65 536, P*S*H or P*K*S > INT32_MAX, weather_rows < 1, a sigma "
-                "negative or not finite, phi outside [0, 1), or a null weather / w_off_parent / timestep_parent / window)";
-        return GLGYM_EINVAL;
-    }
-    if (!h) { g_err = "glgym_plan_weather: null handle"; return GLGYM_EINVAL; }
-    DeviceGuard dev_guard(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (h->dtype == GLGYM_F32) HIPCHK(plan_weather_launch<float>(*a, h->nd, st));
-    else HIPCHK(plan_weather_launch<double>(*a, h->nd, st));
-    return GLGYM_OK;
-}
-
-int glgym_rule_based(glgym_handle h, const glgym_rule_cfg* cfg, const glgym_rule_args* a, void* stream)
-{
-    DeviceGuard dev_guard(h);
-    if (!h || !cfg || !a || a->B < 1 || a->ld < a->B || !a->x || !a->weather || !a->w_off || !a->timestep || !a->control ||
-        a->weather_rows < 1 || (!a->start_day && !a->doy) || cfg->vent_heat_Pband == 0 || cfg->vent_rh_Pband == 0 ||
-        cfg->vent_cold_Pband == 0 || cfg->thScrPband == 0 || cfg->thScrRhPband == 0 || cfg->tHeatBand == 0 ||
-        cfg->co2Band == 0) {
-        g_err = "glgym_rule_based: bad arguments (null pointer, ld < B, or a zero proportional band)";
-        return GLGYM_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((a->B + 255) / 256), block(256);
-    const double doy_inc = std::fmod(h->dt / 86400.0, 365.0), hod_inc = h->dt / 3600.0;
-    if (h->dtype == GLGYM_F32)
-        hipLaunchKernelGGL((rule_based_kernel<float>), grid, block, 0, st, *cfg, a->B, a->ld, (const float*)a->x,
-                           (const float*)a->weather, a->weather_rows, a->w_off, a->timestep, a->start_day, a->hour, a->doy,
-                           doy_inc, hod_inc, (float*)a->control, h->nd);
-    else
-        hipLaunchKernelGGL((rule_based_kernel<double>), grid, block, 0, st, *cfg, a->B, a->ld, (const double*)a->x,
-                           (const double*)a->weather, a->weather_rows, a->w_off, a->timestep, a->start_day, a->hour,
-                           a->doy, doy_inc, hod_inc, (double*)a->control, h->nd);
-    HIPCHK(hipGetLastError());
-    return GLGYM_OK;
 }
 
 int glgym_timer_start(glgym_handle h, void* stream)

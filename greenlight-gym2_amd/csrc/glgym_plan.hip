@@ -1,7 +1,8 @@
-// glgym_plan.hip -- the kernels of device-side planning (include/glgym.h glgym_plan_*): fork children from parent environments,
+// glgym_plan.hip -- device-side planning (include/glgym.h glgym_plan_*), kernels and C entry points: fork children from parent environments,
 // accumulate a step's reward into the children's returns, pick the best of K candidates per parent and the MPPI-weighted mean.
 // The scalar logic is gl_plan.hpp's (instantiated on the host by tests/planhost/planhost.cpp); the env-steps in between are
-// glgym_step's own kernels, launched by the C ABI -- nothing of them is instantiated or fused here.
+// glgym_step's own kernels (glgym.hip), reached through the C ABI -- nothing of them is instantiated or fused here.  Each entry point
+// checks its arguments and launches its kernels itself, at the bottom of this file.
 //
 // Layouts.  fork / accumulate: one lane per child; every child-side access is coalesced (SoA planes, lane c at base[i*ld + c]), the
 // parent side of a fork is a broadcast read (the K children of a parent sit in adjacent lanes and read one address).  select: one
@@ -31,7 +32,10 @@
 // model leaves alone, so that eight adjacent lanes write one contiguous row of nd values per step and a wavefront eight rows.  The
 // source rows are shared by the S scenarios of a greenhouse (L2 hits).  No LDS: nothing is exchanged between lanes.  The child
 // offsets are a second launch, lane = child.
-#include "glgym_plan.h"
+#include <cmath>
+#include <string>
+
+#include "glgym_internal.h"
 
 #include "gl_cem.hpp"
 #include "gl_plan.hpp"
@@ -337,85 +341,287 @@ __global__ __launch_bounds__(256) void plan_weather_offsets_kernel(glgym_plan_we
 
 }  // namespace
 
-template <class T>
-hipError_t plan_weather_launch(const glgym_plan_weather_args& a, int nd, hipStream_t stream)
+// The loop of glgym_plan_rollout and glgym_plan_rollout_scenarios: per horizon step k the caller's prologue(k) -- it points s at the step's
+// actions, or launches the scenario prologue --, glgym_step, then glgym_plan_accumulate with the weight gamma^k.  The first refusal ends it.
+template <class F>
+static int rollout_steps(glgym_handle h, glgym_step_args& s, const glgym_plan_rollout_args& r, void* stream, F&& prologue)
 {
-    const double innov = glwscen::innov_of(a.phi);       // the one square root, on the host
-    const int64_t n_lanes = (int64_t)a.P * a.S * glwscen::LANES;
-    hipLaunchKernelGGL(plan_weather_kernel<T>, dim3((unsigned)((n_lanes + 255) / 256)), dim3(256), 0, stream, a, nd, innov, n_lanes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !a.w_off_child) return e;
-    const int n_children = a.P * a.K * a.S;
-    hipLaunchKernelGGL(plan_weather_offsets_kernel, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, stream, a, n_children);
-    return hipGetLastError();
-}
-
-template hipError_t plan_weather_launch<float>(const glgym_plan_weather_args&, int, hipStream_t);
-template hipError_t plan_weather_launch<double>(const glgym_plan_weather_args&, int, hipStream_t);
-
-template <class T>
-hipError_t plan_scenario_launch(const glgym_plan_scenario_args& a, const float* p0_crop, hipStream_t stream)
-{
-    const int n_children = a.P * a.K * a.S;             // <= INT32_MAX: checked by the caller
-    hipLaunchKernelGGL(plan_scenario_kernel<T>, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, stream, a, p0_crop, n_children);
-    return hipGetLastError();
-}
-
-template hipError_t plan_scenario_launch<float>(const glgym_plan_scenario_args&, const float*, hipStream_t);
-template hipError_t plan_scenario_launch<double>(const glgym_plan_scenario_args&, const float*, hipStream_t);
-
-hipError_t plan_aggregate_launch(const glgym_plan_aggregate_args& a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(plan_aggregate_kernel, dim3((unsigned)a.J), dim3(WAVE), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t plan_sample_launch(const glgym_plan_sample_args& a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(plan_sample_kernel, dim3((unsigned)(((int64_t)a.P * a.K + WAVE - 1) / WAVE)), dim3(SAMPLE_WAVES * WAVE), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t plan_elites_launch(const glgym_plan_elites_args& a, hipStream_t stream)
-{
-    const int n_chunks = (a.K + glcem::CHUNK - 1) / glcem::CHUNK;
-    hipLaunchKernelGGL(plan_elites_kernel, dim3((unsigned)((int64_t)a.P * n_chunks)), dim3(glcem::TILE), 0, stream, a, n_chunks);
-    return hipGetLastError();
-}
-
-hipError_t plan_refit_launch(const glgym_plan_refit_args& a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(plan_refit_kernel, dim3(a.P, a.H), dim3(WAVE), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <class T>
-hipError_t plan_fork_launch(const glgym_plan_fork_args& a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(plan_fork_kernel<T>, dim3((a.n_children + 255) / 256), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <class T>
-hipError_t plan_accumulate_launch(const glgym_plan_accumulate_args& a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(plan_accumulate_kernel<T>, dim3((a.B + 255) / 256), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-template hipError_t plan_fork_launch<float>(const glgym_plan_fork_args&, hipStream_t);
-template hipError_t plan_fork_launch<double>(const glgym_plan_fork_args&, hipStream_t);
-template hipError_t plan_accumulate_launch<float>(const glgym_plan_accumulate_args&, hipStream_t);
-template hipError_t plan_accumulate_launch<double>(const glgym_plan_accumulate_args&, hipStream_t);
-
-hipError_t plan_select_launch(const glgym_plan_select_args& a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(plan_select_kernel, dim3(a.P), dim3(WAVE), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (a.mean_sequence) {
-        hipLaunchKernelGGL(plan_mean_kernel, dim3(a.P, a.H), dim3(WAVE), 0, stream, a);
-        e = hipGetLastError();
+    glgym_plan_accumulate_args acc;
+    acc.struct_size = (int32_t)sizeof acc;
+    acc.B = s.B; acc.ld = s.ld; acc.reward = s.reward; acc.info = s.info; acc.done = s.done; acc.step_flags = s.step_flags;
+    acc.ret = r.ret; acc.viol = r.viol; acc.n_steps = r.n_steps; acc.alive = r.alive; acc.failed = r.failed;
+    double w = 1.0;
+    for (int k = 0; k < r.H; ++k) {
+        int rc = prologue(k);
+        if (rc != GLGYM_OK) return rc;
+        if ((rc = glgym_step(h, &s, stream)) != GLGYM_OK) return rc;
+        acc.w = w;
+        if ((rc = glgym_plan_accumulate(h, &acc, stream)) != GLGYM_OK) return rc;
+        w = w * r.gamma;
     }
-    return e;
+    return GLGYM_OK;
 }
+
+extern "C" {
+
+// ---- the C entry points: argument checks, the launches, and the rollouts' loop over glgym_step (glgym.hip's, through the C ABI) ----
+static bool plan_size_ok(const char* who, int32_t got, size_t want)
+{
+    if (got == (int32_t)want) return true;
+    g_err = std::string(who) + ": struct_size is " + std::to_string(got) + ", this library expects " + std::to_string(want) +
+            " (ABI " + std::to_string(GLGYM_ABI_VERSION) + "): rebuild against include/glgym.h";
+    return false;
+}
+
+int glgym_plan_fork(glgym_handle h, const glgym_plan_fork_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_fork: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_fork", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->n_children < 1 || a->n_parents < 1 || a->ld_parent < a->n_parents || a->ld_child < a->n_children ||
+        (!a->parent && (a->K < 1 || (int64_t)a->n_parents * a->K < a->n_children)) ||
+        !a->x_parent || !a->u_parent || !a->timestep_parent || !a->w_off_parent || !a->x || !a->u || !a->timestep || !a->w_off ||
+        !a->ret || !a->viol || !a->n_steps || !a->alive || !a->failed) {
+        g_err = "glgym_plan_fork: bad arguments (null pointer, ld < batch, or without a parent table K < 1 or fewer than C = P * K slots)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    with_dtype(h->dtype, [&](auto t) { hipLaunchKernelGGL(plan_fork_kernel<decltype(t)>, dim3((a->n_children + 255) / 256), dim3(256), 0, st, *a); });
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_accumulate(glgym_handle h, const glgym_plan_accumulate_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_accumulate: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_accumulate", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->B < 1 || a->ld < a->B || !a->reward || !a->info || !a->done || !a->ret || !a->viol || !a->n_steps || !a->alive || !a->failed) {
+        g_err = "glgym_plan_accumulate: bad arguments (null pointer or ld < B)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    with_dtype(h->dtype, [&](auto t) { hipLaunchKernelGGL(plan_accumulate_kernel<decltype(t)>, dim3((a->B + 255) / 256), dim3(256), 0, st, *a); });
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_rollout(glgym_handle h, const glgym_plan_rollout_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_rollout: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_rollout", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->H < 1 || !(a->gamma >= 0.0) || !std::isfinite(a->gamma) || (!a->actions) == (!a->controls) || a->step.B < 1 ||
+        a->step.ld < a->step.B || !a->step.reward || !a->step.info || !a->step.done || !a->ret || !a->viol || !a->n_steps ||
+        !a->alive || !a->failed) {
+        g_err = "glgym_plan_rollout: bad arguments (H < 1, gamma, exactly one of actions / controls, ld >= B, non-null reward / info / done / accumulators)";
+        return GLGYM_EINVAL;
+    }
+    glgym_step_args s = a->step;                 // glgym_step checks its struct_size and the remaining members
+    s.metrics = nullptr;
+    const size_t plane = (size_t)NU * (size_t)s.ld * (h->dtype == GLGYM_F32 ? sizeof(float) : sizeof(double));
+    return rollout_steps(h, s, *a, stream, [&](int k) {
+        s.action = a->actions ? a->actions + (size_t)k * (size_t)s.B * NU : nullptr;
+        s.control = a->controls ? (const void*)((const char*)a->controls + (size_t)k * plane) : nullptr;
+        return (int)GLGYM_OK;
+    });
+}
+
+int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_select: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_select", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    const bool wants_actions = a->best_action || a->best_sequence || a->mean_sequence;
+    if (a->P < 1 || a->K < 1 || a->H < 1 || a->H > 65535 || (int64_t)a->P * a->K > INT32_MAX || !a->ret || !a->failed || !a->best_k ||
+        !a->best_ret || (wants_actions && !a->actions) || (a->mean_sequence && !(a->temperature > 0.0 && std::isfinite(a->temperature)))) {
+        g_err = "glgym_plan_select: bad arguments (P, K, H < 1, H > 65 535, null pointer, action outputs without actions, or mean_sequence "
+                "without a finite temperature > 0)";
+        return GLGYM_EINVAL;
+    }
+    // the kernel multiplies by 1 / temperature: at 2^-1024 and below that is +inf and the best candidate's own (ret - max) * inf = 0 * inf a NaN
+    if (a->mean_sequence && !std::isfinite(1.0 / a->temperature)) {
+        g_err = "glgym_plan_select: temperature is too small (1 / temperature is not finite: it must be above 2^-1024, about 5.6e-309)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(plan_select_kernel, dim3(a->P), dim3(WAVE), 0, st, *a);
+    HIPCHK(hipGetLastError());
+    if (a->mean_sequence) {
+        hipLaunchKernelGGL(plan_mean_kernel, dim3(a->P, a->H), dim3(WAVE), 0, st, *a);
+        HIPCHK(hipGetLastError());
+    }
+    return GLGYM_OK;
+}
+
+// the cross-entropy method's stages (gl_cem.hpp): every check that needs no device memory happens here, before anything is launched
+int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_sample: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_sample", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->K < 1 || a->H < 1 || (int64_t)a->P * a->K > INT32_MAX - 255 || !a->mean || !a->std || !a->actions ||
+        !(a->beta >= 0.0 && a->beta < 1.0) || a->carry < 0 ||
+        (a->carry > 0 && (!a->prev_actions || !a->prev_elite_k || !a->prev_n_elite || a->prev_E < a->carry || a->prev_actions == a->actions))) {
+        g_err = "glgym_plan_sample: bad arguments (P, K, H < 1, null pointer, beta outside [0, 1), carry < 0, or with carry > 0: a missing "
+                "prev_ member, carry > prev_E, or prev_actions == actions -- sample into the other of two blocks)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipLaunchKernelGGL(plan_sample_kernel, dim3((unsigned)(((int64_t)a->P * a->K + WAVE - 1) / WAVE)), dim3(SAMPLE_WAVES * WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_elites: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_elites", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->K < 1 || a->E < 1 || a->E > a->K || (int64_t)a->P * a->K > INT32_MAX - 255 || !a->ret || !a->failed || !a->elite_k ||
+        !a->n_elite) {
+        g_err = "glgym_plan_elites: bad arguments (P, K < 1, E outside 1..K, or null pointer)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    const int n_chunks = (a->K + glcem::CHUNK - 1) / glcem::CHUNK;
+    hipLaunchKernelGGL(plan_elites_kernel, dim3((unsigned)((int64_t)a->P * n_chunks)), dim3(glcem::TILE), 0, (hipStream_t)stream, *a, n_chunks);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream)
+{
+    if (!h || !a) { g_err = "glgym_plan_refit: null handle / arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_refit", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->K < 1 || a->H < 1 || a->H > 65535 || a->E < 1 || a->E > a->K || (int64_t)a->P * a->K > INT32_MAX - 255 ||
+        !a->actions || !a->elite_k || !a->n_elite || !a->mean || !a->std || !a->mean_out || !a->std_out ||
+        !(a->alpha >= 0.0 && a->alpha < 1.0) || !(a->min_std >= 0.0 && std::isfinite(a->min_std))) {
+        g_err = "glgym_plan_refit: bad arguments (P, K, H < 1, H > 65 535, E outside 1..K, null pointer, alpha outside [0, 1), or min_std "
+                "negative or not finite)";
+        return GLGYM_EINVAL;
+    }
+    DeviceGuard dev_guard(h);
+    hipLaunchKernelGGL(plan_refit_kernel, dim3(a->P, a->H), dim3(WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+// robust planning (gl_scen.hpp).  The arguments are checked before the handle is looked at, so that a caller without a device gets the
+// refusal that names its mistake.
+static bool scenario_shape_ok(int32_t P, int32_t K, int32_t S, int32_t hold, double scale)
+{
+    return P >= 1 && K >= 1 && S >= 1 && S <= 256 && (int64_t)P * K * S <= INT32_MAX && (hold == 0 || hold == 1) && scale >= 0.0 &&
+           std::isfinite(scale);
+}
+
+int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_scenario: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_scenario", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || (int64_t)a->ld < (int64_t)a->P * a->K * a->S || a->h_step < 0 ||
+        a->h_step > 65535 || !a->crop || (!a->actions_in) != (!a->actions_out)) {
+        g_err = "glgym_plan_scenario: bad arguments (P, K, S < 1, S > 256, P*K*S > INT32_MAX, ld < P*K*S, h_step outside 0 .. 65 535, hold "
+                "not 0 | 1, scale negative or not finite, null crop, or one of actions_in / actions_out without the other)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_scenario: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int n_children = a->P * a->K * a->S;             // <= INT32_MAX: checked above
+    with_dtype(h->dtype, [&](auto t) {
+        hipLaunchKernelGGL(plan_scenario_kernel<decltype(t)>, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, st, *a, h->p0_crop_dev, n_children);
+    });
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_aggregate: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_aggregate", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->J < 1 || a->S < 1 || a->S > 256 || a->m < 1 || a->m > a->S || (int64_t)a->J * a->S > INT32_MAX || !a->ret || !a->failed ||
+        !a->ret_cand || !a->failed_cand || (a->viol_cand && (!a->viol || (int64_t)a->ld < (int64_t)a->J * a->S || a->ld_cand < a->J)) ||
+        (a->steps_cand && !a->n_steps)) {
+        g_err = "glgym_plan_aggregate: bad arguments (J, S < 1, S > 256, m outside 1 .. S, J*S > INT32_MAX, null pointer, or with viol_cand: "
+                "ld < J*S or ld_cand < J)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_aggregate: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    hipLaunchKernelGGL(plan_aggregate_kernel, dim3((unsigned)a->J), dim3(WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_rollout_scenarios: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_rollout_scenarios", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    const glgym_plan_rollout_args& r = a->rollout;
+    if (!plan_size_ok("glgym_plan_rollout_scenarios: rollout", r.struct_size, sizeof r)) return GLGYM_EINVAL;
+    if (r.controls) {
+        g_err = "glgym_plan_rollout_scenarios: raw-control scenario rollouts are not supported (rollout.controls must be NULL)";
+        return GLGYM_EINVAL;
+    }
+    glgym_step_args s = r.step;
+    if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || !a->staging || r.H < 1 || r.H > 65536 || !(r.gamma >= 0.0) ||
+        !std::isfinite(r.gamma) || !r.actions || (int64_t)s.B != (int64_t)a->P * a->K * a->S || s.ld < s.B || !s.crop_p || !s.reward ||
+        !s.info || !s.done || !r.ret || !r.viol || !r.n_steps || !r.alive || !r.failed) {
+        g_err = "glgym_plan_rollout_scenarios: bad arguments (P, K, S < 1, S > 256, hold not 0 | 1, scale negative or not finite, null "
+                "staging / actions / crop_p / reward / info / done / accumulators, H outside 1 .. 65 536, gamma, step.B != P*K*S, or ld < B)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_rollout_scenarios: null handle"; return GLGYM_EINVAL; }
+    s.metrics = nullptr;
+    s.action = a->staging;
+    s.control = nullptr;
+    // what glgym_step refuses without launching is refused by it, in its own words, before the first prologue is launched: a struct
+    // or pointer it checks itself, GLGYM_ODE_PIPE with a crop block (either step integrator), a BDF glgym_evalF setting on explicit steps
+    if (s.struct_size != (int32_t)sizeof s || !s.x || !s.u || !s.weather || !s.w_off || !s.timestep || s.weather_rows < 1 ||
+        h->variant == GLGYM_ODE_PIPE || (h->step_integrator != GLGYM_INTEGRATOR_BDF && h->integrator != GLGYM_INTEGRATOR_EXPLICIT)) {
+        const int rc = glgym_step(h, &s, stream);
+        if (rc != GLGYM_OK) return rc;
+        g_err = "glgym_plan_rollout_scenarios: glgym_step accepted a call it was expected to refuse";        // unreachable
+        return GLGYM_EINVAL;
+    }
+    glgym_plan_scenario_args sc;
+    sc.struct_size = (int32_t)sizeof sc;
+    sc.P = a->P; sc.K = a->K; sc.S = a->S; sc.ld = s.ld; sc.hold = a->hold; sc.scale = a->scale; sc.seed = a->seed;
+    sc.draw_index = a->draw_index; sc.draw_base = a->draw_base; sc.crop = (void*)s.crop_p; sc.actions_out = a->staging;
+    const size_t plane = (size_t)a->P * (size_t)a->K * NU;             // the candidates' action plane of one step
+    return rollout_steps(h, s, r, stream, [&](int k) {
+        sc.h_step = k;
+        sc.actions_in = r.actions + (size_t)k * plane;
+        return glgym_plan_scenario(h, &sc, stream);
+    });
+}
+
+// weather-forecast scenarios (gl_wscen.hpp): checked before the handle is looked at, like the entry points above
+int glgym_plan_weather(glgym_handle h, const glgym_plan_weather_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_weather: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_weather", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    bool sigma_ok = true;
+    for (int j = 0; j < 7; ++j) sigma_ok = sigma_ok && a->sigma[j] >= 0.0 && std::isfinite(a->sigma[j]);
+    if (a->P < 1 || a->K < 1 || a->S < 1 || a->S > 256 || a->H < 1 || a->H > 65536 || (int64_t)a->P * a->S * a->H > INT32_MAX ||
+        (int64_t)a->P * a->K * a->S > INT32_MAX || a->weather_rows < 1 || !sigma_ok || !(a->phi >= 0.0 && a->phi < 1.0) || !a->weather ||
+        !a->w_off_parent || !a->timestep_parent || !a->window) {
+        g_err = "glgym_plan_weather: bad arguments (P, K, S, H < 1, S > 256, H > 65 536, P*S*H or P*K*S > INT32_MAX, weather_rows < 1, a sigma "
+                "negative or not finite, phi outside [0, 1), or a null weather / w_off_parent / timestep_parent / window)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_weather: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    const double innov = glwscen::innov_of(a->phi);       // the one square root, on the host
+    const int64_t n_lanes = (int64_t)a->P * a->S * glwscen::LANES;
+    with_dtype(h->dtype, [&](auto t) {
+        hipLaunchKernelGGL(plan_weather_kernel<decltype(t)>, dim3((unsigned)((n_lanes + 255) / 256)), dim3(256), 0, st, *a, h->nd, innov, n_lanes);
+    });
+    HIPCHK(hipGetLastError());
+    if (!a->w_off_child) return GLGYM_OK;
+    const int n_children = a->P * a->K * a->S;
+    hipLaunchKernelGGL(plan_weather_offsets_kernel, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, st, *a, n_children);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+}  // extern "C"

@@ -1,10 +1,11 @@
-// glgym_rng.hip -- the kernels of rng = "numpy": each environment's own PCG64 stream (gl_pcg64.hpp) on the device, drawing what the
-// reference's TomatoEnv draws from its NumPy generator, in the same order and bit for bit.
+// glgym_rng.hip -- the kernels of rng = "numpy" and their C entry points (glgym_rng_crop_noise, glgym_rng_reset_draw): each
+// environment's own PCG64 stream (gl_pcg64.hpp) on the device, drawing what the reference's TomatoEnv draws from its NumPy generator,
+// in the same order and bit for bit.
 //
 // Layout: one lane per environment.  The stream state is the caller's SoA buffer uint64 [5][ld] (state lo / hi, inc lo / hi, buffer
 // word), so adjacent lanes read adjacent addresses; the increment is read only.  All arithmetic is 64-bit integer and fp64 on the
 // vector unit; no LDS, no atomics, no scalar-memory stores.
-#include "glgym_rng.h"
+#include "glgym_internal.h"
 
 #include "gl_pcg64.hpp"
 
@@ -60,20 +61,36 @@ __global__ __launch_bounds__(256) void rng_reset_draw_kernel(int B, int ld, cons
 
 }  // namespace
 
-template <class T>
-hipError_t rng_crop_noise_launch(T* crop_p, int B, int ld, const float* p0, double scale, uint64_t* rng_state, hipStream_t stream)
+extern "C" {
+
+int glgym_rng_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double scale, uint64_t* rng_state, void* stream)
 {
-    hipLaunchKernelGGL(rng_crop_noise_kernel<T>, dim3((B + 255) / 256), dim3(256), 0, stream, crop_p, B, ld, p0, scale, rng_state);
-    return hipGetLastError();
+    DeviceGuard dev_guard(h);
+    if (!h || !rng_state || B < 1 || ld < B || !(scale >= 0.0)) {
+        g_err = "glgym_rng_crop_noise: bad arguments (null handle or stream buffer, ld < B, or a negative scale)";
+        return GLGYM_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    with_dtype(h->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(rng_crop_noise_kernel<T>, dim3((B + 255) / 256), dim3(256), 0, st, (T*)crop_p, B, ld, h->p0_crop_dev, scale, rng_state);
+    });
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
 }
 
-template hipError_t rng_crop_noise_launch<float>(float*, int, int, const float*, double, uint64_t*, hipStream_t);
-template hipError_t rng_crop_noise_launch<double>(double*, int, int, const float*, double, uint64_t*, hipStream_t);
-
-hipError_t rng_reset_draw_launch(int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
-                                 const int* start_rows, const float* start_days, int* w_off, float* start_day, hipStream_t stream)
+int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
+                         const int32_t* start_rows, const float* start_days, int32_t* w_off, float* start_day, void* stream)
 {
-    hipLaunchKernelGGL(rng_reset_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, ld, mask, rng_state, n_years, n_days,
+    DeviceGuard dev_guard(h);
+    if (!h || !rng_state || B < 1 || ld < B || n_years < 1 || n_days < 1 || !start_rows || !w_off) {
+        g_err = "glgym_rng_reset_draw: bad arguments (null pointer, ld < B, or an empty start grid)";
+        return GLGYM_EINVAL;
+    }
+    hipLaunchKernelGGL(rng_reset_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, ld, mask, rng_state, n_years, n_days,
                        start_rows, start_days, w_off, start_day);
-    return hipGetLastError();
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
 }
+
+}  // extern "C"

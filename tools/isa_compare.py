@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Did a change move a kernel?  Compares two device assemblies of glgym.hip (`make -C greenlight-gym2_amd/csrc asm` writes /tmp/glgym.s;
-keep the parent commit's under another name) kernel by kernel: instruction streams with labels and symbol names normalised, registers,
+"""Did a change move a kernel?  Compares two sets of device assemblies (`make -C greenlight-gym2_amd/csrc asm` writes one per
+translation unit, /tmp/glgym.s, /tmp/glgym_env.s, ...; keep the parent commit's under other names) kernel by kernel: instruction streams with labels and symbol names normalised, registers,
 scratch, LDS, whether any loop holds a scratch instruction, the four largest loop blocks, and -- where the streams differ -- whether the
 floating-point opcode histogram did.
-    python tools/isa_compare.py parent.s change.s [filter]      (profiles/step_reset_fusion.txt section 1)"""
+A side is one .s file or several joined by commas: a kernel is found whichever translation unit holds it, so a kernel that
+only moved between files compares as itself.  The default filter shows the kernels that inline gl_envlayer.hpp; "." shows all.
+    python tools/isa_compare.py parent.s[,parent2.s,...] change.s[,change2.s,...] [filter]      (profiles/tu_split.txt section 1)"""
 import collections
 import re
 import subprocess
@@ -54,8 +56,8 @@ def scan_body(lines):
     return ins, blocks
 
 
-def kernels(path):
-    s = open(path).read()
+def kernels(paths):
+    s = "\n".join(open(p).read() for p in paths.split(","))
     names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", s, flags=re.M)
     out = {}
     for name, dn in zip(names, demangle(names)):
@@ -72,7 +74,7 @@ def kernels(path):
         nv, acc = field("next_free_vgpr"), field("accum_offset")
         big = sorted([b for b in blocks if b[0] >= 2], key=lambda b: -b[1])[:4]
         fp = collections.Counter(t.split()[0] for t in ins if re.match(r"v_\S*f(16|32|64)", t.split()[0]))
-        out[dn] = dict(ins=ins, vgpr=min(nv, acc), agpr=max(0, nv - acc), scratch=field("private_segment_fixed_size"),
+        out[dn] = dict(mangled=name, ins=ins, vgpr=min(nv, acc), agpr=max(0, nv - acc), scratch=field("private_segment_fixed_size"),
                        lds=field("group_segment_fixed_size"), big=[(b[1], b[0], b[2], b[3]) for b in big], fp=fp,
                        loop_scratch=any(b[4] for b in blocks if b[0] >= 1))
     return out
@@ -81,8 +83,11 @@ def kernels(path):
 def status(p, c):
     if p is None:
         return "new"
+    if p["mangled"] != c["mangled"]:
+        return "MANGLED NAME CHANGED: %s -> %s" % (p["mangled"], c["mangled"])
     if p["ins"] == c["ins"]:
-        return "= parent, instruction for instruction"
+        res = [k for k in ("vgpr", "agpr", "scratch", "lds") if p[k] != c[k]]
+        return "= parent, instruction for instruction" + ("".join("; %s WAS %d" % (k, p[k]) for k in res))
     if p["fp"] == c["fp"]:
         hist = "unchanged"
     else:

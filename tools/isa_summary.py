@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """Per-kernel ISA facts of libglgym.so's device code: registers (VGPR + AGPR), scratch, LDS, static instruction counts.
-    python tools/isa_summary.py [EXTRA hipcc flags ...]        (cross-compiles, no GPU needed; writes /tmp/glgym_isa.s)"""
+    python tools/isa_summary.py [EXTRA hipcc flags ...]        (cross-compiles, no GPU needed; writes /tmp/<unit>_isa.s)
+Every translation unit of csrc/ is compiled, one after the other."""
 import re, subprocess, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 csrc = ROOT / "greenlight-gym2_amd" / "csrc"
-out = Path("/tmp/glgym_isa.s")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-fno-slp-vectorize",
-                       "--offload-arch=gfx950", "-std=c++17", f"-I{ROOT / 'include'}", "-S", "--cuda-device-only", "-o", str(out),
-                       str(csrc / "glgym.hip")] + sys.argv[1:])
-s = out.read_text()
+s = ""
+for unit in ("glgym", "glgym_env", "glgym_ancillary", "glgym_plan", "glgym_rng", "glgym_bdf"):
+    out = Path(f"/tmp/{unit}_isa.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-fno-slp-vectorize",
+                           "--offload-arch=gfx950", "-std=c++17", f"-I{ROOT / 'include'}", "-S", "--cuda-device-only", "-o", str(out),
+                           str(csrc / f"{unit}.hip")] + sys.argv[1:])
+    s += out.read_text() + "\n"
 dem = {}
 for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)", s, flags=re.M):
     name = m.group(1)
