@@ -32,6 +32,11 @@
 // model leaves alone, so that eight adjacent lanes write one contiguous row of nd values per step and a wavefront eight rows.  The
 // source rows are shared by the S scenarios of a greenhouse (L2 hits).  No LDS: nothing is exchanged between lanes.  The child
 // offsets are a second launch, lane = child.
+//
+// Closed-loop rule-based rollouts (glgym_rule_rows / glgym_plan_rollout_rule; scalar logic in gl_rule.hpp, instantiated on the host by
+// tests/rulehost/rulehost.cpp).  rows: lane = row, the rule-based controller with the row's own 29 constants, decoded from its row of
+// the candidates' parameter block.  The rollout is rollout_steps with that kernel (after the scenario prologue, if any) in front of
+// every env-step, writing the control plane the step then reads.
 #include <cmath>
 #include <string>
 
@@ -39,6 +44,7 @@
 
 #include "gl_cem.hpp"
 #include "gl_plan.hpp"
+#include "gl_rule.hpp"
 #include "gl_scen.hpp"
 #include "gl_wscen.hpp"
 
@@ -339,6 +345,32 @@ __global__ __launch_bounds__(256) void plan_weather_offsets_kernel(glgym_plan_we
     a.w_off_child[c] = glwscen::child_offset(ps, a.H, a.timestep_parent[cand / a.K]);
 }
 
+// grid = ceil(B / 256), lane = row b.  The row's 29 constants are decoded from theta row b / max(S, 1) into registers (the space comes
+// by field, gl_rule.hpp: no run-time field index); the theta reads are 6 consecutive floats per row and plane, the S children of a
+// candidate read one row (a broadcast).  x, the clocks and the six control planes are coalesced along b; the weather row is a gather.
+template <class T>
+__global__ __launch_bounds__(256) void rule_rows_kernel(glrule::Space sp, const float* __restrict__ theta, int J, int S, int B, int ld,
+                                                        const T* __restrict__ x, const T* __restrict__ weather, int weather_rows,
+                                                        const int* __restrict__ w_off, const int* __restrict__ timestep,
+                                                        const float* __restrict__ start_day, const double* hour, const double* doy_in,
+                                                        double doy_inc, double hod_inc, T* __restrict__ control, int nd)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int ts = timestep[b];
+    int row = w_off[b] + ts;
+    row = row >= weather_rows ? weather_rows - 1 : (row < 0 ? 0 : row);
+    const T* w = weather + (size_t)row * nd;
+    const double hod = hour ? hour[b] : fmod((double)ts * hod_inc, 24.0);
+    const double doy = doy_in ? doy_in[b] : (double)start_day[b] + (double)ts * doy_inc;
+    double c[glrule::NF], u[NU];
+    glrule::row_cfg(sp, theta, J, glrule::theta_row(b, S), c);
+    glrule::controls(c, (double)w[0], (double)w[1], (double)w[7], (double)w[8], (double)w[9], (double)x[b], (double)x[(size_t)2 * ld + b],
+                     (double)x[(size_t)15 * ld + b], hod, doy, u);
+#pragma unroll
+    for (int i = 0; i < NU; ++i) control[(size_t)i * ld + b] = (T)u[i];
+}
+
 }  // namespace
 
 // The loop of glgym_plan_rollout and glgym_plan_rollout_scenarios: per horizon step k the caller's prologue(k) -- it points s at the step's
@@ -622,6 +654,118 @@ int glgym_plan_weather(glgym_handle h, const glgym_plan_weather_args* a, void* s
     hipLaunchKernelGGL(plan_weather_offsets_kernel, dim3((unsigned)(((int64_t)n_children + 255) / 256)), dim3(256), 0, st, *a, n_children);
     HIPCHK(hipGetLastError());
     return GLGYM_OK;
+}
+
+// closed-loop rule-based rollouts (gl_rule.hpp): checked before the handle is looked at, like the entry points above
+static bool rule_space_ok(const char* who, const glgym_rule_space* sp)
+{
+    const char* why = glrule::space_error(sp);
+    if (why) g_err = std::string(who) + ": bad search space (" + why + ")";
+    return !why;
+}
+
+// the launch behind both entry points: arguments already checked
+static int launch_rule_rows(glgym_handle h, const glrule::Space& sp, const float* theta, int J, int S, const glgym_rule_args& r, hipStream_t st)
+{
+    DeviceGuard dev_guard(h);
+    const double doy_inc = std::fmod(h->dt / 86400.0, 365.0), hod_inc = h->dt / 3600.0;       // glgym_rule_based's
+    with_dtype(h->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((rule_rows_kernel<T>), dim3((r.B + 255) / 256), dim3(256), 0, st, sp, theta, J, S, r.B, r.ld, (const T*)r.x,
+                           (const T*)r.weather, r.weather_rows, r.w_off, r.timestep, r.start_day, r.hour, r.doy, doy_inc, hod_inc,
+                           (T*)r.control, h->nd);
+    });
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_rule_rows(glgym_handle h, const glgym_rule_rows_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_rule_rows: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_rule_rows", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!rule_space_ok("glgym_rule_rows", &a->space)) return GLGYM_EINVAL;
+    const glgym_rule_args& r = a->rule;
+    if (!a->theta || !r.control) { g_err = "glgym_rule_rows: null theta or control"; return GLGYM_EINVAL; }
+    if (r.B < 1 || r.ld < r.B) { g_err = "glgym_rule_rows: B < 1 or ld < B"; return GLGYM_EINVAL; }
+    if (a->S < 0 || a->S > 256) { g_err = "glgym_rule_rows: S outside 0 .. 256"; return GLGYM_EINVAL; }
+    if (a->J < 1 || (int64_t)r.B > (int64_t)a->J * (a->S > 1 ? a->S : 1)) {
+        g_err = "glgym_rule_rows: J < 1, or more rows than parameters (B > J * max(S, 1))";
+        return GLGYM_EINVAL;
+    }
+    if (!r.x || !r.weather || !r.w_off || !r.timestep || r.weather_rows < 1 || (!r.start_day && !r.doy)) {
+        g_err = "glgym_rule_rows: bad arguments (null x / weather / w_off / timestep, weather_rows < 1, or neither start_day nor doy)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_rule_rows: null handle"; return GLGYM_EINVAL; }
+    return launch_rule_rows(h, glrule::make_space(a->space), a->theta, a->J, a->S, r, (hipStream_t)stream);
+}
+
+int glgym_plan_rollout_rule(glgym_handle h, const glgym_plan_rollout_rule_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_rollout_rule: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_rollout_rule", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    const glgym_plan_rollout_args& r = a->rollout;
+    if (!plan_size_ok("glgym_plan_rollout_rule: rollout", r.struct_size, sizeof r)) return GLGYM_EINVAL;
+    if (!rule_space_ok("glgym_plan_rollout_rule", &a->space)) return GLGYM_EINVAL;
+    if (r.actions) {
+        g_err = "glgym_plan_rollout_rule: the controller makes the controls (rollout.actions must be NULL)";
+        return GLGYM_EINVAL;
+    }
+    if (!a->theta || !r.controls) { g_err = "glgym_plan_rollout_rule: null theta or controls"; return GLGYM_EINVAL; }
+    if (a->record != 0 && a->record != 1) { g_err = "glgym_plan_rollout_rule: record must be 0 or 1"; return GLGYM_EINVAL; }
+    if (r.H < 1 || !(r.gamma >= 0.0) || !std::isfinite(r.gamma)) {
+        g_err = "glgym_plan_rollout_rule: H < 1, or gamma negative or not finite";
+        return GLGYM_EINVAL;
+    }
+    if (a->S < 0 || a->S > 256) { g_err = "glgym_plan_rollout_rule: S outside 0 .. 256"; return GLGYM_EINVAL; }
+    glgym_step_args s = r.step;
+    if (s.B < 1 || s.ld < s.B) { g_err = "glgym_plan_rollout_rule: step.B < 1 or step.ld < step.B"; return GLGYM_EINVAL; }
+    if (a->S == 0) {
+        if (a->J < 1 || s.B > a->J) { g_err = "glgym_plan_rollout_rule: without scenarios step.B <= J is needed (and J >= 1)"; return GLGYM_EINVAL; }
+    } else if (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || r.H > 65536 || (int64_t)s.B != (int64_t)a->P * a->K * a->S ||
+               (int64_t)a->J != (int64_t)a->P * a->K || !s.crop_p) {
+        g_err = "glgym_plan_rollout_rule: with scenarios P, K >= 1, hold 0 | 1, scale finite and >= 0, H <= 65 536, step.B == P*K*S, "
+                "J == P*K and a crop block (step.crop_p) are needed";
+        return GLGYM_EINVAL;
+    }
+    if (!a->start_day || !s.reward || !s.info || !s.done || !r.ret || !r.viol || !r.n_steps || !r.alive || !r.failed) {
+        g_err = "glgym_plan_rollout_rule: null start_day / reward / info / done / accumulators";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_rollout_rule: null handle"; return GLGYM_EINVAL; }
+    const size_t plane = (size_t)NU * (size_t)s.ld * (h->dtype == GLGYM_F32 ? sizeof(float) : sizeof(double));
+    s.metrics = nullptr;
+    s.action = nullptr;
+    s.control = r.controls;
+    // what glgym_step refuses without launching is refused by it, in its own words, before the first prologue is launched: a struct
+    // or pointer it checks itself, GLGYM_ODE_PIPE with a crop block, another scheme than RK4 or the BDF step integrator, a BDF
+    // glgym_evalF setting on explicit steps
+    const bool pipe = h->variant == GLGYM_ODE_PIPE, bdf = h->step_integrator == GLGYM_INTEGRATOR_BDF;
+    if (s.struct_size != (int32_t)sizeof s || !s.x || !s.u || !s.weather || !s.w_off || !s.timestep || s.weather_rows < 1 ||
+        (bdf ? pipe : (h->integrator != GLGYM_INTEGRATOR_EXPLICIT || (pipe && (s.crop_p || h->scheme != GLGYM_SCHEME_RK4))))) {
+        const int rc = glgym_step(h, &s, stream);
+        if (rc != GLGYM_OK) return rc;
+        g_err = "glgym_plan_rollout_rule: glgym_step accepted a call it was expected to refuse";        // unreachable
+        return GLGYM_EINVAL;
+    }
+    const glrule::Space sp = glrule::make_space(a->space);
+    glgym_rule_args rule;
+    rule.B = s.B; rule.ld = s.ld; rule.x = s.x; rule.weather = s.weather; rule.weather_rows = s.weather_rows; rule.w_off = s.w_off;
+    rule.timestep = s.timestep; rule.start_day = a->start_day; rule.hour = nullptr; rule.doy = nullptr;
+    glgym_plan_scenario_args sc;
+    sc.struct_size = (int32_t)sizeof sc;
+    sc.P = a->P; sc.K = a->K; sc.S = a->S; sc.ld = s.ld; sc.hold = a->hold; sc.scale = a->scale; sc.seed = a->seed;
+    sc.draw_index = a->draw_index; sc.draw_base = a->draw_base; sc.crop = (void*)s.crop_p; sc.actions_in = nullptr; sc.actions_out = nullptr;
+    return rollout_steps(h, s, r, stream, [&](int k) {
+        if (a->S >= 1) {
+            sc.h_step = k;
+            const int rc = glgym_plan_scenario(h, &sc, stream);
+            if (rc != GLGYM_OK) return rc;
+        }
+        rule.control = (char*)const_cast<void*>(r.controls) + (a->record ? (size_t)k * plane : 0);
+        s.control = rule.control;
+        return launch_rule_rows(h, sp, a->theta, a->J, a->S, rule, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

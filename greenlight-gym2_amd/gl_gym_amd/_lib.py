@@ -243,6 +243,25 @@ class RuleArgs(C.Structure):
                 ("hour", C.c_void_p), ("doy", C.c_void_p), ("control", C.c_void_p)]
 
 
+# closed-loop rule-based rollouts (include/glgym.h glgym_rule_rows / glgym_plan_rollout_rule)
+RULE_BANDS = ("vent_heat_Pband", "vent_rh_Pband", "vent_cold_Pband", "thScrPband", "thScrRhPband", "tHeatBand", "co2Band")
+
+
+class RuleSpace(C.Structure):
+    _fields_ = [("base", RuleCfg), ("D", C.c_int32), ("field", C.c_int32 * 29), ("lo", C.c_double * 29), ("hi", C.c_double * 29)]
+
+
+class RuleRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("J", C.c_int32), ("S", C.c_int32), ("rule", RuleArgs), ("space", RuleSpace),
+                ("theta", C.c_void_p)]
+
+
+class PlanRolloutRuleArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("record", C.c_int32), ("rollout", PlanRolloutArgs), ("space", RuleSpace),
+                ("theta", C.c_void_p), ("start_day", C.c_void_p), ("J", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("S", C.c_int32),
+                ("hold", C.c_int32), ("scale", C.c_double), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p)]
+
+
 class WeatherArgs(C.Structure):
     _fields_ = [("n_raw", C.c_int32), ("time", C.c_void_p), ("i_glob", C.c_void_p), ("t_out", C.c_void_p),
                 ("rh", C.c_void_p), ("wind", C.c_void_p), ("t_sky", C.c_void_p), ("co2_ppm", C.c_double),
@@ -302,6 +321,8 @@ PROTOTYPES = {
     "glgym_plan_aggregate": (C.c_int, [C.c_void_p, C.POINTER(PlanAggregateArgs), C.c_void_p]),
     "glgym_plan_weather": (C.c_int, [C.c_void_p, C.POINTER(PlanWeatherArgs), C.c_void_p]),
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
+    "glgym_rule_rows": (C.c_int, [C.c_void_p, C.POINTER(RuleRowsArgs), C.c_void_p]),
+    "glgym_plan_rollout_rule": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutRuleArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),
     "glgym_timer_start": (C.c_int, [C.c_void_p, C.c_void_p]),

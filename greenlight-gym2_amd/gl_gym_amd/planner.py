@@ -30,7 +30,11 @@ a rollout what they were before.
 
 Iterated sampling (the cross-entropy method, glgym_plan_sample / _elites / _refit): cem() draws the candidates on the device from a
 Gaussian per (horizon step, greenhouse, actuator), simulates them, ranks each greenhouse's returns, refits mean and spread to the best
-n_elite, and repeats; sample(), elites() and refit() are the single stages, shift() the receding-horizon warm start."""
+n_elite, and repeats; sample(), elites() and refit() are the single stages, shift() the receding-horizon warm start.
+
+Closed-loop candidates (RuleSearch below, glgym_rule_rows / glgym_plan_rollout_rule): every candidate above is an open-loop sequence.
+RuleSearch rolls out a feedback law instead -- the rule-based controller with per-candidate constants, evaluated on each child's own
+state before every step -- and tunes those constants with the same cross-entropy stages."""
 from __future__ import annotations
 
 import ctypes as C
@@ -253,16 +257,26 @@ class Planner:
             sc = L.make_plan_args(L.PlanRolloutScenariosArgs, B, K, self.S, 1 if self.noise == "hold" else 0, self.noise_scale,
                                   self.scenario_seed & (2 ** 64 - 1), self._scen_draw, self.scenario_base_t.data_ptr(), self.stage_t.data_ptr(), a)
             L.check(e._lib.glgym_plan_rollout_scenarios(e._h, C.byref(sc), e._stream()), "glgym_plan_rollout_scenarios")
-            g = L.make_plan_args(L.PlanAggregateArgs, self.J, self.S, self.n_tail, self.ld, self.ld_cand, self.ret_t.data_ptr(),
-                                 self.failed_t.data_ptr(), self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.ret_cand_t.data_ptr(),
-                                 self.failed_cand_t.data_ptr(), self.viol_cand_T.data_ptr(), self.steps_cand_t.data_ptr())
-            L.check(e._lib.glgym_plan_aggregate(e._h, C.byref(g), e._stream()), "glgym_plan_aggregate")
-            torch.amin(self.alive_t.view(self.J, self.S), dim=1, out=self.alive_cand_t)
-            return (self.ret_cand_t.view(B, K), self.alive_cand_t.view(B, K), self.steps_cand_t.view(B, K),
-                    self.viol_cand_T[:, :self.J].view(3, B, K), self.failed_cand_t.view(B, K))
+            return self._aggregate()
         L.check(e._lib.glgym_plan_rollout(e._h, C.byref(a), e._stream()), "glgym_plan_rollout")
+        return self._results()
+
+    def _results(self):
+        """The five tensors rollout() returns without scenarios: views of the children's accumulators."""
+        B, K = self.B, self.K
         return (self.ret_t.view(B, K), self.alive_t.view(B, K), self.n_steps_t.view(B, K), self.viol_T[:, :self.C].view(3, B, K),
                 self.failed_t.view(B, K))
+
+    def _aggregate(self):
+        """glgym_plan_aggregate over the S scenario runs of every candidate -> the five tensors rollout() returns with scenarios."""
+        e, B, K = self.env, self.B, self.K
+        g = L.make_plan_args(L.PlanAggregateArgs, self.J, self.S, self.n_tail, self.ld, self.ld_cand, self.ret_t.data_ptr(),
+                             self.failed_t.data_ptr(), self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.ret_cand_t.data_ptr(),
+                             self.failed_cand_t.data_ptr(), self.viol_cand_T.data_ptr(), self.steps_cand_t.data_ptr())
+        L.check(e._lib.glgym_plan_aggregate(e._h, C.byref(g), e._stream()), "glgym_plan_aggregate")
+        self.torch.amin(self.alive_t.view(self.J, self.S), dim=1, out=self.alive_cand_t)
+        return (self.ret_cand_t.view(B, K), self.alive_cand_t.view(B, K), self.steps_cand_t.view(B, K),
+                self.viol_cand_T[:, :self.J].view(3, B, K), self.failed_cand_t.view(B, K))
 
     def new_scenarios(self):
         """Draw other futures (crop and weather alike) from the next scenario rollout on: the scenario draw index moves by one.  (A replayed
@@ -437,3 +451,339 @@ class Planner:
             t[-1].fill_(last)
         self._drop_carry()
         return self.cem_mean_t, self.cem_std_t
+
+
+# ---- closed-loop rule-based rollouts and controller tuning (include/glgym.h glgym_rule_rows / glgym_plan_rollout_rule) --------------
+RULE_CLOCK_QUANTUM = 450.0        # [s] dt / 3600 must be a multiple of 1/8 h: then timestep * dt / 3600 is the reference's running sum
+
+
+def check_rule_dt(dt: float) -> None:
+    """The children's clocks are DERIVED, hour = (timestep * dt / 3600) mod 24 (glgym_rule_args with hour = NULL).  The reference keeps
+    a running sum, which the product reproduces exactly only where the increment is a multiple of 1/8 h, dt a multiple of 450 s; the
+    environment's running-sum table for other steps (dt = 300 s) is not forked.  ValueError otherwise."""
+    if not float(dt) > 0.0 or float(dt) % RULE_CLOCK_QUANTUM != 0.0:
+        raise ValueError(f"rule-based rollouts need dt to be a multiple of {RULE_CLOCK_QUANTUM:g} s (got {dt}): the children's clocks are "
+                         "derived from the timestep by the product form; the running-sum clock of other steps is not forked")
+
+
+class RuleParams:
+    """The search space of a controller tuning on the host: which of the 29 constants of gl_gym_amd.baseline.RuleBasedController are
+    tuned, between which bounds, and the base controller the others come from -- include/glgym.h glgym_rule_space.  tune: {name: (lo, hi)},
+    in the order given (component i of theta is the i-th name).  encode / decode are NumPy restatements of the header's map."""
+
+    def __init__(self, tune, base=None):
+        import numpy as np
+        from .baseline import RuleBasedController
+        self.np = np
+        self.base = RuleBasedController() if base is None else base
+        if not tune:
+            raise ValueError("tune must name at least one controller constant: {name: (lo, hi), ...}")
+        unknown = sorted(set(tune) - set(L.RULE_FIELDS))
+        if unknown:
+            raise ValueError(f"tune: unknown controller constants {unknown}; the names are {L.RULE_FIELDS}")
+        self.names = tuple(tune)
+        self.D, self.Ht = len(self.names), (len(self.names) + L.NU - 1) // L.NU
+        self.field = [L.RULE_FIELDS.index(n) for n in self.names]
+        try:
+            bounds = np.array([[float(tune[n][0]), float(tune[n][1])] for n in self.names], dtype=np.float64).reshape(self.D, 2)
+        except (TypeError, IndexError):
+            raise ValueError("tune: every entry must be a (lo, hi) pair of numbers") from None
+        self.lo, self.hi = bounds[:, 0].copy(), bounds[:, 1].copy()
+        if not np.isfinite(bounds).all() or (self.lo > self.hi).any():
+            raise ValueError("tune: bounds must be finite with lo <= hi")
+        for n, lo, hi in zip(self.names, self.lo, self.hi):
+            if n in L.RULE_BANDS and lo <= 0.0 <= hi:
+                raise ValueError(f"tune: the interval of the proportional band {n} must not contain 0 (the rules divide by it)")
+        for n in L.RULE_BANDS:
+            if n not in self.names and float(getattr(self.base, n)) == 0.0:
+                raise ValueError(f"base: the proportional band {n} is 0 (the rules divide by it)")
+
+    def struct(self):
+        s = L.RuleSpace()
+        s.base = L.RuleCfg(*[float(getattr(self.base, n)) for n in L.RULE_FIELDS])
+        s.D = self.D
+        for i in range(self.D):
+            s.field[i], s.lo[i], s.hi[i] = self.field[i], self.lo[i], self.hi[i]
+        return s
+
+    def values(self, controller_or_dict):
+        """The tuned constants of a controller, or of a dict (names it lacks come from base) -> float64 [D]."""
+        src = controller_or_dict
+        if isinstance(src, dict):
+            unknown = sorted(set(src) - set(L.RULE_FIELDS))
+            if unknown:
+                raise ValueError(f"unknown controller constants {unknown}")
+            return self.np.array([float(src.get(n, getattr(self.base, n))) for n in self.names], dtype=self.np.float64)
+        return self.np.array([float(getattr(src, n)) for n in self.names], dtype=self.np.float64)
+
+    def inside(self, controller_or_dict) -> bool:
+        v = self.values(controller_or_dict)
+        return bool(((self.lo <= v) & (v <= self.hi)).all())
+
+    def encode(self, controller_or_dict):
+        """-> theta float32 [Ht, 1, 6]: tuned constant i mapped from [lo_i, hi_i] onto [-1, 1] (0 where lo_i = hi_i), padding 0.
+        ValueError if a value lies outside its bounds."""
+        np, v = self.np, self.values(controller_or_dict)
+        if not self.inside(controller_or_dict):
+            bad = [n for n, x, lo, hi in zip(self.names, v, self.lo, self.hi) if not lo <= x <= hi]
+            raise ValueError(f"encode: {bad} outside the bounds of the search space")
+        span = self.hi - self.lo
+        t = np.where(span > 0, 2.0 * (v - self.lo) / np.where(span > 0, span, 1.0) - 1.0, 0.0)
+        theta = np.zeros(self.Ht * L.NU, dtype=np.float32)
+        theta[:self.D] = t.astype(np.float32)
+        return theta.reshape(self.Ht, 1, L.NU)
+
+    def decode(self, theta):
+        """theta [Ht, J, 6] (any float array) -> {name: float64 [J]} by the header's formula; a NaN reads as -1, i.e. lo."""
+        np = self.np
+        th = np.asarray(theta, dtype=np.float32).reshape(self.Ht, -1, L.NU)
+        comp = th.transpose(1, 0, 2).reshape(th.shape[1], self.Ht * L.NU)[:, :self.D].astype(np.float64)
+        t = np.fmin(np.fmax(comp, -1.0), 1.0)
+        v = self.lo + (self.hi - self.lo) * (0.5 * (t + 1.0))
+        return {n: v[:, i].copy() for i, n in enumerate(self.names)}
+
+
+class RuleSearch:
+    """Closed-loop rollouts of the rule-based controller, and the tuning of its constants by the cross-entropy method, on the device
+    (TomatoVecEnv.rule_search).  A candidate is not a control sequence but a FEEDBACK LAW: a row of K per greenhouse of the float32 block
+    theta [Ht, B*K, 6], Ht = ceil(D / 6), which decodes to the D tuned constants (RuleParams; the others come from `base`).  rollout()
+    forks the environment's greenhouses into B*K children (x S scenarios) and runs controller -> env-step -> accumulate for `horizon`
+    steps in one library call (glgym_plan_rollout_rule): the control of step h is computed from the child's own state after step h-1.
+
+    A Planner (self.plan) owns the children's buffers, the fork, the accumulators, the scenarios and the weather windows; n_scenarios,
+    n_tail, noise, noise_scale, scenario_seed, weather_sigma and weather_phi are its.  theta has the layout of an action block of
+    horizon Ht, so sample / elites / refit / select are the Planner's library stages called with H = Ht (no correlation along "the
+    horizon": beta = 0).
+
+    Limits.  dt must be a multiple of 450 s (check_rule_dt): the children's clocks are derived by the product form.  The steps are
+    raw-control steps: under the default verify mode "auto" they run verified (TomatoVecEnv.set_verify).  The environment is only read."""
+
+    SCENARIO_KEYS = ("n_scenarios", "n_tail", "noise", "noise_scale", "scenario_seed", "weather_sigma", "weather_phi")
+
+    def __init__(self, env, n_candidates: int, horizon: int, tune, base=None, gamma: float = 1.0, **scenario_kwargs):
+        unknown = sorted(set(scenario_kwargs) - set(self.SCENARIO_KEYS))
+        if unknown:
+            raise TypeError(f"unexpected arguments {unknown}; the scenario arguments are {self.SCENARIO_KEYS}")
+        check_rule_dt(env.dt)
+        self.params = RuleParams(tune, base)
+        self.base = self.params.base
+        self.plan = p = Planner(env, n_candidates, horizon, gamma=gamma, crop="nominal", **scenario_kwargs)
+        self.env, self.torch = env, env.torch
+        torch, dev = env.torch, env.device
+        self.B, self.K, self.H, self.J, self.C, self.S = p.B, p.K, p.H, p.J, p.C, p.S
+        self.D, self.Ht, self.names = self.params.D, self.params.Ht, self.params.names
+        self._space = self.params.struct()
+        Ht, B, J = self.Ht, self.B, self.J
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
+        self._lo_t = torch.as_tensor(self.params.lo, device=dev).view(self.D, 1)
+        self._span_t = torch.as_tensor(self.params.hi - self.params.lo, device=dev).view(self.D, 1)
+        self._plane_T = z(1, L.NU, p.ld, dtype=env.tdtype)           # the one control plane of record=False
+        self.controls_T = self.controls = None                       # record=True: [H, 6, ld] and its [H, C, 6] view
+        self._theta_buf = None
+        self._theta = None                                           # the [Ht, J, 6] block of the last rollout
+        self._blocks = [z(Ht, J, L.NU) for _ in range(2)]            # populations: sampled into the one the previous does not occupy
+        self._cur = self._rolled = self._elites = None
+        self.elite_k_t = torch.full((J,), -1, dtype=torch.int32, device=dev)
+        self.n_elite_t = z(B, dtype=torch.int32)
+        self.mean_t, self.std_t = z(Ht, B, L.NU), z(Ht, B, L.NU)
+        self.best_sequence_t = z(Ht, B, L.NU)
+        self.best_theta_t = z(B, Ht * L.NU)
+        self._dec_t = z(B, Ht * L.NU, dtype=torch.float64)
+        self._params_T = z(self.D, B, dtype=torch.float64)
+        self.best_params = {n: self._params_T[i] for i, n in enumerate(self.names)}
+        self._base_theta = torch.as_tensor(self.params.encode(self.base), device=dev) if self.params.inside(self.base) else None
+        self._draw = 0
+        self.scenario_returns = getattr(p, "scenario_returns", None)
+        self.scenario_failed = getattr(p, "scenario_failed", None)
+
+    # ------------------------------------------------------------------------------------------------
+    def encode(self, controller_or_dict):
+        """theta [Ht, 1, 6] f32 on the environment's device of a RuleBasedController (or a dict of constants; missing names come from
+        base): the tuned constants mapped into [-1, 1], padding 0.  ValueError outside the bounds."""
+        return self.torch.as_tensor(self.params.encode(controller_or_dict), device=self.env.device)
+
+    def decode(self, theta_t):
+        """theta_t [Ht, n, 6] -> {name: float64 [n]} on theta_t's device, by the formula of include/glgym.h (a NaN reads as lo)."""
+        torch = self.torch
+        th = theta_t.reshape(self.Ht, -1, L.NU)
+        t = th.permute(1, 0, 2).reshape(th.shape[1], self.Ht * L.NU)[:, :self.D].double()
+        t = torch.nan_to_num(t, nan=-1.0).clamp(-1.0, 1.0)
+        lo, span = self._lo_t.view(-1).to(t.device), self._span_t.view(-1).to(t.device)
+        v = lo + span * (0.5 * (t + 1.0))
+        return {n: v[:, i] for i, n in enumerate(self.names)}
+
+    def theta_of(self, controller_or_dict):
+        """The block [Ht, B*K, 6] in which every candidate is that controller."""
+        return self.encode(controller_or_dict).expand(self.Ht, self.J, L.NU).contiguous()
+
+    def rollout(self, theta_t, record: bool = False):
+        """Fork from the environment's current state and run the closed-loop rollout of every candidate controller.  theta_t holds
+        [Ht, B*K, 6] f32 values (row b*K + k: candidate k of greenhouse b); a contiguous float32 tensor on the environment's device is
+        read in place.  Returns what Planner.rollout returns: returns, alive, steps, violations, failed -- with scenarios the aggregated
+        ones, scenario_returns / scenario_failed [B, K, S] holding the single runs.  record=True keeps the controls of every step:
+        controls_T [H, 6, ld] and controls, its [H, C, 6] view (child c = (b*K + k)*S + s)."""
+        torch, e, p = self.torch, self.env, self.plan
+        n = self.Ht * self.J * L.NU
+        if theta_t.numel() != n:
+            raise ValueError(f"theta_t must hold ceil(D / 6) x (num_envs * n_candidates) x 6 = {n} values, got {tuple(theta_t.shape)}")
+        if theta_t.dtype == torch.float32 and theta_t.is_cuda and theta_t.device == e.device and theta_t.is_contiguous():
+            self._theta = theta_t.view(self.Ht, self.J, L.NU)
+            self._rolled = next((i for i, b in enumerate(self._blocks) if theta_t is b), None)
+        else:
+            if self._theta_buf is None:
+                self._theta_buf = torch.zeros(self.Ht, self.J, L.NU, dtype=torch.float32, device=e.device)
+            self._theta_buf.copy_(theta_t.reshape(self.Ht, self.J, L.NU))
+            self._theta, self._rolled = self._theta_buf, None
+        if record and self.controls_T is None:
+            self.controls_T = torch.zeros(self.H, L.NU, p.ld, dtype=e.tdtype, device=e.device)
+            self.controls = self.controls_T[:, :, :self.C].permute(0, 2, 1)
+        planes = self.controls_T if record else self._plane_T
+        p._actions = p._rolled = None
+        p.fork()
+        if p.weather_window_t is not None:
+            p._weather()
+        a = L.make_plan_args(L.PlanRolloutArgs, self.H, p.gamma, p._step_args(), None, planes.data_ptr(), p.ret_t.data_ptr(),
+                             p.viol_T.data_ptr(), p.n_steps_t.data_ptr(), p.alive_t.data_ptr(), p.failed_t.data_ptr())
+        if self.S:
+            scen = (self.B, self.K, self.S, 1 if p.noise == "hold" else 0, p.noise_scale, p.scenario_seed & (2 ** 64 - 1), p._scen_draw,
+                    p.scenario_base_t.data_ptr())
+        else:
+            scen = (0, 0, 0, 0, 0.0, 0, 0, None)
+        r = L.make_plan_args(L.PlanRolloutRuleArgs, 1 if record else 0, a, self._space, self._theta.data_ptr(), p.start_day_t.data_ptr(),
+                             self.J, *scen)
+        L.check(e._lib.glgym_plan_rollout_rule(e._h, C.byref(r), e._stream()), "glgym_plan_rollout_rule")
+        return p._aggregate() if self.S else p._results()
+
+    def new_scenarios(self):
+        self.plan.new_scenarios()
+
+    # ---- the cross-entropy method over theta: the Planner's library stages with H = Ht ---------------------------------------
+    def _check_dist(self, mean_t, std_t):
+        torch, n = self.torch, self.Ht * self.B * L.NU
+        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
+            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.env.device or not t.is_contiguous()
+                    or t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of ceil(D / 6) x num_envs x 6 = {n} values on the environment's device")
+
+    def sample(self, mean_t, std_t, seed: int = 0, draw_index: int = 0, carry: int = 0):
+        """glgym_plan_sample with H = Ht, beta = 0: the population theta [Ht, B*K, 6] from N(mean_t, std_t) [Ht, B, 6], clipped to
+        [-1, 1], into the block the previous population does not occupy; returns it.  Candidate 0 is the clipped mean; with carry >= 1
+        and elites() of the previous sampled population at hand, candidates 1 .. carry are its best rows."""
+        self._check_dist(mean_t, std_t)
+        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
+            raise ValueError("carry, seed and draw_index must be >= 0")
+        n_elites, src = self._elites or (0, None)
+        carried = int(carry) if src is not None else 0
+        if carried > n_elites:
+            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
+        e = self.env
+        dst = 0 if self._cur is None else 1 - self._cur
+        a = L.make_plan_args(L.PlanSampleArgs, self.B, self.K, self.Ht, mean_t.data_ptr(), std_t.data_ptr(), 0.0,
+                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.plan.draw_base_t.data_ptr(),
+                             self._blocks[dst].data_ptr(), carried, n_elites if carried else 0,
+                             self._blocks[src].data_ptr() if carried else None, self.elite_k_t.data_ptr() if carried else None,
+                             self.n_elite_t.data_ptr() if carried else None)
+        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
+        self._cur = dst
+        self._elites = (n_elites, None) if self._elites else None
+        return self._blocks[dst]
+
+    def elites(self, n_elite: int):
+        """glgym_plan_elites on the last rollout's scores: (elite_k [B, n_elite] i32, n_elite [B] i32), as Planner.elites."""
+        E = int(n_elite)
+        if not 1 <= E <= self.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
+        e, p = self.env, self.plan
+        a = L.make_plan_args(L.PlanElitesArgs, self.B, self.K, E, p._score_t.data_ptr(), p._score_failed_t.data_ptr(),
+                             self.elite_k_t.data_ptr(), self.n_elite_t.data_ptr())
+        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
+        self._elites = (E, self._rolled if self._rolled == self._cur else None)
+        return self.elite_k_t[:self.B * E].view(self.B, E), self.n_elite_t
+
+    def refit(self, mean_t, std_t, alpha: float, min_std: float):
+        """glgym_plan_refit with H = Ht, in place on mean_t / std_t [Ht, B, 6], over the elites() of the last rollout's theta."""
+        self._check_dist(mean_t, std_t)
+        if not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf"):
+            raise ValueError("min_std must be finite and >= 0")
+        if self._theta is None or self._elites is None:
+            raise ValueError("refit needs a rollout and its elites()")
+        e = self.env
+        a = L.make_plan_args(L.PlanRefitArgs, self.B, self.K, self.Ht, self._elites[0], self._theta.data_ptr(), self.elite_k_t.data_ptr(),
+                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
+                             mean_t.data_ptr(), std_t.data_ptr())
+        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
+        return mean_t, std_t
+
+    def select(self) -> Dict[str, Any]:
+        """glgym_plan_select with H = Ht on the last rollout: {"best_k" [B] i32 (-1: every candidate failed), "best_return" [B] f64,
+        "best_theta" [B, Ht*6] f32 (component i of greenhouse b at [b, i]; zeros without an admissible candidate), "best_params"
+        {name: [B] f64}}.  Device tensors, overwritten by the next call; no allocation."""
+        if self._theta is None:
+            raise ValueError("select needs a rollout")
+        e, p = self.env, self.plan
+        a = L.make_plan_args(L.PlanSelectArgs, self.B, self.K, self.Ht, p._score_t.data_ptr(), p._score_failed_t.data_ptr(),
+                             self._theta.data_ptr(), p.best_k_t.data_ptr(), p.best_ret_t.data_ptr(), None,
+                             self.best_sequence_t.data_ptr(), 0.0, None)
+        L.check(e._lib.glgym_plan_select(e._h, C.byref(a), e._stream()), "glgym_plan_select")
+        self.best_theta_t.view(self.B, self.Ht, L.NU).copy_(self.best_sequence_t.permute(1, 0, 2))
+        # the header's decode with in-place operations: t = clamp, half = 0.5 * (t + 1), v = lo + span * half
+        d = self._dec_t
+        d.copy_(self.best_theta_t)
+        d.nan_to_num_(nan=-1.0).clamp_(-1.0, 1.0).add_(1.0).mul_(0.5)
+        self.torch.mul(d[:, :self.D].t(), self._span_t, out=self._params_T)
+        self._params_T.add_(self._lo_t)
+        return {"best_k": p.best_k_t, "best_return": p.best_ret_t, "best_theta": self.best_theta_t, "best_params": self.best_params}
+
+    def cem(self, n_iter: int, n_elite: int, init_std: float = 0.5, min_std: float = 0.05, alpha: float = 0.1, carry: int = 0,
+            seed: int = 0, mean=None) -> Dict[str, Any]:
+        """Tune the controller: n_iter x (sample -> rollout -> elites -> refit), then select() on the last population.  mean None:
+        start from encode(base) where base lies inside the bounds, else from 0 (the middle of every interval); otherwise from `mean`
+        [Ht, B, 6] or [Ht, 1, 6].  The spread starts at init_std (theta units: the half-width of an interval is 1).  carry <= n_elite
+        elites survive from one population into the next; nothing is carried into the first.  Every sample() takes the next draw index
+        of this object's lifetime.
+        Returns device tensors, overwritten by the next call: best_theta [B, Ht*6], best_params {name: [B]}, best_return, best_k,
+        mean, std [Ht, B, 6], elite_k [B, n_elite], n_elite [B].  No host synchronisation and, after the first call, no allocation: a
+        whole cem() can be captured in a graph (add n_iter to plan.draw_base_t between replays for fresh noise)."""
+        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
+        if n_iter < 1:
+            raise ValueError("n_iter must be at least 1")
+        if not 1 <= E <= self.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
+        if not 0 <= carry <= E:
+            raise ValueError("carry must be in 0 .. n_elite")
+        if not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
+            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
+        if mean is not None:
+            if mean.numel() not in (self.Ht * L.NU, self.Ht * self.B * L.NU):
+                raise ValueError(f"mean must hold ceil(D / 6) x (1 or num_envs) x 6 values, got {tuple(mean.shape)}")
+            self.mean_t.copy_(mean.reshape(self.Ht, -1, L.NU))
+        elif self._base_theta is not None:
+            self.mean_t.copy_(self._base_theta)
+        else:
+            self.mean_t.zero_()
+        self.std_t.fill_(float(init_std))
+        self._elites = None
+        for _ in range(n_iter):
+            block = self.sample(self.mean_t, self.std_t, seed=seed, draw_index=self._draw, carry=carry)
+            self._draw += 1
+            self.rollout(block)
+            elite_k, n_el = self.elites(E)
+            self.refit(self.mean_t, self.std_t, alpha, min_std)
+        sel = self.select()
+        return {"best_theta": sel["best_theta"], "best_params": sel["best_params"], "best_return": sel["best_return"], "best_k": sel["best_k"],
+                "mean": self.mean_t, "std": self.std_t, "elite_k": elite_k, "n_elite": n_el}
+
+    def best_controller(self, b: int = 0):
+        """The RuleBasedController of greenhouse b's best candidate of the last select() / cem(): base with the tuned constants
+        replaced.  Synchronises (reads the device)."""
+        from .baseline import RULE_BASED_DEFAULTS, RuleBasedController
+        if not 0 <= int(b) < self.B:
+            raise ValueError(f"b must be in 0 .. {self.B - 1}")
+        cfg = {n: getattr(self.base, n) for n in RULE_BASED_DEFAULTS}
+        vals = self._params_T[:, int(b)].cpu().numpy()
+        cfg.update({n: float(vals[i]) for i, n in enumerate(self.names)})
+        return RuleBasedController(**cfg)

@@ -458,6 +458,15 @@ class TomatoVecEnv:
         from .planner import Planner
         return Planner(self, n_candidates, horizon, gamma=gamma, crop=crop, **scenarios)
 
+    def rule_search(self, n_candidates: int, horizon: int, tune, base=None, gamma: float = 1.0, **scenario_kwargs):
+        """A gl_gym_amd.planner.RuleSearch for this environment: closed-loop rollouts of n_candidates rule-based controllers per
+        environment over `horizon` env-steps on forked copies, and the tuning of the constants named in tune = {name: (lo, hi), ...}
+        by the cross-entropy method; the other constants come from `base` (default RuleBasedController()).  The scenario arguments of
+        planner() (n_scenarios, n_tail, noise, noise_scale, scenario_seed, weather_sigma, weather_phi) make the tuning robust to crop
+        noise and forecast error.  Needs dt to be a multiple of 450 s (planner.check_rule_dt)."""
+        from .planner import RuleSearch
+        return RuleSearch(self, n_candidates, horizon, tune, base=base, gamma=gamma, **scenario_kwargs)
+
     def _launch_reset(self, mask_t):
         """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).
         rng="numpy": glgym_rng_reset_draw takes choice(years), choice(days) from each masked environment's stream first, and

@@ -163,7 +163,7 @@ typedef struct {
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
- * glgym_plan_weather */
+ * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -722,6 +722,73 @@ typedef struct {
 } glgym_rule_args;
 
 int glgym_rule_based(glgym_handle h, const glgym_rule_cfg* cfg, const glgym_rule_args* a, void* stream);
+
+/* ---- closed-loop rule-based rollouts: per-row controller constants, controller tuning (csrc/gl_rule.hpp, csrc/glgym_plan.hip) ----
+ * The planning section above simulates OPEN-LOOP candidates, given as action or control blocks.  Here a candidate is a FEEDBACK LAW:
+ * the rule-based controller with constants of its own, evaluated on the child's present state before every env-step of the horizon.
+ * This section belongs to the planning section (it stands here because it needs glgym_rule_cfg and glgym_rule_args) and keeps its
+ * conventions: struct_size first, every refusal GLGYM_EINVAL with a message before anything is launched, asynchronous on `stream`,
+ * no allocation, no host synchronisation (capturable), plain vector stores, no atomics.  Opt-in: no other entry point changes.
+ *
+ * Search space.  D of the 29 constants are tuned: component i < D is constant number field[i] of glgym_rule_cfg read as double[29]
+ * in declaration order (all distinct), between lo[i] and hi[i]; the others come from `base`.  Candidate parameters are a float32
+ * block theta [Ht][J][6], Ht = ceil(D / 6): component i of row j is theta[i / 6][j][i % 6]; the padding entries are ignored.  That is
+ * the block glgym_plan_sample / _elites / _refit / _select draw, rank, refit and pick when they are called with H = Ht.
+ * Decode, in double with products and sums rounded separately: t = fmin(fmax((double)theta_i, -1.0), 1.0); v = lo_i + (hi_i - lo_i) *
+ * (0.5 * (t + 1.0)).  A NaN theta reads as -1, i.e. lo (fmax / fmin return the other operand): a NaN control never reaches a step.
+ * Refused: D outside 1..29, a field index outside 0..28 or given twice, a non-finite lo or hi, lo > hi, a tuned proportional band
+ * (vent_heat_Pband, vent_rh_Pband, vent_cold_Pband, thScrPband, thScrRhPband, tHeatBand, co2Band) whose interval contains 0
+ * (lo <= 0 <= hi), and an untuned band that is 0 in base (as glgym_rule_based refuses it). */
+typedef struct {
+    glgym_rule_cfg base;
+    int32_t D;                   /* 1 .. 29 */
+    int32_t field[29];
+    double lo[29];
+    double hi[29];
+} glgym_rule_space;
+
+/* glgym_rule_based with per-row constants: row b < B takes the constants decoded from row b / max(S, 1) of theta (S = 0 or 1: its
+ * own row; S >= 2: the S scenario children of a candidate share one).  Needs B <= J * max(S, 1).  One thread per row, blocks of 256;
+ * rows B .. ld-1 of `control` are not written.  The rules are those of glgym_rule_based, in fp64 for either handle dtype; the
+ * comparisons between lamps_on / lamps_off and lamps_day_start / lamps_day_stop are taken per row. */
+typedef struct {
+    int32_t struct_size;
+    int32_t J;                   /* rows of theta (>= 1) */
+    int32_t S;                   /* 0 .. 256 */
+    glgym_rule_args rule;        /* as for glgym_rule_based: x, weather, clocks (hour / doy optional), control out */
+    glgym_rule_space space;
+    const float* theta;          /* [Ht][J][6] f32 */
+} glgym_rule_rows_args;
+
+/* H CLOSED-LOOP env-steps of the children.  For h = 0 .. H-1: with S >= 1 glgym_plan_scenario at step h (crop blocks only, no action
+ * plane); the rows kernel above on the children's present x, timestep and w_off with rollout.step.weather / weather_rows (the row
+ * about to be integrated; clocks derived from timestep and start_day), into plane (record ? h : 0) of rollout.controls; glgym_step
+ * with control = that plane and metrics = NULL; glgym_plan_accumulate with the running-product weight.  rollout.actions must be NULL
+ * and rollout.controls is the plane buffer, record ? H : 1 planes of SoA [6][ld] T, WRITTEN by this call (rows step.B .. ld-1 of a
+ * plane are not).  S = 0: no scenarios, rollout.step.B <= J, child c reads theta row c (P, K, hold, scale, seed, draw_index, draw_base
+ * are ignored).  1 <= S <= 256: rollout.step.B == P*K*S, J == P*K, rollout.step.crop_p is required and child c reads theta row
+ * c / S.  H >= 1 (with S >= 1 also H <= 65 536) and gamma as for glgym_plan_rollout.  The handle's verify mode, scheme, n_sub and
+ * integrator apply as they do to any raw-control step (under GLGYM_VERIFY_AUTO a raw-control step runs verified); what glgym_step
+ * refuses without launching (GLGYM_ODE_PIPE with a crop block or another scheme than RK4, a BDF glgym_evalF setting on explicit
+ * steps) is refused here in its words before the first launch. */
+typedef struct {
+    int32_t struct_size;
+    int32_t record;              /* 0: one control plane, overwritten at every step; 1: H planes, plane h = the controls of step h */
+    glgym_plan_rollout_args rollout;
+    glgym_rule_space space;
+    const float* theta;          /* [Ht][J][6] f32 */
+    const float* start_day;      /* [step.B]: the children's (glgym_plan_fork writes it) */
+    int32_t J;
+    int32_t P, K, S;             /* as glgym_plan_rollout_scenarios_args; S = 0: no scenarios */
+    int32_t hold;
+    double scale;
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;
+} glgym_plan_rollout_rule_args;
+
+int glgym_rule_rows(glgym_handle h, const glgym_rule_rows_args* a, void* stream);
+int glgym_plan_rollout_rule(glgym_handle h, const glgym_plan_rollout_rule_args* a, void* stream);
 
 /* ---- on-device VecNormalize ---------------------------------------------------------------------
  * Replaces stable_baselines3.common.vec_env.VecNormalize (3rd party, pinned ==2.6.0 in the reference's requirements.txt)
