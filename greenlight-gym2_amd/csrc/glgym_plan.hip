@@ -37,12 +37,22 @@
 // tests/rulehost/rulehost.cpp).  rows: lane = row, the rule-based controller with the row's own 29 constants, decoded from its row of
 // the candidates' parameter block.  The rollout is rollout_steps with that kernel (after the scenario prologue, if any) in front of
 // every env-step, writing the control plane the step then reads.
+//
+// Closed-loop neural-policy rollouts (glgym_policy_rows / glgym_plan_rollout_policy; scalar logic in gl_mlp.hpp, instantiated on the host
+// by tests/mlphost/mlphost.cpp).  rows: lane = row, one wavefront per block, the MLP with the row's own weights.  A lane's activations
+// live in LDS as [neuron][lane] -- a wavefront's access to one neuron is 64 consecutive floats, conflict-free, and no lane ever reads
+// another lane's column, so there is no barrier -- in two buffers sized by the net (at most 2 x 64 x 64 floats = 32 KB); nothing is
+// indexed by a run-time value in registers, so there is no scratch.  Weights are read once, in the order of the flat parameter vector:
+// 6 consecutive floats per lane and plane, neighbouring rows adjacent, lanes that share a row one address, four planes in flight; the walk (gl_mlp.hpp dot)
+// is the same for all lanes and stays in scalar registers.  The rollout is rollout_steps with glgym_obs and that kernel (after the
+// scenario prologue, if any) in front of every env-step, writing the action plane the step then reads.
 #include <cmath>
 #include <string>
 
 #include "glgym_internal.h"
 
 #include "gl_cem.hpp"
+#include "gl_mlp.hpp"
 #include "gl_plan.hpp"
 #include "gl_rule.hpp"
 #include "gl_scen.hpp"
@@ -371,6 +381,24 @@ __global__ __launch_bounds__(256) void rule_rows_kernel(glrule::Space sp, const 
     for (int i = 0; i < NU; ++i) control[(size_t)i * ld + b] = (T)u[i];
 }
 
+// grid = ceil(B / 64) blocks of one wavefront, lane = row b; dynamic LDS = 2 * rows * 64 floats, rows = glmlp::buffer_rows(net).  Float k
+// of buffer `which` of this lane is lds[(which * rows + k) * 64 + lane].  No barrier: a lane touches its own column only.
+__global__ __launch_bounds__(WAVE) void policy_rows_kernel(glgym_mlp_net net, int rows, const float* __restrict__ obs,
+                                                           const float* __restrict__ theta, int J, int S, int mode, int B,
+                                                           float* __restrict__ action)
+{
+    extern __shared__ float policy_lds[];
+    const int b = blockIdx.x * WAVE + threadIdx.x;
+    if (b >= B) return;
+    float* mine = policy_lds + threadIdx.x;
+    auto buf = [mine, rows](int which, int k) -> float& { return mine[(which * rows + k) * WAVE]; };
+    const int j = glmlp::policy_row(b, S, J, mode);
+    float a[NU];
+    glmlp::forward(net, obs + (size_t)b * (size_t)net.in_dim, theta + (size_t)j * NU, (size_t)J * NU, buf, a);
+#pragma unroll
+    for (int i = 0; i < NU; ++i) action[(size_t)b * NU + i] = a[i];
+}
+
 }  // namespace
 
 // The loop of glgym_plan_rollout and glgym_plan_rollout_scenarios: per horizon step k the caller's prologue(k) -- it points s at the step's
@@ -664,6 +692,14 @@ static bool rule_space_ok(const char* who, const glgym_rule_space* sp)
     return !why;
 }
 
+// what glgym_step refuses without launching, for a block whose B, ld, reward, done and action / control the caller has checked
+static bool step_refuses(glgym_handle h, const glgym_step_args& s)
+{
+    const bool pipe = h->variant == GLGYM_ODE_PIPE, bdf = h->step_integrator == GLGYM_INTEGRATOR_BDF;
+    return s.struct_size != (int32_t)sizeof s || !s.x || !s.u || !s.weather || !s.w_off || !s.timestep || s.weather_rows < 1 ||
+           (bdf ? pipe : (h->integrator != GLGYM_INTEGRATOR_EXPLICIT || (pipe && (s.crop_p || h->scheme != GLGYM_SCHEME_RK4))));
+}
+
 // the launch behind both entry points: arguments already checked
 static int launch_rule_rows(glgym_handle h, const glrule::Space& sp, const float* theta, int J, int S, const glgym_rule_args& r, hipStream_t st)
 {
@@ -740,9 +776,7 @@ int glgym_plan_rollout_rule(glgym_handle h, const glgym_plan_rollout_rule_args* 
     // what glgym_step refuses without launching is refused by it, in its own words, before the first prologue is launched: a struct
     // or pointer it checks itself, GLGYM_ODE_PIPE with a crop block, another scheme than RK4 or the BDF step integrator, a BDF
     // glgym_evalF setting on explicit steps
-    const bool pipe = h->variant == GLGYM_ODE_PIPE, bdf = h->step_integrator == GLGYM_INTEGRATOR_BDF;
-    if (s.struct_size != (int32_t)sizeof s || !s.x || !s.u || !s.weather || !s.w_off || !s.timestep || s.weather_rows < 1 ||
-        (bdf ? pipe : (h->integrator != GLGYM_INTEGRATOR_EXPLICIT || (pipe && (s.crop_p || h->scheme != GLGYM_SCHEME_RK4))))) {
+    if (step_refuses(h, s)) {
         const int rc = glgym_step(h, &s, stream);
         if (rc != GLGYM_OK) return rc;
         g_err = "glgym_plan_rollout_rule: glgym_step accepted a call it was expected to refuse";        // unreachable
@@ -765,6 +799,126 @@ int glgym_plan_rollout_rule(glgym_handle h, const glgym_plan_rollout_rule_args* 
         rule.control = (char*)const_cast<void*>(r.controls) + (a->record ? (size_t)k * plane : 0);
         s.control = rule.control;
         return launch_rule_rows(h, sp, a->theta, a->J, a->S, rule, (hipStream_t)stream);
+    });
+}
+
+// closed-loop neural-policy rollouts (gl_mlp.hpp): checked before the handle is looked at, like the entry points above
+static bool policy_net_ok(const char* who, const glgym_mlp_net* net)
+{
+    const char* why = glmlp::net_error(net);
+    if (why) g_err = std::string(who) + ": bad net (" + why + ")";
+    return !why;
+}
+
+// S, the row mode and J against the B rows that read theta
+static bool policy_rows_ok(const char* who, int32_t B, int32_t J, int32_t S, int32_t mode)
+{
+    if (S < 0 || S > 256) { g_err = std::string(who) + ": S outside 0 .. 256"; return false; }
+    if (B > INT32_MAX - (WAVE - 1)) {                            // the last block's lane indices must not wrap
+        g_err = std::string(who) + ": more than 2^31 - 64 rows";
+        return false;
+    }
+    if (mode != GLGYM_POLICY_ROW_CHILD && mode != GLGYM_POLICY_ROW_CANDIDATE) {
+        g_err = std::string(who) + ": row_mode is not GLGYM_POLICY_ROW_CHILD or _CANDIDATE";
+        return false;
+    }
+    if (J < 1 || (mode == GLGYM_POLICY_ROW_CHILD && (int64_t)B > (int64_t)J * (S > 1 ? S : 1))) {
+        g_err = std::string(who) + ": J < 1, or in CHILD mode more rows than parameters (B > J * max(S, 1))";
+        return false;
+    }
+    return true;
+}
+
+// the launch behind both entry points: arguments already checked
+static int launch_policy_rows(glgym_handle h, const glgym_mlp_net& net, const float* obs, const float* theta, int J, int S, int mode, int B,
+                              float* action, hipStream_t st)
+{
+    DeviceGuard dev_guard(h);
+    const int rows = glmlp::buffer_rows(net);
+    const size_t lds = (size_t)2 * rows * WAVE * sizeof(float);
+    hipLaunchKernelGGL(policy_rows_kernel, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), lds, st, net, rows, obs, theta, J, S, mode, B, action);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_policy_rows(glgym_handle h, const glgym_policy_rows_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_policy_rows: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_policy_rows", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!policy_net_ok("glgym_policy_rows", &a->net)) return GLGYM_EINVAL;
+    if (!a->obs || !a->theta || !a->action) { g_err = "glgym_policy_rows: null obs, theta or action"; return GLGYM_EINVAL; }
+    if (a->B < 1) { g_err = "glgym_policy_rows: B < 1"; return GLGYM_EINVAL; }
+    if (!policy_rows_ok("glgym_policy_rows", a->B, a->J, a->S, a->row_mode)) return GLGYM_EINVAL;
+    if (!h) { g_err = "glgym_policy_rows: null handle"; return GLGYM_EINVAL; }
+    return launch_policy_rows(h, a->net, a->obs, a->theta, a->J, a->S, a->row_mode, a->B, a->action, (hipStream_t)stream);
+}
+
+int glgym_plan_rollout_policy(glgym_handle h, const glgym_plan_rollout_policy_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_rollout_policy: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_rollout_policy", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    const glgym_plan_rollout_args& r = a->rollout;
+    if (!plan_size_ok("glgym_plan_rollout_policy: rollout", r.struct_size, sizeof r)) return GLGYM_EINVAL;
+    if (!policy_net_ok("glgym_plan_rollout_policy", &a->net)) return GLGYM_EINVAL;
+    if (r.actions || r.controls) {
+        g_err = "glgym_plan_rollout_policy: the policy makes the actions (rollout.actions and rollout.controls must be NULL)";
+        return GLGYM_EINVAL;
+    }
+    if (!a->theta || !a->obs || !a->actions) { g_err = "glgym_plan_rollout_policy: null theta, obs or actions"; return GLGYM_EINVAL; }
+    if (a->record != 0 && a->record != 1) { g_err = "glgym_plan_rollout_policy: record must be 0 or 1"; return GLGYM_EINVAL; }
+    if (r.H < 1 || !(r.gamma >= 0.0) || !std::isfinite(r.gamma)) {
+        g_err = "glgym_plan_rollout_policy: H < 1, or gamma negative or not finite";
+        return GLGYM_EINVAL;
+    }
+    if (a->Np < 0 || a->Np > OBS_MAX_NP) { g_err = "glgym_plan_rollout_policy: Np outside 0 .. 128"; return GLGYM_EINVAL; }
+    glgym_step_args s = r.step;
+    if (s.B < 1 || s.ld < s.B) { g_err = "glgym_plan_rollout_policy: step.B < 1 or step.ld < step.B"; return GLGYM_EINVAL; }
+    if (!policy_rows_ok("glgym_plan_rollout_policy", s.B, a->J, a->S, a->row_mode)) return GLGYM_EINVAL;
+    if (a->S >= 1 && (!scenario_shape_ok(a->P, a->K, a->S, a->hold, a->scale) || r.H > 65536 || (int64_t)s.B != (int64_t)a->P * a->K * a->S ||
+                      (int64_t)a->J != (a->row_mode == GLGYM_POLICY_ROW_CHILD ? (int64_t)a->P * a->K : (int64_t)a->K) || !s.crop_p)) {
+        g_err = "glgym_plan_rollout_policy: with scenarios P, K >= 1, hold 0 | 1, scale finite and >= 0, H <= 65 536, step.B == P*K*S, "
+                "J == P*K (CHILD mode) or K (CANDIDATE mode) and a crop block (step.crop_p) are needed";
+        return GLGYM_EINVAL;
+    }
+    if (!a->start_day || !s.reward || !s.info || !s.done || !r.ret || !r.viol || !r.n_steps || !r.alive || !r.failed) {
+        g_err = "glgym_plan_rollout_policy: null start_day / reward / info / done / accumulators";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_rollout_policy: null handle"; return GLGYM_EINVAL; }
+    const int dim = glgym_obs_dim(h, a->Np);
+    if (dim != a->net.in_dim) {
+        g_err = "glgym_plan_rollout_policy: net.in_dim is " + std::to_string(a->net.in_dim) + ", the handle's observation row at Np = " +
+                std::to_string(a->Np) + " has " + std::to_string(dim) + " columns (glgym_obs_dim)";
+        return GLGYM_EINVAL;
+    }
+    const size_t plane = (size_t)NU * (size_t)s.B;               // floats per action plane
+    s.metrics = nullptr;
+    s.control = nullptr;
+    s.action = a->actions;
+    // what glgym_step refuses without launching is refused by it, in its own words, before the first prologue is launched
+    if (step_refuses(h, s)) {
+        const int rc = glgym_step(h, &s, stream);
+        if (rc != GLGYM_OK) return rc;
+        g_err = "glgym_plan_rollout_policy: glgym_step accepted a call it was expected to refuse";      // unreachable
+        return GLGYM_EINVAL;
+    }
+    glgym_obs_args ob;
+    ob.B = s.B; ob.ld = s.ld; ob.x = s.x; ob.u = s.u; ob.weather = s.weather; ob.weather_rows = s.weather_rows; ob.w_off = s.w_off;
+    ob.timestep = s.timestep; ob.start_day = a->start_day; ob.Np = a->Np; ob.obs = a->obs; ob.mask = nullptr; ob.term_obs = nullptr;
+    glgym_plan_scenario_args sc;
+    sc.struct_size = (int32_t)sizeof sc;
+    sc.P = a->P; sc.K = a->K; sc.S = a->S; sc.ld = s.ld; sc.hold = a->hold; sc.scale = a->scale; sc.seed = a->seed;
+    sc.draw_index = a->draw_index; sc.draw_base = a->draw_base; sc.crop = (void*)s.crop_p; sc.actions_in = nullptr; sc.actions_out = nullptr;
+    return rollout_steps(h, s, r, stream, [&](int k) {
+        int rc;
+        if (a->S >= 1) {
+            sc.h_step = k;
+            if ((rc = glgym_plan_scenario(h, &sc, stream)) != GLGYM_OK) return rc;
+        }
+        if ((rc = glgym_obs(h, &ob, stream)) != GLGYM_OK) return rc;
+        float* act = a->actions + (a->record ? (size_t)k * plane : 0);
+        s.action = act;
+        return launch_policy_rows(h, a->net, a->obs, a->theta, a->J, a->S, a->row_mode, s.B, act, (hipStream_t)stream);
     });
 }
 

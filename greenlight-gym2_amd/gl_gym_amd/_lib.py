@@ -262,6 +262,30 @@ class PlanRolloutRuleArgs(C.Structure):
                 ("hold", C.c_int32), ("scale", C.c_double), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p)]
 
 
+# closed-loop neural-policy rollouts (include/glgym.h glgym_policy_rows / glgym_plan_rollout_policy)
+MLP_ACTIVATIONS = {"relu": 0, "tanh": 1, "silu": 2}
+MLP_SQUASHES = {"clip": 0, "tanh": 1}
+MLP_MAX_HIDDEN, MLP_MAX_WIDTH, MLP_MAX_IN, MLP_MAX_HT = 3, 64, 1024, 65535
+POLICY_ROW_CHILD, POLICY_ROW_CANDIDATE = 0, 1
+
+
+class MlpNet(C.Structure):
+    _fields_ = [("in_dim", C.c_int32), ("n_hidden", C.c_int32), ("width", C.c_int32 * 3), ("activation", C.c_int32), ("squash", C.c_int32),
+                ("scale", C.c_float * 8), ("clip_obs", C.c_float), ("mean", C.c_void_p), ("inv_std", C.c_void_p)]
+
+
+class PolicyRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("J", C.c_int32), ("S", C.c_int32), ("row_mode", C.c_int32), ("net", MlpNet),
+                ("obs", C.c_void_p), ("theta", C.c_void_p), ("action", C.c_void_p)]
+
+
+class PlanRolloutPolicyArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("record", C.c_int32), ("rollout", PlanRolloutArgs), ("net", MlpNet), ("theta", C.c_void_p),
+                ("start_day", C.c_void_p), ("obs", C.c_void_p), ("actions", C.c_void_p), ("Np", C.c_int32), ("row_mode", C.c_int32),
+                ("J", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("hold", C.c_int32), ("scale", C.c_double),
+                ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p)]
+
+
 class WeatherArgs(C.Structure):
     _fields_ = [("n_raw", C.c_int32), ("time", C.c_void_p), ("i_glob", C.c_void_p), ("t_out", C.c_void_p),
                 ("rh", C.c_void_p), ("wind", C.c_void_p), ("t_sky", C.c_void_p), ("co2_ppm", C.c_double),
@@ -323,6 +347,8 @@ PROTOTYPES = {
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
     "glgym_rule_rows": (C.c_int, [C.c_void_p, C.POINTER(RuleRowsArgs), C.c_void_p]),
     "glgym_plan_rollout_rule": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutRuleArgs), C.c_void_p]),
+    "glgym_policy_rows": (C.c_int, [C.c_void_p, C.POINTER(PolicyRowsArgs), C.c_void_p]),
+    "glgym_plan_rollout_policy": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutPolicyArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),
     "glgym_timer_start": (C.c_int, [C.c_void_p, C.c_void_p]),

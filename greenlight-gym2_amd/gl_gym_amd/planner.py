@@ -34,7 +34,9 @@ n_elite, and repeats; sample(), elites() and refit() are the single stages, shif
 
 Closed-loop candidates (RuleSearch below, glgym_rule_rows / glgym_plan_rollout_rule): every candidate above is an open-loop sequence.
 RuleSearch rolls out a feedback law instead -- the rule-based controller with per-candidate constants, evaluated on each child's own
-state before every step -- and tunes those constants with the same cross-entropy stages."""
+state before every step -- and tunes those constants with the same cross-entropy stages.  PolicySearch (glgym_policy_rows /
+glgym_plan_rollout_policy) does the same with a learned feedback law: an MLP from the child's observation row to the six actions
+(MLPSpec), with per-candidate weights -- scenario evaluation of a trained policy, and CEM over the weights of small nets."""
 from __future__ import annotations
 
 import ctypes as C
@@ -787,3 +789,380 @@ class RuleSearch:
         vals = self._params_T[:, int(b)].cpu().numpy()
         cfg.update({n: float(vals[i]) for i, n in enumerate(self.names)})
         return RuleBasedController(**cfg)
+
+
+# ---- closed-loop neural-policy rollouts and policy search (include/glgym.h glgym_policy_rows / glgym_plan_rollout_policy) -----------
+class MLPSpec:
+    """The shape of an MLP policy on the host -- include/glgym.h glgym_mlp_net: in_dim observations -> hidden layers of the widths in
+    `hidden` (at most 3 of at most 64 neurons; () is a linear policy) -> 6 actions.  activation "relu" | "tanh" | "silu" on the hidden
+    layers, squash "clip" | "tanh" on the outputs (both end in a clip to [-1, 1]).  scale: the value of a parameter is scale[g] *
+    theta, g = 2 l for the weights of layer l and 2 l + 1 for its biases; one number for all groups or a list of 2 (len(hidden) + 1).
+    With scale 1 a trained net loads exactly; with theta sampled in [-1, 1] the scale is the search bound.  obs_norm: None, a
+    VecNormalizeGPU, or (mean, var, epsilon, clip_obs): the input is clip((obs - mean) * inv_std, -clip_obs, clip_obs) with inv_std =
+    1 / sqrt(var + epsilon) computed in double and rounded once to float32.
+
+    The flat parameter vector has D components, layer by layer the weight [out, in] row-major, then the bias [out] -- the order of
+    torch.nn.utils.parameters_to_vector on nn.Sequential(Linear, act, ..., Linear); a block theta is float32 [Ht, J, 6], Ht =
+    ceil(D / 6), component i of row j at theta[i // 6, j, i % 6]."""
+
+    def __init__(self, in_dim: int, hidden=(), activation: str = "tanh", squash: str = "clip", scale=1.0, obs_norm=None):
+        import numpy as np
+        self.np = np
+        self.in_dim, self.hidden = int(in_dim), tuple(int(w) for w in hidden)
+        if not 1 <= self.in_dim <= L.MLP_MAX_IN:
+            raise ValueError(f"in_dim must be in 1 .. {L.MLP_MAX_IN}")
+        if len(self.hidden) > L.MLP_MAX_HIDDEN or any(not 1 <= w <= L.MLP_MAX_WIDTH for w in self.hidden):
+            raise ValueError(f"hidden: at most {L.MLP_MAX_HIDDEN} layers of 1 .. {L.MLP_MAX_WIDTH} neurons")
+        if activation not in L.MLP_ACTIVATIONS:
+            raise ValueError(f"activation must be one of {tuple(L.MLP_ACTIVATIONS)}")
+        if squash not in L.MLP_SQUASHES:
+            raise ValueError(f"squash must be one of {tuple(L.MLP_SQUASHES)}")
+        self.activation, self.squash = activation, squash
+        sizes = (self.in_dim,) + self.hidden + (L.NU,)
+        self.shapes = [(sizes[l + 1], sizes[l]) for l in range(len(sizes) - 1)]          # (out, in) per layer
+        self.n_groups = 2 * len(self.shapes)
+        try:
+            sc = [float(scale)] * self.n_groups
+        except TypeError:
+            sc = [float(v) for v in scale]
+        self.scale = np.asarray(sc, dtype=np.float32)
+        if len(sc) != self.n_groups or not (np.isfinite(self.scale).all() and (self.scale > 0).all()):
+            raise ValueError(f"scale must be one number or {self.n_groups} numbers (weights, biases per layer), finite and > 0")
+        self.D = sum(o * (i + 1) for o, i in self.shapes)
+        self.Ht = (self.D + L.NU - 1) // L.NU
+        if self.Ht > L.MLP_MAX_HT:
+            raise ValueError(f"the net has {self.D} parameters: more than {L.MLP_MAX_HT} planes of 6")
+        self.mean = self.inv_std = None
+        self.clip_obs = 10.0
+        if obs_norm is not None:
+            if hasattr(obs_norm, "obs_mean"):
+                mean, var = obs_norm.obs_mean.detach().cpu().numpy(), obs_norm.obs_var.detach().cpu().numpy()
+                eps, clip = obs_norm.epsilon, obs_norm.clip_obs
+            else:
+                mean, var, eps, clip = obs_norm
+            mean, var = np.asarray(mean, dtype=np.float64).reshape(-1), np.asarray(var, dtype=np.float64).reshape(-1)
+            if mean.shape != (self.in_dim,) or var.shape != (self.in_dim,):
+                raise ValueError(f"obs_norm: mean and var must hold in_dim = {self.in_dim} values")
+            self.mean = mean.astype(np.float32)
+            with np.errstate(invalid="ignore", divide="ignore"):             # a bad variance is refused below, not warned about
+                self.inv_std = (1.0 / np.sqrt(var + float(eps))).astype(np.float32)
+            self.clip_obs = float(np.float32(clip))
+            if not (np.isfinite(self.mean).all() and np.isfinite(self.inv_std).all()):
+                raise ValueError("obs_norm: mean and 1 / sqrt(var + epsilon) must be finite")
+            if not 0.0 < self.clip_obs < float("inf"):
+                raise ValueError("obs_norm: clip_obs must be finite and > 0")
+
+    def struct(self, mean_ptr=None, inv_std_ptr=None):
+        """The glgym_mlp_net; mean_ptr / inv_std_ptr: device pointers of float32 [in_dim] copies of self.mean / self.inv_std."""
+        n = L.MlpNet()
+        n.in_dim, n.n_hidden, n.activation, n.squash = self.in_dim, len(self.hidden), L.MLP_ACTIVATIONS[self.activation], L.MLP_SQUASHES[self.squash]
+        for l, w in enumerate(self.hidden):
+            n.width[l] = w
+        for g in range(8):
+            n.scale[g] = float(self.scale[g]) if g < self.n_groups else 1.0
+        n.clip_obs, n.mean, n.inv_std = self.clip_obs, mean_ptr, inv_std_ptr
+        return n
+
+    def _layers(self, src):
+        """[(W, b)] as float64 arrays from an nn.Sequential of Linear / activation layers, an SB3-style state dict or a list of (W, b)."""
+        np = self.np
+        to_np = lambda t: np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)  # noqa: E731
+        if isinstance(src, dict):
+            n_h, layers = len(self.hidden), []
+            for l in range(n_h):
+                layers.append((src[f"mlp_extractor.policy_net.{2 * l}.weight"], src[f"mlp_extractor.policy_net.{2 * l}.bias"]))
+            layers.append((src["action_net.weight"], src["action_net.bias"]))
+            if f"mlp_extractor.policy_net.{2 * n_h}.weight" in src:
+                raise ValueError("the state dict has more policy layers than the spec")
+        elif hasattr(src, "children"):
+            layers = [(m.weight, m.bias) for m in src.children() if hasattr(m, "weight")]
+        else:
+            layers = list(src)
+        if len(layers) != len(self.shapes):
+            raise ValueError(f"{len(layers)} linear layers given, the spec has {len(self.shapes)}")
+        out = []
+        for l, ((W, b), (o, i)) in enumerate(zip(layers, self.shapes)):
+            if b is None:
+                raise ValueError(f"layer {l} has no bias")
+            W, b = to_np(W), to_np(b)
+            if W.shape != (o, i) or b.shape != (o,):
+                raise ValueError(f"layer {l}: weight {W.shape} / bias {b.shape}, the spec has ({o}, {i}) / ({o},)")
+            out.append((W, b))
+        return out
+
+    def encode(self, module_or_arrays):
+        """-> theta float32 [Ht, 1, 6]: the parameters divided by their group's scale (in double, rounded once), padding 0.  Takes a
+        torch nn.Sequential of Linear / activation layers, an SB3-style state dict (mlp_extractor.policy_net.{2l}.weight | bias,
+        action_net.weight | bias) or a list of (W, b); ValueError where a shape differs from the spec."""
+        np = self.np
+        flat = np.zeros(self.Ht * L.NU, dtype=np.float32)
+        at = 0
+        for l, (W, b) in enumerate(self._layers(module_or_arrays)):
+            for g, v in ((2 * l, W.reshape(-1)), (2 * l + 1, b)):
+                flat[at:at + v.size] = (v / np.float64(self.scale[g])).astype(np.float32)
+                at += v.size
+        return flat.reshape(self.Ht, 1, L.NU)
+
+    def flat(self, theta):
+        """theta [Ht, J, 6] -> [J, D] float32: component i of row j at [j, i]."""
+        np = self.np
+        th = np.asarray(theta, dtype=np.float32).reshape(self.Ht, -1, L.NU)
+        return np.ascontiguousarray(th.transpose(1, 0, 2)).reshape(th.shape[1], self.Ht * L.NU)[:, :self.D]
+
+    def decode(self, theta):
+        """theta [Ht, J, 6] -> [(W [J, out, in], b [J, out])] float32, every parameter scale[g] * theta in float32."""
+        flat, out, at = self.flat(theta), [], 0
+        for l, (o, i) in enumerate(self.shapes):
+            W = (self.scale[2 * l] * flat[:, at:at + o * i]).reshape(-1, o, i)
+            at += o * i
+            b = self.scale[2 * l + 1] * flat[:, at:at + o]
+            at += o
+            out.append((W, b))
+        return out
+
+
+class PolicySearch:
+    """Closed-loop rollouts of MLP policies and gradient-free policy search by the cross-entropy method on the device
+    (TomatoVecEnv.policy_search).  A candidate is a FEEDBACK LAW: a row of the float32 block theta [Ht, J, 6] holding the D parameters
+    of an MLPSpec net.  rollout() forks the environment's greenhouses into B*K children (x S scenarios) and runs observation -> policy
+    -> env-step -> accumulate for `horizon` steps in one library call (glgym_plan_rollout_policy): the action of step h is computed from
+    the child's own observation after step h-1, the observation the environment itself would return.
+
+    share="greenhouse": every greenhouse has K candidates of its own (J = B*K rows, the distribution is [Ht, B, 6]), as RuleSearch.
+    share="all": K policies, each run on all B greenhouses (J = K rows, the distribution is [Ht, 1, 6]); policy k's score is the
+    float64 mean over the greenhouses of its (aggregated) returns, and it counts as failed if any of its children failed.
+
+    A Planner (self.plan) owns the children's buffers, the fork, the accumulators and the scenarios; n_scenarios, n_tail, noise,
+    noise_scale and scenario_seed are its.  theta has the layout of an action block of horizon Ht, so sample / elites / refit / select
+    are the library's CEM stages called with H = Ht (beta = 0).
+
+    Limits.  spec.in_dim must be the environment's observation width.  Weather windows (weather_sigma) are refused: a child on a private
+    window keeps the parent's timestep, and the observation's current-row and forecast indices (w_off + timestep - 1 ...) would leave
+    the window.  The steps are action steps (u <- clip(u + 0.1 a)); the environment is only read."""
+
+    SCENARIO_KEYS = ("n_scenarios", "n_tail", "noise", "noise_scale", "scenario_seed", "weather_sigma", "weather_phi")
+
+    def __init__(self, env, n_candidates: int, horizon: int, spec: MLPSpec, share: str = "greenhouse", gamma: float = 1.0, **scenario_kwargs):
+        unknown = sorted(set(scenario_kwargs) - set(self.SCENARIO_KEYS))
+        if unknown:
+            raise TypeError(f"unexpected arguments {unknown}; the scenario arguments are {self.SCENARIO_KEYS}")
+        if scenario_kwargs.get("weather_sigma") is not None:
+            raise ValueError("policy rollouts do not take weather_sigma: a child on a private weather window keeps the parent's timestep, and "
+                             "the observation's current-row and forecast indices (w_off + timestep - 1 ...) would leave the window")
+        if share not in ("greenhouse", "all"):
+            raise ValueError("share must be 'greenhouse' or 'all'")
+        if not isinstance(spec, MLPSpec):
+            raise TypeError("spec must be an MLPSpec")
+        if spec.in_dim != env.obs_dim:
+            raise ValueError(f"spec.in_dim = {spec.in_dim}, the environment's observations have {env.obs_dim} columns")
+        self.spec, self.share = spec, share
+        self.plan = p = Planner(env, n_candidates, horizon, gamma=gamma, crop="nominal", **scenario_kwargs)
+        self.env, self.torch = env, env.torch
+        torch, dev = env.torch, env.device
+        self.B, self.K, self.H, self.C, self.S = p.B, p.K, p.H, p.C, p.S
+        self.D, self.Ht = spec.D, spec.Ht
+        self.P = self.B if share == "greenhouse" else 1              # distributions: rows of mean / std, calls of the CEM stages
+        self.J = self.P * self.K                                     # rows of theta
+        self.row_mode = L.POLICY_ROW_CHILD if share == "greenhouse" else L.POLICY_ROW_CANDIDATE
+        Ht, P, J = self.Ht, self.P, self.J
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
+        self._mean_t = torch.as_tensor(spec.mean, device=dev) if spec.mean is not None else None
+        self._inv_std_t = torch.as_tensor(spec.inv_std, device=dev) if spec.inv_std is not None else None
+        self._net = spec.struct(self._mean_t.data_ptr() if self._mean_t is not None else None,
+                                self._inv_std_t.data_ptr() if self._inv_std_t is not None else None)
+        self.obs_t = z(self.C, spec.in_dim)                          # the children's observations: the last step's afterwards
+        self._plane_t = z(1, self.C, L.NU)                           # the one action plane of record=False
+        self.actions = None                                          # record=True: [H, C, 6], child c = (b*K + k)*S + s
+        self._theta_buf = None
+        self._theta = None                                           # the [Ht, J, 6] block of the last rollout
+        self._blocks = [z(Ht, J, L.NU) for _ in range(2)]            # populations: sampled into the one the previous does not occupy
+        self._cur = self._rolled = self._elites = None
+        self.elite_k_t = torch.full((J,), -1, dtype=torch.int32, device=dev)
+        self.n_elite_t = z(P, dtype=torch.int32)
+        self.mean_t, self.std_t = z(Ht, P, L.NU), z(Ht, P, L.NU)
+        self.best_k_t, self.best_ret_t = z(P, dtype=torch.int32), z(P, dtype=torch.float64)
+        self.best_sequence_t = z(Ht, P, L.NU)
+        self.best_theta_t = z(P, Ht * L.NU)
+        if share == "all":
+            self.score_t, self.score_failed_t = z(self.K, dtype=torch.float64), z(self.K, dtype=torch.uint8)
+        else:
+            self.score_t, self.score_failed_t = p._score_t, p._score_failed_t
+        self._draw = 0
+        self.scenario_returns = getattr(p, "scenario_returns", None)
+        self.scenario_failed = getattr(p, "scenario_failed", None)
+
+    # ------------------------------------------------------------------------------------------------
+    def encode(self, module_or_arrays):
+        """theta [Ht, 1, 6] f32 on the environment's device of a trained net (MLPSpec.encode)."""
+        return self.torch.as_tensor(self.spec.encode(module_or_arrays), device=self.env.device)
+
+    def rollout(self, theta_t, record: bool = False):
+        """Fork from the environment's current state and run the closed-loop rollout of every candidate policy.  theta_t holds
+        [Ht, J, 6] f32 values (share="greenhouse": row b*K + k is candidate k of greenhouse b; share="all": row k is policy k); a
+        contiguous float32 tensor on the environment's device is read in place.  Returns what Planner.rollout returns -- returns,
+        alive, steps, violations, failed, [B, K] per (greenhouse, candidate) in either share mode -- with scenarios the aggregated ones,
+        scenario_returns / scenario_failed [B, K, S] holding the single runs.  With share="all" score_t / score_failed_t [K] hold the
+        policies' scores afterwards.  record=True keeps the actions of every step: actions [H, C, 6] (child c = (b*K + k)*S + s)."""
+        torch, e, p = self.torch, self.env, self.plan
+        n = self.Ht * self.J * L.NU
+        if theta_t.numel() != n:
+            raise ValueError(f"theta_t must hold ceil(D / 6) x {self.J} x 6 = {n} values, got {tuple(theta_t.shape)}")
+        if theta_t.dtype == torch.float32 and theta_t.is_cuda and theta_t.device == e.device and theta_t.is_contiguous():
+            self._theta = theta_t.view(self.Ht, self.J, L.NU)
+            self._rolled = next((i for i, b in enumerate(self._blocks) if theta_t is b), None)
+        else:
+            if self._theta_buf is None:
+                self._theta_buf = torch.zeros(self.Ht, self.J, L.NU, dtype=torch.float32, device=e.device)
+            self._theta_buf.copy_(theta_t.reshape(self.Ht, self.J, L.NU))
+            self._theta, self._rolled = self._theta_buf, None
+        if record and self.actions is None:
+            self.actions = torch.zeros(self.H, self.C, L.NU, dtype=torch.float32, device=e.device)
+        planes = self.actions if record else self._plane_t
+        p._actions = p._rolled = None
+        p.fork()
+        a = L.make_plan_args(L.PlanRolloutArgs, self.H, p.gamma, p._step_args(), None, None, p.ret_t.data_ptr(), p.viol_T.data_ptr(),
+                             p.n_steps_t.data_ptr(), p.alive_t.data_ptr(), p.failed_t.data_ptr())
+        if self.S:
+            scen = (self.B, self.K, self.S, 1 if p.noise == "hold" else 0, p.noise_scale, p.scenario_seed & (2 ** 64 - 1), p._scen_draw,
+                    p.scenario_base_t.data_ptr())
+        else:
+            scen = (0, 0, 0, 0, 0.0, 0, 0, None)
+        r = L.make_plan_args(L.PlanRolloutPolicyArgs, 1 if record else 0, a, self._net, self._theta.data_ptr(), p.start_day_t.data_ptr(),
+                             self.obs_t.data_ptr(), planes.data_ptr(), e.Np, self.row_mode, self.J, *scen)
+        L.check(e._lib.glgym_plan_rollout_policy(e._h, C.byref(r), e._stream()), "glgym_plan_rollout_policy")
+        out = p._aggregate() if self.S else p._results()
+        if self.share == "all":
+            torch.mean(out[0], dim=0, out=self.score_t)
+            torch.amax(out[4], dim=0, out=self.score_failed_t)
+        return out
+
+    def evaluate(self, theta_row, record: bool = False):
+        """Run ONE policy, theta_row [Ht, 1, 6] (Ht * 6 values), as every candidate of every greenhouse: with scenarios the evaluation
+        of a trained policy under crop noise.  Returns what rollout() returns."""
+        if theta_row.numel() != self.Ht * L.NU:
+            raise ValueError(f"theta_row must hold ceil(D / 6) x 6 = {self.Ht * L.NU} values, got {tuple(theta_row.shape)}")
+        row = theta_row.to(device=self.env.device, dtype=self.torch.float32).reshape(self.Ht, 1, L.NU)
+        return self.rollout(row.expand(self.Ht, self.J, L.NU).contiguous(), record=record)
+
+    def new_scenarios(self):
+        self.plan.new_scenarios()
+
+    # ---- the cross-entropy method over theta: the library's stages with H = Ht, P = B or 1 -----------------------------------
+    def _check_dist(self, mean_t, std_t):
+        torch, n = self.torch, self.Ht * self.P * L.NU
+        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
+            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.env.device or not t.is_contiguous()
+                    or t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of ceil(D / 6) x {self.P} x 6 = {n} values on the environment's device")
+
+    def sample(self, mean_t, std_t, seed: int = 0, draw_index: int = 0, carry: int = 0):
+        """glgym_plan_sample with H = Ht, beta = 0: the population theta [Ht, J, 6] from N(mean_t, std_t) [Ht, P, 6], clipped to
+        [-1, 1], into the block the previous population does not occupy; returns it.  Candidate 0 is the clipped mean; with carry >= 1
+        and elites() of the previous sampled population at hand, candidates 1 .. carry are its best rows."""
+        self._check_dist(mean_t, std_t)
+        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
+            raise ValueError("carry, seed and draw_index must be >= 0")
+        n_elites, src = self._elites or (0, None)
+        carried = int(carry) if src is not None else 0
+        if carried > n_elites:
+            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
+        e = self.env
+        dst = 0 if self._cur is None else 1 - self._cur
+        a = L.make_plan_args(L.PlanSampleArgs, self.P, self.K, self.Ht, mean_t.data_ptr(), std_t.data_ptr(), 0.0,
+                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.plan.draw_base_t.data_ptr(),
+                             self._blocks[dst].data_ptr(), carried, n_elites if carried else 0,
+                             self._blocks[src].data_ptr() if carried else None, self.elite_k_t.data_ptr() if carried else None,
+                             self.n_elite_t.data_ptr() if carried else None)
+        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
+        self._cur = dst
+        self._elites = (n_elites, None) if self._elites else None
+        return self._blocks[dst]
+
+    def elites(self, n_elite: int):
+        """glgym_plan_elites on the last rollout's scores: (elite_k [P, n_elite] i32, n_elite [P] i32), as Planner.elites."""
+        E = int(n_elite)
+        if not 1 <= E <= self.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
+        e = self.env
+        a = L.make_plan_args(L.PlanElitesArgs, self.P, self.K, E, self.score_t.data_ptr(), self.score_failed_t.data_ptr(),
+                             self.elite_k_t.data_ptr(), self.n_elite_t.data_ptr())
+        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
+        self._elites = (E, self._rolled if self._rolled == self._cur else None)
+        return self.elite_k_t[:self.P * E].view(self.P, E), self.n_elite_t
+
+    def refit(self, mean_t, std_t, alpha: float, min_std: float):
+        """glgym_plan_refit with H = Ht, in place on mean_t / std_t [Ht, P, 6], over the elites() of the last rollout's theta."""
+        self._check_dist(mean_t, std_t)
+        if not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf"):
+            raise ValueError("min_std must be finite and >= 0")
+        if self._theta is None or self._elites is None:
+            raise ValueError("refit needs a rollout and its elites()")
+        e = self.env
+        a = L.make_plan_args(L.PlanRefitArgs, self.P, self.K, self.Ht, self._elites[0], self._theta.data_ptr(), self.elite_k_t.data_ptr(),
+                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
+                             mean_t.data_ptr(), std_t.data_ptr())
+        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
+        return mean_t, std_t
+
+    def select(self) -> Dict[str, Any]:
+        """glgym_plan_select with H = Ht on the last rollout's scores: {"best_k" [P] i32 (-1: every candidate failed), "best_return"
+        [P] f64, "best_theta" [P, Ht*6] f32 (component i at [., i]; zeros without an admissible candidate)}.  Device tensors,
+        overwritten by the next call; no allocation."""
+        if self._theta is None:
+            raise ValueError("select needs a rollout")
+        e = self.env
+        a = L.make_plan_args(L.PlanSelectArgs, self.P, self.K, self.Ht, self.score_t.data_ptr(), self.score_failed_t.data_ptr(),
+                             self._theta.data_ptr(), self.best_k_t.data_ptr(), self.best_ret_t.data_ptr(), None,
+                             self.best_sequence_t.data_ptr(), 0.0, None)
+        L.check(e._lib.glgym_plan_select(e._h, C.byref(a), e._stream()), "glgym_plan_select")
+        self.best_theta_t.view(self.P, self.Ht, L.NU).copy_(self.best_sequence_t.permute(1, 0, 2))
+        return {"best_k": self.best_k_t, "best_return": self.best_ret_t, "best_theta": self.best_theta_t}
+
+    def cem(self, n_iter: int, n_elite: int, init_std: float = 0.5, min_std: float = 0.02, alpha: float = 0.1, carry: int = 0,
+            seed: int = 0, mean=None) -> Dict[str, Any]:
+        """Policy search: n_iter x (sample -> rollout -> elites -> refit), then select() on the last population.  mean None: start
+        from theta = 0 (the policy that holds the controls); otherwise from `mean` [Ht, P, 6] or [Ht, 1, 6] -- encode(net) for a warm
+        start.  The spread starts at init_std (theta units: a parameter's bound is its scale).  carry <= n_elite elites survive from
+        one population into the next; nothing is carried into the first.  Every sample() takes the next draw index of this object's
+        lifetime.
+        Returns device tensors, overwritten by the next call: best_theta [P, Ht*6], best_return, best_k [P], mean, std [Ht, P, 6],
+        elite_k [P, n_elite], n_elite [P].  No host synchronisation and, after the first call, no allocation: a whole cem() can be
+        captured in a graph (add n_iter to plan.draw_base_t between replays for fresh noise)."""
+        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
+        if n_iter < 1:
+            raise ValueError("n_iter must be at least 1")
+        if not 1 <= E <= self.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
+        if not 0 <= carry <= E:
+            raise ValueError("carry must be in 0 .. n_elite")
+        if not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
+            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
+        if mean is not None:
+            if mean.numel() not in (self.Ht * L.NU, self.Ht * self.P * L.NU):
+                raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
+            self.mean_t.copy_(mean.reshape(self.Ht, -1, L.NU))
+        else:
+            self.mean_t.zero_()
+        self.std_t.fill_(float(init_std))
+        self._elites = None
+        for _ in range(n_iter):
+            block = self.sample(self.mean_t, self.std_t, seed=seed, draw_index=self._draw, carry=carry)
+            self._draw += 1
+            self.rollout(block)
+            elite_k, n_el = self.elites(E)
+            self.refit(self.mean_t, self.std_t, alpha, min_std)
+        sel = self.select()
+        return {"best_theta": sel["best_theta"], "best_return": sel["best_return"], "best_k": sel["best_k"], "mean": self.mean_t,
+                "std": self.std_t, "elite_k": elite_k, "n_elite": n_el}
+
+    def best_theta(self, b: int = 0):
+        """theta [Ht, 1, 6] of the best candidate of the last select() / cem(): greenhouse b's with share="greenhouse", the one best
+        policy with share="all" (b is ignored).  A copy: pass it to evaluate(), or to MLPSpec.decode after .cpu()."""
+        b = int(b) if self.share == "greenhouse" else 0
+        if not 0 <= b < self.P:
+            raise ValueError(f"b must be in 0 .. {self.P - 1}")
+        return self.best_theta_t[b].clone().view(self.Ht, 1, L.NU)

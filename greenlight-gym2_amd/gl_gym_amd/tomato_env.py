@@ -467,6 +467,14 @@ class TomatoVecEnv:
         from .planner import RuleSearch
         return RuleSearch(self, n_candidates, horizon, tune, base=base, gamma=gamma, **scenario_kwargs)
 
+    def policy_search(self, n_candidates: int, horizon: int, spec, share: str = "greenhouse", gamma: float = 1.0, **scenario_kwargs):
+        """A gl_gym_amd.planner.PolicySearch for this environment: closed-loop rollouts of n_candidates MLP policies (spec: a
+        planner.MLPSpec with in_dim = obs_dim) over `horizon` env-steps on forked copies, and gradient-free policy search by the
+        cross-entropy method.  share="greenhouse": candidates per greenhouse; "all": every policy runs on all greenhouses and is scored
+        by its mean return.  The scenario arguments of planner() except weather_sigma apply (evaluation and search under crop noise)."""
+        from .planner import PolicySearch
+        return PolicySearch(self, n_candidates, horizon, spec, share=share, gamma=gamma, **scenario_kwargs)
+
     def _launch_reset(self, mask_t):
         """Masked reset; the kernel draws each new episode's start from the start table (Philox on (seed, env, episode)).
         rng="numpy": glgym_rng_reset_draw takes choice(years), choice(days) from each masked environment's stream first, and

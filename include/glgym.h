@@ -163,7 +163,7 @@ typedef struct {
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
- * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule */
+ * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -789,6 +789,97 @@ typedef struct {
 
 int glgym_rule_rows(glgym_handle h, const glgym_rule_rows_args* a, void* stream);
 int glgym_plan_rollout_rule(glgym_handle h, const glgym_plan_rollout_rule_args* a, void* stream);
+
+/* ---- closed-loop neural-policy rollouts: per-row MLP weights, policy search (csrc/gl_mlp.hpp, csrc/glgym_plan.hip) ----
+ * The feedback law of a candidate is a small MLP from the observation row glgym_obs writes to the six actions of glgym_step's action
+ * path, with weights of its own.  The section keeps the planning section's conventions: struct_size first, every refusal GLGYM_EINVAL
+ * with a message before anything is launched, asynchronous on `stream`, no allocation, no host synchronisation (capturable), plain
+ * vector stores, no atomics.  Opt-in: no other entry point changes.
+ *
+ * The net.  in_dim inputs (1 .. 1024), n_hidden hidden layers (0 .. 3; 0 is a linear policy) of width[l] neurons (1 .. 64), six
+ * outputs; one activation for all hidden layers, one squash on the outputs.
+ * Flat parameter vector, D components: layer by layer, the layer's weight [out][in] row-major, then its bias [out] -- the order of
+ * torch's parameters_to_vector on nn.Sequential(Linear, act, ..., Linear).  Candidate parameters are a float32 block theta [Ht][J][6],
+ * Ht = ceil(D / 6) <= 65 535: component i of row j is theta[i / 6][j][i % 6]; the padding entries are never used.  That is the block
+ * glgym_plan_sample / _elites / _refit / _select draw, rank, refit and pick when they are called with H = Ht.
+ * Parameter value: w_i = scale[g] * theta_i, one float32 product; g = 2 l for the weights of layer l and 2 l + 1 for its biases
+ * (2 (n_hidden + 1) groups; scale finite and > 0).  With scale 1 a trained net loads exactly; with theta sampled in [-1, 1] the scale
+ * is the search bound.
+ * Arithmetic: float32 throughout, products and sums rounded separately (no fused multiply-add).
+ *   input       o_i = fminf(fmaxf((obs_i - mean_i) * inv_std_i, -clip_obs), clip_obs); with mean = inv_std = NULL o_i = obs_i
+ *   layer       z_o = bias_o, then for i ascending z_o = z_o + w_oi * a_i
+ *   activation  relu: fmaxf(z, 0), a NaN reads as 0 | tanh: tanhf(z) | silu: z / (1 + expf(-z)), expf and IEEE division
+ *   output      a_j = fminf(fmaxf(s, -1), 1) with s = z_j (squash clip) or tanhf(z_j) (squash tanh); a NaN reads as -1, so that a NaN
+ *               action never reaches a step
+ * Refused: a size outside its range, another activation or squash, a scale that is not finite and > 0, exactly one of mean / inv_std
+ * NULL, with mean / inv_std a clip_obs that is not finite and > 0 (without them clip_obs is not looked at), Ht > 65 535. */
+enum { GLGYM_MLP_RELU = 0, GLGYM_MLP_TANH = 1, GLGYM_MLP_SILU = 2 };
+enum { GLGYM_MLP_SQUASH_CLIP = 0, GLGYM_MLP_SQUASH_TANH = 1 };
+typedef struct {
+    int32_t in_dim;              /* 1 .. 1024 */
+    int32_t n_hidden;            /* 0 .. 3 */
+    int32_t width[3];            /* 1 .. 64 each; entries n_hidden .. 2 are ignored */
+    int32_t activation;          /* GLGYM_MLP_RELU | _TANH | _SILU */
+    int32_t squash;              /* GLGYM_MLP_SQUASH_CLIP | _TANH */
+    float scale[8];              /* entries 2 (n_hidden + 1) .. 7 are ignored */
+    float clip_obs;
+    const float* mean;           /* device [in_dim] f32, or NULL with inv_std */
+    const float* inv_std;        /* device [in_dim] f32: 1 / sqrt(var + epsilon) */
+} glgym_mlp_net;
+
+/* which row of theta child c reads.  CHILD: row c / max(S, 1) -- every candidate of every greenhouse has weights of its own; needs
+ * B <= J * max(S, 1).  CANDIDATE: row (c / max(S, 1)) % J -- policy k is shared by all greenhouses (children ordered greenhouse,
+ * candidate, scenario with J candidates per greenhouse); J = 1 runs one policy everywhere. */
+enum { GLGYM_POLICY_ROW_CHILD = 0, GLGYM_POLICY_ROW_CANDIDATE = 1 };
+
+/* The policy of B rows: action[b] = net(obs[b]; theta row of b).  One lane per row, one wavefront per block; the activations of a
+ * lane pass through LDS laid out [neuron][lane] (two buffers of at most 64 x 64 floats), inputs wider than 64 in tiles of 64.  The
+ * theta reads of a wavefront are 6 consecutive floats per lane with neighbouring rows adjacent; lanes that share a row read one
+ * address.  Nothing outside action [B][6] is written. */
+typedef struct {
+    int32_t struct_size;
+    int32_t B;                   /* rows (1 .. 2^31 - 64) */
+    int32_t J;                   /* rows of theta (>= 1) */
+    int32_t S;                   /* 0 .. 256 */
+    int32_t row_mode;            /* GLGYM_POLICY_ROW_CHILD | _CANDIDATE */
+    glgym_mlp_net net;
+    const float* obs;            /* [B][in_dim] row-major f32: what glgym_obs writes */
+    const float* theta;          /* [Ht][J][6] f32 */
+    float* action;               /* [B][6] row-major f32 out, in [-1, 1] */
+} glgym_policy_rows_args;
+
+/* H CLOSED-LOOP env-steps of the children.  For h = 0 .. H-1: with S >= 1 glgym_plan_scenario at step h (crop blocks only, no action
+ * plane); glgym_obs in full mode on the children's present x, u, timestep, w_off and start_day with rollout.step.weather /
+ * weather_rows and Np, into `obs` [step.B][in_dim]; the policy kernel above into plane (record ? h : 0) of `actions`; glgym_step
+ * with action = that plane and metrics = NULL; glgym_plan_accumulate with the running-product weight.  rollout.actions and
+ * rollout.controls must be NULL; `actions` is record ? H : 1 planes of [step.B][6] f32, WRITTEN by this call.  The handle's
+ * observation modules apply: net.in_dim must equal glgym_obs_dim(h, Np).  S = 0: no scenarios (P, K, hold, scale, seed, draw_index,
+ * draw_base are ignored); CHILD mode needs step.B <= J.  1 <= S <= 256: step.B == P*K*S, rollout.step.crop_p is required, J == P*K
+ * in CHILD mode and J == K in CANDIDATE mode.  H >= 1 (with S >= 1 also H <= 65 536) and gamma as for glgym_plan_rollout.  The
+ * handle's verify mode, scheme, n_sub and integrator apply as to any action step; what glgym_step refuses without launching is
+ * refused here in its words before the first launch. */
+typedef struct {
+    int32_t struct_size;
+    int32_t record;              /* 0: one action plane, overwritten at every step; 1: H planes, plane h = the actions of step h */
+    glgym_plan_rollout_args rollout;
+    glgym_mlp_net net;
+    const float* theta;          /* [Ht][J][6] f32 */
+    const float* start_day;      /* [step.B]: the children's (glgym_plan_fork writes it) */
+    float* obs;                  /* [step.B][in_dim] f32 workspace: the observations of the last step afterwards */
+    float* actions;              /* [record ? H : 1][step.B][6] f32 out */
+    int32_t Np;                  /* forecast rows of the observation (glgym_obs_args.Np) */
+    int32_t row_mode;
+    int32_t J;
+    int32_t P, K, S;             /* as glgym_plan_rollout_scenarios_args; S = 0: no scenarios */
+    int32_t hold;
+    double scale;
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;
+} glgym_plan_rollout_policy_args;
+
+int glgym_policy_rows(glgym_handle h, const glgym_policy_rows_args* a, void* stream);
+int glgym_plan_rollout_policy(glgym_handle h, const glgym_plan_rollout_policy_args* a, void* stream);
 
 /* ---- on-device VecNormalize ---------------------------------------------------------------------
  * Replaces stable_baselines3.common.vec_env.VecNormalize (3rd party, pinned ==2.6.0 in the reference's requirements.txt)
