@@ -21,6 +21,11 @@
 // network and no atomic.  refit: one wavefront per (parent, horizon step), lanes stride over the elites, two passes over at most E
 // gathered rows.
 //
+// The evolution strategy's stages (glgym_plan_es_sample / _es_utilities / _es_update; scalar logic in gl_es.hpp, instantiated on the host
+// by tests/eshost/eshost.cpp).  sample: lane = mirrored pair, one wavefront per 64 pairs and plane, four to a block; no LDS (no recurrence along
+// h), three 16-byte stores per lane and plane.  utilities: the elites' grid and counting, one utility stored per candidate.  update: one
+// wavefront per (row, plane), lanes stride over the pairs, one pass over the plane's K rows, lane 0 steps mean, std and moments.
+//
 // Robust planning (glgym_plan_scenario / _aggregate; scalar logic in gl_scen.hpp, instantiated on the host by
 // tests/scenhost/scenhost.cpp).  scenario: lane = child, the prologue of one env-step of a scenario rollout -- the child's crop block
 // for this step and its row of the expanded action plane.  aggregate: one wavefront per candidate, its S <= 256 scenario returns
@@ -52,6 +57,7 @@
 #include "glgym_internal.h"
 
 #include "gl_cem.hpp"
+#include "gl_es.hpp"
 #include "gl_mlp.hpp"
 #include "gl_plan.hpp"
 #include "gl_rule.hpp"
@@ -272,6 +278,88 @@ __global__ __launch_bounds__(WAVE) void plan_refit_kernel(glgym_plan_refit_args 
             a.mean_out[o + j] = keep ? mean : (float)glcem::blend_mean(a.alpha, mean, m[j]);
             a.std_out[o + j] = keep ? sd : (float)glcem::blend_std(a.alpha, sd, s[j], a.min_std);
         }
+}
+
+// ---- the evolution strategy's stages (gl_es.hpp) ------------------------------------------------------------------------------------
+// grid = (ceil(P*M / 64), ceil(H / SAMPLE_WAVES)) blocks of SAMPLE_WAVES wavefronts: lane = pair q = p*M + m, wave w of block (x, y)
+// draws the plane h = y * SAMPLE_WAVES + w, so that a small population (P*M of a few thousand) still fills the chip with its planes.
+// There is no recurrence along h (beta = 0), so nothing is staged: a lane draws its pair's six normals once and stores both rows, 48
+// contiguous bytes (16-byte aligned: 48 q from an aligned base, P*K even) as three 16-byte stores; a wave writes 3 072 contiguous bytes.
+__global__ __launch_bounds__(SAMPLE_WAVES * WAVE) void plan_es_sample_kernel(glgym_plan_es_sample_args a)
+{
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int M = a.K / 2, n_pair = a.P * M;
+    const int q = blockIdx.x * WAVE + lane, h = blockIdx.y * SAMPLE_WAVES + w;
+    if (q >= n_pair || h >= a.H) return;                // no barrier below
+    const int p = q / M;
+    const uint64_t D = a.draw_index + (a.draw_base ? *a.draw_base : 0ull);
+    const size_t row = ((size_t)h * a.P + p) * NU;
+    float r[2 * NU];
+    gles::pair_rows(q, h, D, a.seed, a.mean + row, a.std + row, r);
+    float4* out = reinterpret_cast<float4*>(a.actions + ((size_t)h * a.P * a.K + 2 * (size_t)q) * NU);
+    out[0] = make_float4(r[0], r[1], r[2], r[3]);
+    out[1] = make_float4(r[4], r[5], r[6], r[7]);
+    out[2] = make_float4(r[8], r[9], r[10], r[11]);
+}
+
+// plan_elites_kernel's grid and counting (P * n_chunks blocks, tiles of 256 keys in LDS, broadcast reads); every candidate stores its
+// utility, thread 0 of a row's first block the row's number of admissible candidates.
+__global__ __launch_bounds__(glcem::TILE) void plan_es_utilities_kernel(glgym_plan_es_utilities_args a, int n_chunks)
+{
+    constexpr int TILE = glcem::TILE, CHUNK = glcem::CHUNK;
+    __shared__ double s_key[TILE];
+    __shared__ int s_rank[ELITE_WAVES][CHUNK];
+    const int p = blockIdx.x / n_chunks, tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int k0 = (blockIdx.x - p * n_chunks) * CHUNK, t = k0 + lane;
+    const double* ret = a.ret + (size_t)p * a.K;
+    const uint8_t* failed = a.failed + (size_t)p * a.K;
+    const double rk = t < a.K ? glcem::key(ret[t], failed[t]) : __builtin_nan("");
+    int rank = 0, n_adm = 0;
+    for (int j0 = 0; j0 < a.K; j0 += TILE) {            // block-uniform trip count: every thread reaches both barriers
+        const int j = j0 + tid;
+        const double kj = j < a.K ? glcem::key(ret[j], failed[j]) : __builtin_nan("");
+        s_key[tid] = kj;
+        n_adm += __syncthreads_count(kj == kj);
+        const int c0 = j0 + w * CHUNK, n = a.K - c0 < CHUNK ? a.K - c0 : CHUNK;
+        if (n > 0) rank += glcem::count_chunk(s_key + w * CHUNK, c0, n, rk, t, k0);
+        __syncthreads();
+    }
+    s_rank[w][lane] = rank;
+    __syncthreads();
+    if (w == 0) {
+        for (int i = 1; i < ELITE_WAVES; ++i) rank += s_rank[i][lane];
+        if (t < a.K) a.u[(size_t)p * a.K + t] = gles::utility(rk == rk, rank, n_adm);
+        if (t == 0) a.n_adm[p] = n_adm;
+    }
+}
+
+// grid = (P, H), one wavefront each: lane l takes the pairs m = l, l + 64, ... -- 48 bytes of the plane as three 16-byte loads, the two
+// utilities as one -- so a load round of the wavefront covers 3 072 contiguous bytes; the population is read once.  The sums end in
+// every lane (butterfly); lane 0 updates and stores.
+__global__ __launch_bounds__(WAVE) void plan_es_update_kernel(glgym_plan_es_update_args a)
+{
+    const gles::Hyper hp{a.optimizer, a.lr, a.lr_std, a.std_decay, a.min_std, a.max_std, a.beta1, a.beta2, a.eps};
+    const int p = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+    const int M = a.K / 2;
+    const size_t o = ((size_t)h * a.P + p) * NU;
+    const float4* rows = reinterpret_cast<const float4*>(a.actions + ((size_t)h * a.P + p) * a.K * NU);
+    const double2* u = reinterpret_cast<const double2*>(a.u + (size_t)p * a.K);
+    double sigma[NU], g[NU], s[NU];
+    for (int j = 0; j < NU; ++j) { sigma[j] = (double)a.std[o + j]; g[j] = s[j] = 0.0; }
+    for (int m = lane; m < M; m += WAVE) {
+        const float4 r0 = rows[3 * (size_t)m], r1 = rows[3 * (size_t)m + 1], r2 = rows[3 * (size_t)m + 2];
+        const double2 um = u[m];
+        const float r[2 * NU] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+        gles::pair_terms(r, um.x, um.y, sigma, g, s);
+    }
+    for (int j = 0; j < NU; ++j) {
+        g[j] = wave_sum(g[j]) / (double)M;
+        s[j] = wave_sum(s[j]) / (double)M;
+    }
+    if (lane != 0) return;
+    const uint64_t t = a.t_index + (a.t_base ? *a.t_base : 0ull);
+    const bool keep = a.n_adm[p] < 2 || t == 0 || !gles::finite6(g) || !gles::finite6(s);
+    gles::update_row(hp, t, keep, g, s, a.mean + o, a.std + o, a.m1 ? a.m1 + o : nullptr, a.m2 ? a.m2 + o : nullptr, a.mean_out + o, a.std_out + o);
 }
 
 // grid = ceil(C / 256), lane = child c = (p*K + k)*S + s: nine Philox blocks keyed by (p*S + s, step) -- the S children of a candidate
@@ -560,6 +648,78 @@ int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* strea
     }
     DeviceGuard dev_guard(h);
     hipLaunchKernelGGL(plan_refit_kernel, dim3(a->P, a->H), dim3(WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+// the evolution strategy's stages (gl_es.hpp): checked before the handle is looked at, one text per mistake
+static bool es_shape_ok(const char* who, int32_t P, int32_t K, int32_t H)
+{
+    const std::string w(who);
+    if (P < 1 || H < 1) { g_err = w + ": P or H < 1"; return false; }
+    if (K < 2) { g_err = w + ": K < 2 (a population is at least one mirrored pair)"; return false; }
+    if (K % 2) { g_err = w + ": K is odd (mirrored sampling draws pairs)"; return false; }
+    if ((int64_t)P * K > INT32_MAX - 255) { g_err = w + ": P * K past INT32_MAX - 255 (the lane indices would wrap)"; return false; }
+    if (H > 65535) { g_err = w + ": H > 65 535"; return false; }
+    return true;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+int glgym_plan_es_sample(glgym_handle h, const glgym_plan_es_sample_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_es_sample: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_es_sample", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!es_shape_ok("glgym_plan_es_sample", a->P, a->K, a->H)) return GLGYM_EINVAL;
+    if (!a->mean || !a->std || !a->actions) { g_err = "glgym_plan_es_sample: null mean, std or actions"; return GLGYM_EINVAL; }
+    if (!aligned16(a->actions)) { g_err = "glgym_plan_es_sample: actions is not 16-byte aligned"; return GLGYM_EINVAL; }
+    if (!h) { g_err = "glgym_plan_es_sample: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    const int64_t n_pair = (int64_t)a->P * (a->K / 2);
+    hipLaunchKernelGGL(plan_es_sample_kernel, dim3((unsigned)((n_pair + WAVE - 1) / WAVE), (a->H + SAMPLE_WAVES - 1) / SAMPLE_WAVES), dim3(SAMPLE_WAVES * WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_es_utilities(glgym_handle h, const glgym_plan_es_utilities_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_es_utilities: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_es_utilities", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!es_shape_ok("glgym_plan_es_utilities", a->P, a->K, 1)) return GLGYM_EINVAL;
+    if (!a->ret || !a->failed || !a->u || !a->n_adm) { g_err = "glgym_plan_es_utilities: null ret, failed, u or n_adm"; return GLGYM_EINVAL; }
+    if (!h) { g_err = "glgym_plan_es_utilities: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    const int n_chunks = (a->K + glcem::CHUNK - 1) / glcem::CHUNK;
+    hipLaunchKernelGGL(plan_es_utilities_kernel, dim3((unsigned)((int64_t)a->P * n_chunks)), dim3(glcem::TILE), 0, (hipStream_t)stream, *a, n_chunks);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_es_update(glgym_handle h, const glgym_plan_es_update_args* a, void* stream)
+{
+    const char* who = "glgym_plan_es_update";
+    const auto refuse = [&](const char* why) { g_err = std::string(who) + ": " + why; return (int)GLGYM_EINVAL; };
+    if (!a) return refuse("null arguments");
+    if (!plan_size_ok(who, a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!es_shape_ok(who, a->P, a->K, a->H)) return GLGYM_EINVAL;
+    if (a->optimizer != GLGYM_ES_SGD && a->optimizer != GLGYM_ES_ADAM) return refuse("optimizer is not GLGYM_ES_SGD or GLGYM_ES_ADAM");
+    if (!a->actions || !a->u || !a->n_adm || !a->mean || !a->std || !a->mean_out || !a->std_out)
+        return refuse("null actions, u, n_adm, mean, std, mean_out or std_out");
+    if (!aligned16(a->actions) || !aligned16(a->u)) return refuse("actions or u is not 16-byte aligned");
+    if (!(a->lr >= 0.0) || !std::isfinite(a->lr)) return refuse("lr negative or not finite");
+    if (!(a->lr_std >= 0.0) || !std::isfinite(a->lr_std)) return refuse("lr_std negative or not finite");
+    if (!(a->std_decay > 0.0) || !std::isfinite(a->std_decay)) return refuse("std_decay not finite or not > 0");
+    if (!(a->min_std >= 0.0) || !std::isfinite(a->max_std) || !(a->min_std <= a->max_std))
+        return refuse("min_std negative, max_std not finite, or min_std > max_std");
+    if (a->t_index == 0) return refuse("t_index = 0 (the step count starts at 1)");
+    if (a->optimizer == GLGYM_ES_ADAM) {
+        if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0)) return refuse("beta1 or beta2 outside [0, 1)");
+        if (!(a->eps > 0.0) || !std::isfinite(a->eps)) return refuse("eps not finite or not > 0");
+        if (!a->m1 || !a->m2) return refuse("GLGYM_ES_ADAM without m1 or m2");
+    }
+    if (!h) return refuse("null handle");
+    DeviceGuard dev_guard(h);
+    hipLaunchKernelGGL(plan_es_update_kernel, dim3(a->P, a->H), dim3(WAVE), 0, (hipStream_t)stream, *a);
     HIPCHK(hipGetLastError());
     return GLGYM_OK;
 }

@@ -188,6 +188,29 @@ class PlanRefitArgs(C.Structure):
                 ("min_std", C.c_double), ("mean", C.c_void_p), ("std", C.c_void_p), ("mean_out", C.c_void_p), ("std_out", C.c_void_p)]
 
 
+# evolution strategy (include/glgym.h glgym_plan_es_sample / _es_utilities / _es_update)
+ES_OPTIMIZERS = {"sgd": 0, "adam": 1}
+
+
+class PlanEsSampleArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("H", C.c_int32), ("mean", C.c_void_p),
+                ("std", C.c_void_p), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p),
+                ("actions", C.c_void_p)]
+
+
+class PlanEsUtilitiesArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("ret", C.c_void_p), ("failed", C.c_void_p),
+                ("u", C.c_void_p), ("n_adm", C.c_void_p)]
+
+
+class PlanEsUpdateArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("H", C.c_int32), ("optimizer", C.c_int32),
+                ("actions", C.c_void_p), ("u", C.c_void_p), ("n_adm", C.c_void_p), ("lr", C.c_double), ("lr_std", C.c_double),
+                ("std_decay", C.c_double), ("min_std", C.c_double), ("max_std", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("t_index", C.c_uint64), ("t_base", C.c_void_p), ("m1", C.c_void_p),
+                ("m2", C.c_void_p), ("mean", C.c_void_p), ("std", C.c_void_p), ("mean_out", C.c_void_p), ("std_out", C.c_void_p)]
+
+
 # robust planning (include/glgym.h glgym_plan_scenario / _rollout_scenarios / _aggregate)
 MAX_SCENARIOS = 256
 
@@ -340,6 +363,9 @@ PROTOTYPES = {
     "glgym_plan_sample": (C.c_int, [C.c_void_p, C.POINTER(PlanSampleArgs), C.c_void_p]),
     "glgym_plan_elites": (C.c_int, [C.c_void_p, C.POINTER(PlanElitesArgs), C.c_void_p]),
     "glgym_plan_refit": (C.c_int, [C.c_void_p, C.POINTER(PlanRefitArgs), C.c_void_p]),
+    "glgym_plan_es_sample": (C.c_int, [C.c_void_p, C.POINTER(PlanEsSampleArgs), C.c_void_p]),
+    "glgym_plan_es_utilities": (C.c_int, [C.c_void_p, C.POINTER(PlanEsUtilitiesArgs), C.c_void_p]),
+    "glgym_plan_es_update": (C.c_int, [C.c_void_p, C.POINTER(PlanEsUpdateArgs), C.c_void_p]),
     "glgym_plan_scenario": (C.c_int, [C.c_void_p, C.POINTER(PlanScenarioArgs), C.c_void_p]),
     "glgym_plan_rollout_scenarios": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutScenariosArgs), C.c_void_p]),
     "glgym_plan_aggregate": (C.c_int, [C.c_void_p, C.POINTER(PlanAggregateArgs), C.c_void_p]),

@@ -36,7 +36,13 @@ Closed-loop candidates (RuleSearch below, glgym_rule_rows / glgym_plan_rollout_r
 RuleSearch rolls out a feedback law instead -- the rule-based controller with per-candidate constants, evaluated on each child's own
 state before every step -- and tunes those constants with the same cross-entropy stages.  PolicySearch (glgym_policy_rows /
 glgym_plan_rollout_policy) does the same with a learned feedback law: an MLP from the child's observation row to the six actions
-(MLPSpec), with per-candidate weights -- scenario evaluation of a trained policy, and CEM over the weights of small nets."""
+(MLPSpec), with per-candidate weights -- scenario evaluation of a trained policy, and CEM over the weights of small nets.
+
+Evolution strategy (glgym_plan_es_sample / _es_utilities / _es_update; _EsStages below): both searches also offer es() -- candidates in
+mirrored pairs around the mean, centred ranks over the whole population, a search-gradient step on the mean (Adam or SGD) and the
+separable-NES update of the per-parameter spread -- with sample_mirrored(), utilities() and es_update() as the single stages.  The CEM
+refits an independent Gaussian to the best few of K, which suits a handful of set-points; the ES uses every return and suits the
+hundreds of weights of a net."""
 from __future__ import annotations
 
 import ctypes as C
@@ -545,6 +551,126 @@ class RuleParams:
         return {n: v[:, i].copy() for i, n in enumerate(self.names)}
 
 
+# ---- evolution strategy over theta (include/glgym.h glgym_plan_es_sample / _es_utilities / _es_update) -------------------------------
+class _EsStages:
+    """The evolution strategy's stages for RuleSearch and PolicySearch, in one place.  `search` supplies env, K, Ht, plan, its two
+    population blocks (_blocks, _cur), the block of its last rollout (_theta), _check_dist, rollout, select, mean_t / std_t and _draw;
+    P is the number of distribution rows, score_t / score_failed_t [P*K] what its rollouts leave behind.  Built at the first ES call,
+    which is the only one that allocates: u_t [P*K] f64, n_adm_t [P] i32, the Adam moments m1_t / m2_t [Ht, P, 6] f64, and t_base_t,
+    the device word added to every step count (as plan.draw_base_t is to every draw index)."""
+
+    def __init__(self, search, P, score_t, score_failed_t):
+        torch, dev = search.torch, search.env.device
+        if search.K < 2 or search.K % 2:
+            raise ValueError(f"the evolution strategy draws mirrored pairs: n_candidates must be even and >= 2, got {search.K}")
+        self.s, self.P, self.score_t, self.score_failed_t = search, int(P), score_t, score_failed_t
+        self.u_t = torch.zeros(self.P * search.K, dtype=torch.float64, device=dev)
+        self.n_adm_t = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self.m1_t = torch.zeros(search.Ht, self.P, L.NU, dtype=torch.float64, device=dev)
+        self.m2_t = torch.zeros_like(self.m1_t)
+        self.t_base_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.t = 0                                                   # updates since the last restart
+        self._scored = None                                          # the block utilities() belongs to
+
+    def restart(self):
+        self.m1_t.zero_()
+        self.m2_t.zero_()
+        self.t = 0
+
+    def sample_mirrored(self, mean_t, std_t, seed=0, draw_index=0):
+        s, e = self.s, self.s.env
+        s._check_dist(mean_t, std_t)
+        if int(seed) < 0 or int(draw_index) < 0:
+            raise ValueError("seed and draw_index must be >= 0")
+        dst = 0 if s._cur is None else 1 - s._cur
+        a = L.make_plan_args(L.PlanEsSampleArgs, self.P, s.K, s.Ht, mean_t.data_ptr(), std_t.data_ptr(), int(seed) & (2 ** 64 - 1),
+                             int(draw_index) & (2 ** 64 - 1), s.plan.draw_base_t.data_ptr(), s._blocks[dst].data_ptr())
+        L.check(e._lib.glgym_plan_es_sample(e._h, C.byref(a), e._stream()), "glgym_plan_es_sample")
+        s._cur = dst
+        s._elites = (s._elites[0], None) if s._elites else None      # no elite of an overwritten block is carried
+        return s._blocks[dst]
+
+    def utilities(self):
+        s, e = self.s, self.s.env
+        if s._theta is None:
+            raise ValueError("utilities needs a rollout")
+        a = L.make_plan_args(L.PlanEsUtilitiesArgs, self.P, s.K, self.score_t.data_ptr(), self.score_failed_t.data_ptr(),
+                             self.u_t.data_ptr(), self.n_adm_t.data_ptr())
+        L.check(e._lib.glgym_plan_es_utilities(e._h, C.byref(a), e._stream()), "glgym_plan_es_utilities")
+        self._scored = s._theta
+        return self.u_t.view(self.P, s.K), self.n_adm_t
+
+    @staticmethod
+    def check_hyper(lr, lr_std, std_decay, min_std, max_std, optimizer, betas, eps):
+        inf = float("inf")
+        if optimizer not in L.ES_OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {sorted(L.ES_OPTIMIZERS)}")
+        if not 0.0 <= float(lr) < inf or not 0.0 <= float(lr_std) < inf:
+            raise ValueError("lr and lr_std must be finite and >= 0")
+        if not 0.0 < float(std_decay) < inf:
+            raise ValueError("std_decay must be finite and > 0")
+        if not 0.0 <= float(min_std) <= float(max_std) < inf:
+            raise ValueError("min_std and max_std must be finite with 0 <= min_std <= max_std")
+        b1, b2 = (float(b) for b in betas)
+        if optimizer == "adam" and (not 0.0 <= b1 < 1.0 or not 0.0 <= b2 < 1.0 or not 0.0 < float(eps) < inf):
+            raise ValueError("betas must lie in [0, 1) and eps must be finite and > 0")
+        return b1, b2
+
+    def update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
+        s, e = self.s, self.s.env
+        s._check_dist(mean_t, std_t)
+        b1, b2 = self.check_hyper(lr, lr_std, std_decay, min_std, max_std, optimizer, betas, eps)
+        if self._scored is None or self._scored is not s._theta:
+            raise ValueError("es_update needs a rollout and its utilities()")
+        a = L.make_plan_args(L.PlanEsUpdateArgs, self.P, s.K, s.Ht, L.ES_OPTIMIZERS[optimizer], self._scored.data_ptr(), self.u_t.data_ptr(),
+                             self.n_adm_t.data_ptr(), float(lr), float(lr_std), float(std_decay), float(min_std), float(max_std), b1, b2,
+                             float(eps), self.t + 1, self.t_base_t.data_ptr(), self.m1_t.data_ptr(), self.m2_t.data_ptr(),
+                             mean_t.data_ptr(), std_t.data_ptr(), mean_t.data_ptr(), std_t.data_ptr())
+        L.check(e._lib.glgym_plan_es_update(e._h, C.byref(a), e._stream()), "glgym_plan_es_update")
+        self.t += 1
+        return mean_t, std_t
+
+    def run(self, n_iter, lr, lr_std, init_std, min_std, max_std, std_decay, optimizer, betas, eps, seed, mean, resume):
+        s = self.s
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise ValueError("n_iter must be at least 1")
+        self.check_hyper(lr, lr_std, std_decay, min_std, max_std, optimizer, betas, eps)
+        if not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
+            raise ValueError("init_std must be finite and >= 0, seed >= 0")
+        if resume and mean is not None:
+            raise ValueError("resume=True continues from mean_t / std_t: it takes no mean")
+        if not resume:
+            if mean is not None:
+                if mean.numel() not in (s.Ht * L.NU, s.Ht * self.P * L.NU):
+                    raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
+                s.mean_t.copy_(mean.reshape(s.Ht, -1, L.NU))
+            else:
+                s._es_start()
+            s.std_t.fill_(float(init_std))
+            self.restart()
+        for _ in range(n_iter):
+            block = self.sample_mirrored(s.mean_t, s.std_t, seed=seed, draw_index=s._draw)
+            s._draw += 1
+            s.rollout(block)
+            u, n_adm = self.utilities()
+            self.update(s.mean_t, s.std_t, lr, lr_std, std_decay, min_std=min_std, max_std=max_std, optimizer=optimizer, betas=betas, eps=eps)
+        out = dict(s.select())
+        out.update(mean=s.mean_t, std=s.std_t, u=u, n_adm=n_adm)
+        return out
+
+
+_ES_DOC = """Evolution strategy: n_iter x (sample_mirrored -> rollout -> utilities -> es_update), then select() on the last population.
+        Mirrored pairs (n_candidates even), centred ranks over the WHOLE population, a search-gradient step on the mean ("adam" or
+        "sgd", ascending the return) and the separable-NES update of the spread, std <- clip(std * std_decay * exp(lr_std / 2 * s),
+        min_std, max_std); lr_std = 0 with std_decay = 1 keeps the spread at init_std.  The start is cem()'s: `mean`, or this object's
+        default.  resume=True continues instead from mean_t / std_t, the Adam moments and the step count of the previous call.  Every
+        sample takes the next draw index of this object's lifetime.
+        Returns device tensors, overwritten by the next call: what select() returns, mean, std, u [P, K] f64, n_adm [P] i32.  No host
+        synchronisation and, after the first call, no allocation: a whole es() can be captured in a graph; between replays add n_iter
+        to plan.draw_base_t for fresh noise and, with resume=True, to es_t_base for the next Adam steps."""
+
+
 class RuleSearch:
     """Closed-loop rollouts of the rule-based controller, and the tuning of its constants by the cross-entropy method, on the device
     (TomatoVecEnv.rule_search).  A candidate is not a control sequence but a FEEDBACK LAW: a row of K per greenhouse of the float32 block
@@ -595,6 +721,7 @@ class RuleSearch:
         self.best_params = {n: self._params_T[i] for i, n in enumerate(self.names)}
         self._base_theta = torch.as_tensor(self.params.encode(self.base), device=dev) if self.params.inside(self.base) else None
         self._draw = 0
+        self._es_stages = None
         self.scenario_returns = getattr(p, "scenario_returns", None)
         self.scenario_failed = getattr(p, "scenario_failed", None)
 
@@ -778,6 +905,47 @@ class RuleSearch:
         sel = self.select()
         return {"best_theta": sel["best_theta"], "best_params": sel["best_params"], "best_return": sel["best_return"], "best_k": sel["best_k"],
                 "mean": self.mean_t, "std": self.std_t, "elite_k": elite_k, "n_elite": n_el}
+
+    # ---- the evolution strategy over theta (_EsStages) -------------------------------------------------------------------------------
+    def _es(self):
+        if self._es_stages is None:
+            self._es_stages = _EsStages(self, self.B, self.plan._score_t, self.plan._score_failed_t)
+        return self._es_stages
+
+    def _es_start(self):
+        if self._base_theta is not None:
+            self.mean_t.copy_(self._base_theta)
+        else:
+            self.mean_t.zero_()
+
+    @property
+    def es_t_base(self):
+        """The device word added to every es_update step count (int64 [1])."""
+        return self._es().t_base_t
+
+    def sample_mirrored(self, mean_t, std_t, seed: int = 0, draw_index: int = 0):
+        """glgym_plan_es_sample with H = Ht: the population theta in mirrored pairs (rows 2m and 2m + 1 of a distribution row:
+        clip(mean + std e) and clip(mean - std e)), into the block the previous population does not occupy; returns it.  No reserved
+        candidate.  ValueError if n_candidates is odd."""
+        return self._es().sample_mirrored(mean_t, std_t, seed, draw_index)
+
+    def utilities(self):
+        """glgym_plan_es_utilities on the last rollout's scores: (u [P, K] f64 -- centred ranks 0.5 .. -0.5 over the admissible
+        candidates, -0.5 for the others, all 0 with fewer than two -- and n_adm [P] i32)."""
+        return self._es().utilities()
+
+    def es_update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
+        """glgym_plan_es_update with H = Ht, in place on mean_t / std_t, over the utilities() of the last rollout's theta.  The Adam
+        moments and the step count are this object's (es() restarts them)."""
+        return self._es().update(mean_t, std_t, lr, lr_std, std_decay, min_std=min_std, max_std=max_std, optimizer=optimizer, betas=betas,
+                                 eps=eps)
+
+    def es(self, n_iter: int, lr: float, lr_std: float = 0.1, init_std: float = 0.3, min_std: float = 0.02, max_std: float = 1.0,
+           std_decay: float = 1.0, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, mean=None,
+           resume: bool = False) -> Dict[str, Any]:
+        return self._es().run(n_iter, lr, lr_std, init_std, min_std, max_std, std_decay, optimizer, betas, eps, seed, mean, resume)
+
+    es.__doc__ = _ES_DOC
 
     def best_controller(self, b: int = 0):
         """The RuleBasedController of greenhouse b's best candidate of the last select() / cem(): base with the tuned constants
@@ -988,6 +1156,7 @@ class PolicySearch:
         else:
             self.score_t, self.score_failed_t = p._score_t, p._score_failed_t
         self._draw = 0
+        self._es_stages = None
         self.scenario_returns = getattr(p, "scenario_returns", None)
         self.scenario_failed = getattr(p, "scenario_failed", None)
 
@@ -1158,6 +1327,44 @@ class PolicySearch:
         sel = self.select()
         return {"best_theta": sel["best_theta"], "best_return": sel["best_return"], "best_k": sel["best_k"], "mean": self.mean_t,
                 "std": self.std_t, "elite_k": elite_k, "n_elite": n_el}
+
+    # ---- the evolution strategy over theta (_EsStages) -------------------------------------------------------------------------------
+    def _es(self):
+        if self._es_stages is None:
+            self._es_stages = _EsStages(self, self.P, self.score_t, self.score_failed_t)
+        return self._es_stages
+
+    def _es_start(self):
+        self.mean_t.zero_()
+
+    @property
+    def es_t_base(self):
+        """The device word added to every es_update step count (int64 [1])."""
+        return self._es().t_base_t
+
+    def sample_mirrored(self, mean_t, std_t, seed: int = 0, draw_index: int = 0):
+        """glgym_plan_es_sample with H = Ht: the population theta in mirrored pairs (rows 2m and 2m + 1 of a distribution row:
+        clip(mean + std e) and clip(mean - std e)), into the block the previous population does not occupy; returns it.  No reserved
+        candidate.  ValueError if n_candidates is odd."""
+        return self._es().sample_mirrored(mean_t, std_t, seed, draw_index)
+
+    def utilities(self):
+        """glgym_plan_es_utilities on the last rollout's scores: (u [P, K] f64 -- centred ranks 0.5 .. -0.5 over the admissible
+        candidates, -0.5 for the others, all 0 with fewer than two -- and n_adm [P] i32)."""
+        return self._es().utilities()
+
+    def es_update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
+        """glgym_plan_es_update with H = Ht, in place on mean_t / std_t, over the utilities() of the last rollout's theta.  The Adam
+        moments and the step count are this object's (es() restarts them)."""
+        return self._es().update(mean_t, std_t, lr, lr_std, std_decay, min_std=min_std, max_std=max_std, optimizer=optimizer, betas=betas,
+                                 eps=eps)
+
+    def es(self, n_iter: int, lr: float, lr_std: float = 0.1, init_std: float = 0.1, min_std: float = 0.01, max_std: float = 1.0,
+           std_decay: float = 1.0, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, mean=None,
+           resume: bool = False) -> Dict[str, Any]:
+        return self._es().run(n_iter, lr, lr_std, init_std, min_std, max_std, std_decay, optimizer, betas, eps, seed, mean, resume)
+
+    es.__doc__ = _ES_DOC
 
     def best_theta(self, b: int = 0):
         """theta [Ht, 1, 6] of the best candidate of the last select() / cem(): greenhouse b's with share="greenhouse", the one best

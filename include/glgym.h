@@ -33,6 +33,8 @@
  *   glgym_plan_fork / _accumulate / _rollout / _select, glgym_plan_sample / _elites / _refit <- no counterpart (the reference's
  *                     README lists MPC as a next step): sampling MPC on forked copies of the environments, one-shot (random
  *                     shooting, MPPI) and iterated (the cross-entropy method: sample, rank the elites, refit), all on the device
+ *   glgym_plan_es_sample / _es_utilities / _es_update <- no counterpart: an evolution strategy over the same blocks (mirrored
+ *                     sampling, centred ranks of the whole population, a search-gradient step on mean and spread), for policy search
  *   glgym_plan_scenario / _rollout_scenarios / _aggregate <- the draw of noise.py:3-23 (parametric_crop_uncertainty) inside the
  *                     planning horizon, with common random numbers across candidates, and a risk score over the sampled futures
  *
@@ -163,7 +165,8 @@ typedef struct {
  * compatible; no struct changed): glgym_set_step_integrator, GLGYM_SF_BDF, GLGYM_METRIC_BDF; glgym_rng_crop_noise, glgym_rng_reset_draw;
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
- * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy */
+ * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
+ * glgym_plan_es_utilities, glgym_plan_es_update */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -578,6 +581,87 @@ typedef struct {
 int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* stream);
 int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream);
 int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream);
+
+/* ---- evolution strategy: mirrored sampling, centred ranks, search-gradient step (csrc/gl_es.hpp, csrc/glgym_plan.hip) -----------
+ * One ES iteration is glgym_plan_es_sample -> a rollout -> glgym_plan_es_utilities -> glgym_plan_es_update.  Same layouts and
+ * conventions as the CEM stages above (mean / std [H][P][6] f32, the block [H][P*K][6] f32; struct_size first; every argument is
+ * checked, GLGYM_EINVAL with a glgym_last_error text, before the handle is looked at and before anything is launched; asynchronous on
+ * `stream`, no allocation, no host synchronisation (capturable), plain vector stores, no atomics).  Opt-in: no other entry point
+ * changes.  K is EVEN and >= 2, M = K/2 pairs per distribution row p; pair m is the children c+ = p*K + 2m and c- = c+ + 1.
+ * P*K <= INT32_MAX - 255, H <= 65 535.  Arithmetic in double, products and sums rounded separately.
+ *
+ * glgym_plan_es_sample, one lane per pair.  The six normals e of pair m at plane h are the CEM stream's of the EVEN child: words
+ * r0..r7 of (c+, h, D = draw_index + *draw_base, seed) and the Box-Muller formula of glgym_plan_sample, drawn once.
+ * actions[h][c+][j] = (float) clip(mean[h][p][j] + std[h][p][j] * e_j, -1, 1), actions[h][c-][j] the same with -e_j.  No reserved
+ * candidates, no carry, no colouring: for even k >= 2 row c+ is bit for bit what glgym_plan_sample (beta = 0, carry = 0) stores.  A
+ * lane stores its pair's 48 contiguous bytes as three 16-byte stores: `actions` must be 16-byte aligned. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, H;
+    const float* mean;           /* [H][P][6] */
+    const float* std;            /* [H][P][6] */
+    uint64_t seed;
+    uint64_t draw_index;         /* which population this is */
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    float* actions;              /* [H][P*K][6] out, 16-byte aligned */
+} glgym_plan_es_sample_args;
+
+/* Centred ranks over the WHOLE population.  Admissibility and order are glgym_plan_elites': per row p, the n candidates that have
+ * not failed and whose ret is finite, by np.argsort(-ret, kind="stable").  The candidate of rank r (0 = best) gets
+ * u = 0.5 - (double) r / (double)(n - 1) (one subtraction, one division); an inadmissible candidate gets -0.5; with n < 2 every u of
+ * the row is 0.  n_adm[p] = n.  Rank by counting over tiles of 256 returns staged in LDS, as glgym_plan_elites. */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K;
+    const double* ret;           /* [P*K] */
+    const uint8_t* failed;       /* [P*K] */
+    double* u;                   /* [P*K] out */
+    int32_t* n_adm;              /* [P] out */
+} glgym_plan_es_utilities_args;
+
+/* One wavefront per (row p, plane h); it reads the plane's K rows of `actions` and the row's K utilities once.
+ * With sigma_j = (double) std[h][p][j], per pair m: d_j = ((double) theta+_j - (double) theta-_j) * 0.5 (exact),
+ *   the gradient term  (u+ - u-) * d_j,
+ *   the spread term    (u+ + u-) * (z * z - 1) with z = d_j / sigma_j -- no term where sigma_j is not > 0.
+ * Lane l adds its terms for m = l, l + 64, ... in ascending order, starting from 0; the 64 partial sums are combined by the butterfly
+ * (xor 32, 16, .. 1) and divided by (double) M: g_j and s_j.  The step ASCENDS the return.  t = t_index + *t_base.
+ *   GLGYM_ES_SGD:   step = lr * g.
+ *   GLGYM_ES_ADAM:  m1 = beta1 * m1 + (1 - beta1) * g;  m2 = beta2 * m2 + (1 - beta2) * (g * g);
+ *                   step = (lr * (m1 / (1 - beta1^t))) / (sqrt(m2 / (1 - beta2^t)) + eps), every operation rounded on its own, left to
+ *                   right as bracketed.  b^t by square-and-multiply from the least significant bit of t: r = 1, q = b; while t != 0
+ *                   { if t is odd r = r * q;  t = t >> 1;  if t != 0 q = q * q }.  m1, m2 [H][P][6] f64 belong to the caller (zero
+ *                   them before t = 1).
+ *   mean_out = (float)((double) mean + step)
+ *   std_out  = (float) min(max((sigma * std_decay) * exp((0.5 * lr_std) * s), min_std), max_std)     (exp is the device library's)
+ * The six components of (p, h) keep their mean, std and moments if n_adm[p] < 2, if any of the six g_j or s_j is not finite (a NaN in
+ * theta), or if t = 0.  mean_out / std_out may be mean / std.  `actions` and `u` must be 16-byte aligned (a lane reads its pair's 48
+ * bytes as three 16-byte loads, its two utilities as one).
+ * Refused: lr or lr_std negative or not finite; std_decay not finite or not > 0; min_std negative, max_std not finite, min_std >
+ * max_std; t_index = 0; with GLGYM_ES_ADAM beta1 or beta2 outside [0, 1), eps not finite or not > 0, m1 or m2 NULL (with GLGYM_ES_SGD
+ * the three numbers and both pointers are ignored). */
+enum { GLGYM_ES_SGD = 0, GLGYM_ES_ADAM = 1 };
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, H;
+    int32_t optimizer;           /* GLGYM_ES_SGD | GLGYM_ES_ADAM */
+    const float* actions;        /* [H][P*K][6]: the population the utilities belong to */
+    const double* u;             /* [P*K]: glgym_plan_es_utilities */
+    const int32_t* n_adm;        /* [P] */
+    double lr, lr_std, std_decay, min_std, max_std;
+    double beta1, beta2, eps;
+    uint64_t t_index;            /* >= 1: the step count */
+    const uint64_t* t_base;      /* device word added to t_index, or NULL: a replayed graph advances it */
+    double* m1;                  /* [H][P][6] in / out (GLGYM_ES_ADAM) */
+    double* m2;
+    const float* mean;           /* [H][P][6] */
+    const float* std;
+    float* mean_out;             /* [H][P][6] out */
+    float* std_out;
+} glgym_plan_es_update_args;
+
+int glgym_plan_es_sample(glgym_handle h, const glgym_plan_es_sample_args* a, void* stream);
+int glgym_plan_es_utilities(glgym_handle h, const glgym_plan_es_utilities_args* a, void* stream);
+int glgym_plan_es_update(glgym_handle h, const glgym_plan_es_update_args* a, void* stream);
 
 /* ---- robust planning: scenario rollouts under crop noise, risk-aware scores (csrc/gl_scen.hpp, csrc/glgym_plan.hip) ----------
  * With uncertainty_scale > 0 the environment multiplies the 34 crop parameters p[128..161] by 1 + U(-scale/2, scale/2) at every
