@@ -1399,6 +1399,7 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
     // unreachable: every build select_step returns is in the lists (tests/test_step_select_host.py asserts it over the full product)
     if (!launched) { g_err = "glgym_step: no kernel was built for the selected configuration (gl_step_select.hpp)"; return GLGYM_EINVAL; }
     HIPCHK(hipGetLastError());
+    h->last_step = c; h->has_last_step = true;
     if (c.fused && fused) *fused = c.fused;
     return GLGYM_OK;
 }
@@ -1422,6 +1423,7 @@ static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const Rewar
     k.du = h->du;
     for (int j = 0; j < NU; ++j) { k.u_min[j] = h->u_min[j]; k.u_max[j] = h->u_max[j]; }
     HIPCHK(bdf_env_launch<T>(k, a->B, h->md, rw, a->metrics, st));
+    h->last_step = glsel::StepChoice{nullptr, {-1, false, false, false, false, 0, 0, 0}, 0, 0}; h->has_last_step = true;
     return GLGYM_OK;
 }
 
@@ -1459,6 +1461,16 @@ extern "C" int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream
 }
 
 extern "C" {
+
+int glgym_last_step_build(glgym_handle h, int32_t out[10])
+{
+    if (!h || !out) { g_err = "glgym_last_step_build: null handle / output"; return GLGYM_EINVAL; }
+    if (!h->has_last_step) { g_err = "glgym_last_step_build: the handle has not launched an env-step yet"; return GLGYM_EINVAL; }
+    const glsel::StepBuild& b = h->last_step.build;
+    const int32_t v[10] = {b.family, b.f64, b.crop, b.def, b.pipe, b.sch, b.epi, b.occ, (int32_t)h->last_step.grid, h->last_step.fused};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return GLGYM_OK;
+}
 
 int glgym_step_obs(glgym_handle h, const glgym_step_args* a, const glgym_obs_args* oa, void* stream)
 {

@@ -13,6 +13,7 @@
 #include "glgym.h"
 #include "gl_model.hpp"
 #include "gl_reward.hpp"
+#include "gl_step_select.hpp"
 
 extern thread_local std::string g_err;      // defined in glgym.hip
 
@@ -52,6 +53,8 @@ struct glgym_handle_s {
     int occupancy = 0;                  // glgym_set_occupancy (one-lane fp32 kernel): 0 = by batch size; initial value from GLGYM_OCC at glgym_create
     int ladder_parallel = 1;            // glgym_set_ladder_parallel: verified glgym_evalF calls may run two rungs of the ladder side by side
     int n_simd = 1024;                  // SIMDs of the device (4 per CU)
+    glsel::StepChoice last_step{};      // what the last env-step launched (glgym_last_step_build); family -1: a BDF env-step
+    bool has_last_step = false;
     float du = 0.1f, u_min[glm::NU] = {0, 0, 0, 0, 0, 0}, u_max[glm::NU] = {1, 1, 1, 1, 1, 1};   // glgym_set_control_limits
     int obs_modules[6] = {0, 1, 2, 3, 4, 5};   // observation modules in output order (glgym_set_obs_modules)
     int n_obs_modules = 6;

@@ -166,7 +166,7 @@ typedef struct {
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
- * glgym_plan_es_utilities, glgym_plan_es_update */
+ * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -359,6 +359,14 @@ int glgym_obs_dim(glgym_handle h, int Np);
  * (fp32 only).  Same scheme decision for decision in both layouts; results equal to fp32 rounding accumulated over the sub-steps
  * (measured on the storm / jump fixtures: <= 2.5e-4 scaled between the two fp32 layouts, tests/test_gpu_storm.py). */
 int glgym_step(glgym_handle h, const glgym_step_args* a, void* stream);
+/* Which build of the step kernel the handle's last successful glgym_step / glgym_step_obs / glgym_step_obs_reset launched (the list of
+ * builds and the rules that choose among them: csrc/gl_step_select.hpp).  out = family (0 one lane per environment, 1 four lanes,
+ * 2 four lanes twice: the verification ladder two rungs at a time), f64, crop (per-env crop blocks compiled in), def (the default
+ * parameter block compiled in), pipe (GLGYM_ODE_PIPE compiled in), sch (GLGYM_SCHEME_*), epi (0, 8 observation epilogue, 24 observation
+ * and auto-reset epilogue), occ (waves per SIMD the build is compiled for), grid (workgroups of 64 lanes), fused (0 the step alone,
+ * 1 the launch wrote the observation rows, 2 it also did the auto-reset).  A GLGYM_INTEGRATOR_BDF env-step records family = -1 and
+ * zeros.  Read-only host state, for tests and diagnostics; GLGYM_EINVAL before the handle's first step. */
+int glgym_last_step_build(glgym_handle h, int32_t out[10]);
 int glgym_obs(glgym_handle h, const glgym_obs_args* a, void* stream);
 /* Exactly glgym_step(h, step, stream) followed by glgym_obs(h, obs, stream) in full mode; obs->mask must be NULL (GLGYM_EINVAL).
  * Both argument blocks are checked before anything is launched.  ONE launch where the handle's configuration has a step kernel with the

@@ -359,10 +359,10 @@ def bits(a):
 
 
 class Handle:
-    """A raw glgym handle with the default parameter block, as tests/test_gpu_vecnorm.py makes its own.  nd: columns of a weather row
-    (default the model's 10; up to 16, 14 being the rows of GLGYM_ODE_PIPE)."""
+    """A raw glgym handle, as tests/test_gpu_vecnorm.py makes its own.  nd: columns of a weather row (default the model's 10; up to 16,
+    14 being the rows of GLGYM_ODE_PIPE).  params: the parameter block [208] (default: the default block)."""
 
-    def __init__(self, f64, dt=900.0, nd=None):
+    def __init__(self, f64, dt=900.0, nd=None, params=None):
         import torch
         from gl_gym_amd import _lib as L
         from gl_gym_amd.parameters import init_default_params
@@ -371,7 +371,7 @@ class Handle:
         self.T = np.float64 if f64 else np.float32
         self.lib, self.h = L.load(), C.c_void_p()
         self.nd = L.ND if nd is None else int(nd)
-        p = np.ascontiguousarray(init_default_params(L.NP), dtype=np.float64)
+        p = np.ascontiguousarray(init_default_params(L.NP) if params is None else params, dtype=np.float64)
         L.check(self.lib.glgym_create(L.NX, L.NU, self.nd, L.NP, dt, p.ctypes.data_as(L._DP), L.F64 if f64 else L.F32, 4, 0,
                                       C.byref(self.h)), "glgym_create")
 

@@ -306,9 +306,13 @@ def test_batch_properties_at_full_size():
 
 
 def test_generic_kernel_with_non_default_parameters(golden, oracle):
-    """A parameter block that differs from the default one takes the generic step kernel (constants in SGPRs
-    instead of compile-time literals) and exercises the branches the default block folds away: interlights on,
-    FIR-transparent cover, grow-pipe emissivity, roof-only ventilation switched off."""
+    """A parameter block that differs from the default one takes the generic step kernels (the handle's constants as a kernel
+    argument instead of compile-time literals: DEF = 0 in csrc/gl_step_select.hpp) and exercises the branches the default block folds
+    away: interlights on, FIR-transparent cover, grow-pipe emissivity, roof-only ventilation switched off.  At B = 64 a layout left on
+    auto takes the four-lanes-per-environment kernel, so the fp32 legs force each layout in turn -- the one-lane generic kernel and the
+    quad generic kernel -- and glgym_last_step_build says which build ran; fp64 has the quad layout only."""
+    import ctypes as C
+    from gl_gym_amd import _lib as L
     from gl_gym_amd.tomato_env import TomatoVecEnv
     w = golden("rollout_10day")["weather"]
     p = golden("params_default")["p"].astype(np.float64).copy()
@@ -318,10 +322,13 @@ def test_generic_kernel_with_non_default_parameters(golden, oracle):
     p[165] = 0.5                              # grow pipes radiate
     p[194], p[195], p[198] = 0.02, 0.8, 1.5   # interlight geometry present (their power stays 0)
     p[8] = 1.2                                # etaRoofThr > 1 -> the "else" ventilation branch
-    for dtype, tol, scheme, n_sub, order, win in (("float64", 1e-8, "rk4", 256, 4, 4), ("float32", 5e-5, "rk4", 256, 4, 4),
-                                                  ("float64", 1e-8, "ls5", 128, 5, 2), ("float32", 5e-5, "ls5", 128, 5, 2)):
+    for dtype, tol, scheme, n_sub, order, win, layout in (
+            ("float64", 1e-8, "rk4", 256, 4, 4, None), ("float32", 5e-5, "rk4", 256, 4, 4, "one"), ("float32", 5e-5, "rk4", 256, 4, 4, "quad"),
+            ("float64", 1e-8, "ls5", 128, 5, 2, None), ("float32", 5e-5, "ls5", 128, 5, 2, "one"), ("float32", 5e-5, "ls5", 128, 5, 2, "quad")):
         env = TomatoVecEnv(64, weather=w, params=p.astype(np.float32), dtype=dtype, scheme=scheme, n_sub=n_sub, season_length=1,
                            start_rows=[0, 50], seed=2, auto_reset=False)
+        if layout is not None:
+            env.set_layout(layout)
         p32 = env.p.astype(np.float64)
         env.reset()
         w_off = env.w_off_t.cpu().numpy()
@@ -331,11 +338,15 @@ def test_generic_kernel_with_non_default_parameters(golden, oracle):
             u_prev = env.u.double().cpu().numpy().copy()
             x_prev = env.x.double().cpu().numpy().copy()
             env.step(acts)
+            build = (C.c_int32 * 10)()
+            assert L.load().glgym_last_step_build(env._h, build) == L.OK
+            family, f64, _, deflt = tuple(build)[:4]
+            assert deflt == 0 and f64 == (dtype == "float64") and family == (0 if layout == "one" else 1), (dtype, layout, tuple(build))
             xg = env.x.double().cpu().numpy()
             for b in range(0, 64, 9):
                 u = np.clip(u_prev[b] + acts[b] * np.float32(0.1), 0, 1)
                 ref = oracle.rk_sc_guarded(x_prev[b], u, w[w_off[b] + k], p32, 900.0, n_sub, order, win)[0]
-                assert scaled_err(xg[b], ref) < tol, (dtype, scheme, k, b)
+                assert scaled_err(xg[b], ref) < tol, (dtype, scheme, layout, k, b)
         env.close()
 
 
