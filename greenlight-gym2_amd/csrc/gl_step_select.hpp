@@ -1,6 +1,7 @@
 // gl_step_select.hpp -- which build of the env-step kernel a glgym_step* call runs, as a pure function of what the call and the handle
 // say, and the one list of the builds that exist.  glgym.hip's launcher and tests/test_step_select_host.py both take the builds from
-// here.  Plain C++17, no HIP types: compiles with a plain host compiler like gl_reward.hpp.
+// here.  Below it the same for glgym_evalF's integrator kernels: select_evalf and the list of the 29 evalF builds.
+// Plain C++17, no HIP types: compiles with a plain host compiler like gl_reward.hpp.
 #pragma once
 
 namespace glsel {
@@ -102,6 +103,70 @@ inline StepChoice select_step(const StepSelectIn& s)
     const int fused = reset ? 2 : obs ? 1 : 0;
     return {nullptr, {ONE_LANE, false, s.crop, s.def, false, s.scheme, reset ? SCH_OBS | SCH_RESET : obs ? SCH_OBS : 0, occ2 ? 2 : 1},
             blocks(1), fused};
+}
+
+// ---- glgym_evalF: the builds that exist -----------------------------------------------------------------------------------------
+// Four lanes per row: evalf_kernel_quad<T, SCH, PIPE, CROP, PAIR> for every scheme SCH.  fp64: ODE_pipe compiled in (selected at run
+// time), plain, per-row crop blocks, PAIR.  fp32: the default ODE, shared crop parameters, plain and PAIR.
+#define GL_EVALF_QUAD_BUILDS(X)                                                                                          \
+    /* F64    PIPE   CROP   PAIR */                                                                                      \
+    X(true, true, false, false) X(true, true, true, false) X(true, true, false, true)                                    \
+    X(false, false, false, false) X(false, false, false, true)
+// One lane per row, fp32 only: evalf_kernel<float, CROP, PIPE, SCH> for every scheme SCH; the ODE_pipe build for GLGYM_SCHEME_RK4 only
+// (one_lane_build_exists).
+#define GL_EVALF_ONE_LANE_BUILDS(X)                                                                                      \
+    /* CROP   PIPE */                                                                                                    \
+    X(false, false) X(true, false) X(false, true)
+
+struct EvalfBuild {
+    int family;
+    bool f64, crop, pipe;                    // crop: per-row crop blocks compiled in; pipe: ODE_pipe compiled in
+    int sch;
+};
+constexpr bool operator==(const EvalfBuild& a, const EvalfBuild& b)
+{
+    return a.family == b.family && a.f64 == b.f64 && a.crop == b.crop && a.pipe == b.pipe && a.sch == b.sch;
+}
+
+struct EvalfSelectIn {
+    bool f64;                    // handle dtype
+    int scheme;                  // GLGYM_SCHEME_*
+    bool pipe;                   // the handle's ODE variant is GLGYM_ODE_PIPE
+    bool crop;                   // the call carries per-row parameter blocks (which differ inside the crop block only)
+    int layout;                  // glgym_set_layout 0 auto / 1 one lane / 2 quad
+    int B, n_simd;
+    bool verify;                 // glgym_set_verify is not GLGYM_VERIFY_NEVER
+    bool ladder_parallel;        // glgym_set_ladder_parallel
+};
+struct EvalfChoice {
+    const char* error;           // non-null: GLGYM_EINVAL with this text, nothing to launch
+    EvalfBuild build;
+    unsigned grid;               // workgroups of WAVE lanes
+};
+
+// Rules, in the order they apply:
+//  * ODE_pipe takes neither per-row parameter blocks nor a scheme other than RK4: an error.
+//  * pair: a verified call with ladder_parallel, no per-row blocks and 8 * B <= WAVE * n_simd lanes (at most one wavefront per SIMD at
+//    eight lanes per row), on an fp64 handle or an fp32 handle whose layout is not forced to one lane.
+//  * fp64 is always quad, ODE_pipe compiled in: the PAIR build under `pair`, else the per-row-crop build where the call carries
+//    blocks, else the plain one.
+//  * fp32 ODE_pipe: the single one-lane RK4 build, before anything else (no fp32 quad build has the pipe equation).
+//  * fp32 under `pair`: the PAIR build.
+//  * fp32 without per-row blocks takes the quad build when the layout is forced to quad, or left to auto with B <= 16 * n_simd (one
+//    round of quad wavefronts, as glgym_step).
+//  * fp32 beyond that: one lane per row, the crop build where the call carries blocks, else the plain one.
+inline EvalfChoice select_evalf(const EvalfSelectIn& s)
+{
+    if (s.pipe && (s.crop || s.scheme != RK4))
+        return {"glgym_evalF: GLGYM_ODE_PIPE supports neither per-row parameter blocks nor schemes other than GLGYM_SCHEME_RK4", {}, 0};
+    const auto blocks = [&](int lanes_per_row) { return (unsigned)(((unsigned long long)lanes_per_row * s.B + WAVE - 1) / WAVE); };
+    const bool pair = s.verify && s.ladder_parallel && !s.crop && 8ull * s.B <= (unsigned long long)WAVE * s.n_simd &&
+                      (s.f64 || s.layout != 1);
+    if (s.f64) return {nullptr, {pair ? QUAD_PAIR : QUAD, true, s.crop, true, s.scheme}, blocks(pair ? 8 : 4)};
+    if (s.pipe) return {nullptr, {ONE_LANE, false, false, true, RK4}, blocks(1)};
+    if (pair) return {nullptr, {QUAD_PAIR, false, false, false, s.scheme}, blocks(8)};
+    if (!s.crop && (s.layout == 2 || (s.layout == 0 && s.B <= 16 * s.n_simd))) return {nullptr, {QUAD, false, false, false, s.scheme}, blocks(4)};
+    return {nullptr, {ONE_LANE, false, s.crop, false, s.scheme}, blocks(1)};
 }
 
 }  // namespace glsel

@@ -811,7 +811,7 @@ __global__ __launch_bounds__(WAVE) void rhs_kernel(const double* x, const double
 // ---------------------------------------------------------------------------------------------------
 template <class T, bool PER_ENV_CROP, bool PIPE = false, int SCH = 0>
 __global__ __launch_bounds__(WAVE) void evalf_kernel(const double* x, const double* u, const double* d,
-                                                     const double* crop, int B, T dt, int n_sub, T gasR, T tCanMin,
+                                                     const double* crop, int B, T dt, int n_sub, double gasR, double tCanMin,
                                                      ModelConst<T> m, double* x_next, int rhs_only, int nd,
                                                      int* n_failed, int verify, int window)
 {
@@ -823,9 +823,11 @@ __global__ __launch_bounds__(WAVE) void evalf_kernel(const double* x, const doub
     for (int i = 0; i < 7; ++i) dd[i] = T(d[(size_t)b * nd + i]);
     CropConst<T> crLocal;
     if (PER_ENV_CROP) {
-        T pc[NCROP];
-        for (int i = 0; i < NCROP; ++i) pc[i] = T(crop[(size_t)b * NCROP + i]);
-        make_crop_const<T, T>(pc, gasR, tCanMin, crLocal);
+        // the row's crop constants from its double block, rounded to T once: what make_model_const computes on the host for a shared
+        // block, so that a block gives the same constants whether it arrives per row or as the handle's (tests/test_gpu_evalf_builds.py)
+        double pc[NCROP];
+        for (int i = 0; i < NCROP; ++i) pc[i] = crop[(size_t)b * NCROP + i];
+        make_crop_const<T, double>(pc, gasR, tCanMin, crLocal);
     }
     const CropConst<T>& cr = PER_ENV_CROP ? crLocal : m.crop;
     StepCoef<T> s;
@@ -846,7 +848,7 @@ __global__ __launch_bounds__(WAVE) void evalf_kernel(const double* x, const doub
     rk4_delta_guarded<T, PIPE, gl_order(SCH), SchemeWin<T, SCH>::value>(x0, s, m, cr, dt, n_sub, del, &failed, nullptr, verify != 0, nullptr, window);
     // a failed integration (the reference's evalF raises): the row is NaN and the call returns GLGYM_EODE
     for (int i = 0; i < NX; ++i)
-        x_next[(size_t)b * NX + i] = failed ? __builtin_nan("") : (double)x0[i] + (double)del[i];
+        x_next[(size_t)b * NX + i] = failed ? __builtin_nan("") : x[(size_t)b * NX + i] + (double)del[i];      // the caller's x: include/glgym.h
     if (failed) atomicAdd(n_failed, 1);
 }
 
@@ -1132,44 +1134,13 @@ static const ModelConst<double>& model_const(glgym_handle h, double) { return h-
 static const RewardConstBase<float>& reward_const(glgym_handle h, float) { return h->rf; }
 static const RewardConstBase<double>& reward_const(glgym_handle h, double) { return h->rd; }
 
-template <class T, int SCH>
-static void launch_evalf_sch(glgym_handle h, const ModelConst<T>& m, const double* p_used, const double* dx, const double* du,
-                             const double* dd, const double* dcrop, int B, double* dout)
-{
-    const int verify = h->verify_mode != GLGYM_VERIFY_NEVER;
-    const int pipe = h->variant == GLGYM_ODE_PIPE ? 1 : 0;
-    const dim3 grid((B + WAVE - 1) / WAVE), qgrid((4 * B + WAVE - 1) / WAVE), pgrid((8 * B + WAVE - 1) / WAVE), block(WAVE);
-    const auto go = [&](auto kernel, dim3 g, auto... tail) {
-        hipLaunchKernelGGL(kernel, g, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub, T(p_used[39]), T(p_used[162]), m,
-                           dout, tail...);
-    };
-    const auto one = [&](auto kernel) { go(kernel, grid, 0, h->nd, h->fail_dev, verify, h->window); };
-    const auto quad = [&](auto kernel, dim3 g) { go(kernel, g, h->nd, h->fail_dev, verify, pipe, h->window); };
-    // verified calls on batches that leave lanes free run the ladder two rungs at a time, two quads per row (evalf_kernel_quad<PAIR>):
-    // up to one wavefront per SIMD of the device (8 lanes per row); beyond that the sequential ladder does the same work on fewer lanes
-    const bool pair = verify && h->ladder_parallel && !dcrop && (size_t)8 * B <= (size_t)WAVE * h->n_simd &&
-                      (sizeof(T) == 8 || h->layout != GLGYM_LAYOUT_ONE);
-    if constexpr (sizeof(T) == 8) {      // fp64: four lanes per row (no one-lane fp64 integrator exists any more), the variant selected at run time
-        if (pair) quad(evalf_kernel_quad<T, SCH, true, false, true>, pgrid);
-        else if (dcrop) quad(evalf_kernel_quad<T, SCH, true, true>, qgrid);
-        else quad(evalf_kernel_quad<T, SCH, true, false>, qgrid);
-    } else {
-        if (pipe) one(evalf_kernel<T, false, true>);        // the single generic RK4 build (run_evalf)
-        else if (pair) quad(evalf_kernel_quad<T, SCH, false, false, true>, pgrid);
-        // fp32 rows without their own parameter block take the four-lanes-per-row kernel where glgym_step does (up to one round of
-        // quad wavefronts: 16 384 rows on MI355X; glgym_set_layout overrides)
-        else if (!dcrop && (h->layout == GLGYM_LAYOUT_QUAD || (h->layout == GLGYM_LAYOUT_AUTO && B <= 4 * h->n_simd * 4)))
-            quad(evalf_kernel_quad<T, SCH, false, false, false>, qgrid);
-        else if (dcrop) one(evalf_kernel<T, true, false, SCH>);
-        else one(evalf_kernel<T, false, false, SCH>);
-    }
-}
-
+// The evalF launcher: the build is chosen by glsel::select_evalf (gl_step_select.hpp, where the rules and the list of builds are) and
+// mapped to its kernel through that list.
 template <class T>
 static int run_evalf(glgym_handle h, const ModelConst<T>& m, const double* p_used, const double* dx, const double* du,
                      const double* dd, const double* dcrop, int B, double* dout, int rhs_only)
 {
-    const bool pipe = h->variant == GLGYM_ODE_PIPE;
+    const int pipe = h->variant == GLGYM_ODE_PIPE ? 1 : 0;
     if (rhs_only) {                      // the right-hand side at one state per row (test hook): one lane per row in either dtype
         const dim3 grid((B + WAVE - 1) / WAVE), block(WAVE);
         if (pipe) hipLaunchKernelGGL((rhs_kernel<T, false, true>), grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(p_used[39]), T(p_used[162]), m, dout, h->nd);
@@ -1178,12 +1149,41 @@ static int run_evalf(glgym_handle h, const ModelConst<T>& m, const double* p_use
         HIPCHK(hipGetLastError());
         return GLGYM_OK;
     }
-    if (pipe && (dcrop || h->scheme != GLGYM_SCHEME_RK4)) {
-        g_err = "glgym_evalF: GLGYM_ODE_PIPE supports neither per-row parameter blocks nor schemes other than GLGYM_SCHEME_RK4";
-        return GLGYM_EINVAL;
-    }
-    with_scheme(h->scheme, [&](auto sch) { launch_evalf_sch<T, decltype(sch)::value>(h, m, p_used, dx, du, dd, dcrop, B, dout); });
+    const int verify = h->verify_mode != GLGYM_VERIFY_NEVER;
+    glsel::EvalfSelectIn in;
+    in.f64 = sizeof(T) == 8; in.scheme = h->scheme; in.pipe = pipe != 0; in.crop = dcrop != nullptr; in.layout = h->layout;
+    in.B = B; in.n_simd = h->n_simd; in.verify = verify != 0; in.ladder_parallel = h->ladder_parallel != 0;
+    const glsel::EvalfChoice c = glsel::select_evalf(in);
+    if (c.error) { g_err = c.error; return GLGYM_EINVAL; }
+    const dim3 grid(c.grid), block(WAVE);
+    const glsel::EvalfBuild& b = c.build;
+    const auto go = [&](auto kernel, auto gasR, auto tCanMin, auto... tail) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)0, dx, du, dd, dcrop, B, T(h->dt), h->n_sub, gasR, tCanMin, m, dout, tail...);
+    };
+    bool launched = false;
+    with_scheme(b.sch, [&](auto sch) {
+        constexpr int SCH = decltype(sch)::value;
+#define GL_LAUNCH_QUAD(F64, PIPE, CROP, PAIR)                                                                                         \
+        if constexpr (F64 == (sizeof(T) == 8))                                                                                       \
+            if (!launched && b == glsel::EvalfBuild{PAIR ? glsel::QUAD_PAIR : glsel::QUAD, F64, CROP, PIPE, SCH}) {                   \
+                go(evalf_kernel_quad<T, SCH, PIPE, CROP, PAIR>, T(p_used[39]), T(p_used[162]), h->nd, h->fail_dev, verify, pipe, h->window); \
+                launched = true;                                                                                                     \
+            }
+        GL_EVALF_QUAD_BUILDS(GL_LAUNCH_QUAD)
+#undef GL_LAUNCH_QUAD
+#define GL_LAUNCH_ONE(CROP, PIPE)                                                                                                     \
+        if constexpr (sizeof(T) == 4 && glsel::one_lane_build_exists(PIPE, SCH))                                                     \
+            if (!launched && b == glsel::EvalfBuild{glsel::ONE_LANE, false, CROP, PIPE, SCH}) {                                      \
+                go(evalf_kernel<T, CROP, PIPE, SCH>, p_used[39], p_used[162], 0, h->nd, h->fail_dev, verify, h->window); \
+                launched = true;                                                                                                     \
+            }
+        GL_EVALF_ONE_LANE_BUILDS(GL_LAUNCH_ONE)
+#undef GL_LAUNCH_ONE
+    });
+    // unreachable: every build select_evalf returns is in the lists (tests/test_step_select_host.py asserts it over the full product)
+    if (!launched) { g_err = "glgym_evalF: no kernel was built for the selected configuration (gl_step_select.hpp)"; return GLGYM_EINVAL; }
     HIPCHK(hipGetLastError());
+    h->last_evalf = c; h->last_evalf_pipe = pipe; h->last_evalf_rows = B; h->has_last_evalf = true;
     return GLGYM_OK;
 }
 
@@ -1253,6 +1253,8 @@ static int evalf_impl(glgym_handle h, const double* x, const double* u, const do
         h->stats.resize((size_t)B * GLGYM_NSOLVER_STAT);
         HIPCHK(hipMemcpy(h->stats.data(), h->stats_dev, h->stats.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         h->stats_rows = B;
+        h->last_evalf = glsel::EvalfChoice{nullptr, {-1, false, false, false, 0}, 0}; h->last_evalf_pipe = 0; h->last_evalf_rows = B;
+        h->has_last_evalf = true;
     } else {
         rc = with_dtype(h->dtype, [&](auto t) {
             using T = decltype(t);
@@ -1297,6 +1299,16 @@ int glgym_evalF(glgym_handle h, const double* x, const double* u, const double* 
 int glgym_rhs(glgym_handle h, const double* x, const double* u, const double* d, int B, double* dx)
 {
     return evalf_impl(h, x, u, d, nullptr, 1, B, dx, 1);
+}
+
+int glgym_last_evalf_build(glgym_handle h, int32_t out[8])
+{
+    if (!h || !out) { g_err = "glgym_last_evalf_build: null handle / output"; return GLGYM_EINVAL; }
+    if (!h->has_last_evalf) { g_err = "glgym_last_evalf_build: the handle has not launched a glgym_evalF yet"; return GLGYM_EINVAL; }
+    const glsel::EvalfBuild& b = h->last_evalf.build;
+    const int32_t v[8] = {b.family, b.f64, b.crop, b.pipe, h->last_evalf_pipe, b.sch, (int32_t)h->last_evalf.grid, h->last_evalf_rows};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return GLGYM_OK;
 }
 
 }  // extern "C"

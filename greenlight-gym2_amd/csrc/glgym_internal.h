@@ -55,6 +55,9 @@ struct glgym_handle_s {
     int n_simd = 1024;                  // SIMDs of the device (4 per CU)
     glsel::StepChoice last_step{};      // what the last env-step launched (glgym_last_step_build); family -1: a BDF env-step
     bool has_last_step = false;
+    glsel::EvalfChoice last_evalf{};    // what the last glgym_evalF launched (glgym_last_evalf_build); family -1: a BDF call
+    int last_evalf_pipe = 0, last_evalf_rows = 0;      // whether that launch integrated ODE_pipe; its rows
+    bool has_last_evalf = false;
     float du = 0.1f, u_min[glm::NU] = {0, 0, 0, 0, 0, 0}, u_max[glm::NU] = {1, 1, 1, 1, 1, 1};   // glgym_set_control_limits
     int obs_modules[6] = {0, 1, 2, 3, 4, 5};   // observation modules in output order (glgym_set_obs_modules)
     int n_obs_modules = 6;

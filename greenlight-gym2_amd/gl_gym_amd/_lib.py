@@ -348,6 +348,7 @@ PROTOTYPES = {
     "glgym_step_obs_reset": (C.c_int, [C.c_void_p, C.POINTER(StepArgs), C.POINTER(ObsArgs), C.POINTER(ResetArgs), C.c_void_p,
                              C.POINTER(C.c_int32)]),
     "glgym_last_step_build": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "glgym_last_evalf_build": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "glgym_set_obs_modules": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "glgym_obs_dim": (C.c_int, [C.c_void_p, C.c_int]),
     "glgym_set_control_limits": (C.c_int, [C.c_void_p, _DP, _DP, C.c_double]),

@@ -166,7 +166,7 @@ typedef struct {
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
- * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build */
+ * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -300,10 +300,20 @@ int glgym_set_model_variant(glgym_handle h, int variant);   /* GLGYM_ODE_PIPE ne
 int glgym_set_reward(glgym_handle h, const glgym_reward_cfg* cfg);
 int glgym_get_reward_scale(glgym_handle h, double* max_profit, double* min_profit, double* fixed_costs);
 
-/* Host pointers, row-major, double.  p_rows = 1 (one block for all rows) or B.  Synchronous. */
+/* Host pointers, row-major, double.  p_rows = 1 (one block for all rows) or B.  Synchronous.
+ * The returned state is the caller's double x plus the increment computed in the handle's dtype: on a GLGYM_F32 handle the integration
+ * starts from float(x), and the bits of x below fp32 spacing come back in x_next unchanged, in every build alike. */
 int glgym_evalF(glgym_handle h, const double* x, const double* u, const double* d, const double* p, int p_rows,
                 int B, double* x_next);
 int glgym_rhs(glgym_handle h, const double* x, const double* u, const double* d, int B, double* dx);
+/* Which build of the integrator kernels the handle's last glgym_evalF launched (the list of builds and the rules that choose among them:
+ * csrc/gl_step_select.hpp, select_evalf).  out = family (0 one lane per row, 1 four lanes, 2 four lanes twice: the verification ladder
+ * two rungs at a time), f64, crop (per-row crop blocks compiled in), pipe (GLGYM_ODE_PIPE compiled in), whether the launch integrated
+ * GLGYM_ODE_PIPE (the fp64 builds choose at run time), sch (GLGYM_SCHEME_*), grid (workgroups of 64 lanes), rows (B of the launch).  A
+ * GLGYM_INTEGRATOR_BDF call records family = -1, zeros and its rows.  A call that returns GLGYM_EINVAL leaves the record as it was, and
+ * so does glgym_rhs; a call that falls back to one launch per row (parameter blocks that differ outside p[128..161]) leaves the record of
+ * its last row.  Read-only host state, for tests and diagnostics; GLGYM_EINVAL before the handle's first glgym_evalF. */
+int glgym_last_evalf_build(glgym_handle h, int32_t out[8]);
 
 /* Integrator of glgym_evalF (ABI 7).  GLGYM_INTEGRATOR_EXPLICIT (default): the sub-stepping scheme above (glgym_set_scheme,
  * glgym_set_n_sub, glgym_set_window, glgym_set_verify).  GLGYM_INTEGRATOR_BDF: the algorithm family of the reference's CVODES

@@ -105,6 +105,8 @@ def stepselect_host(build_dir):
     lib = C.CDLL(str(so))
     lib.stepselect_batch.argtypes, lib.stepselect_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
     lib.stepselect_builds.argtypes, lib.stepselect_builds.restype = [C.c_void_p, C.c_int], C.c_int
+    lib.evalfselect_batch.argtypes, lib.evalfselect_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
+    lib.evalfselect_builds.argtypes, lib.evalfselect_builds.restype = [C.c_void_p, C.c_int], C.c_int
     return lib
 
 

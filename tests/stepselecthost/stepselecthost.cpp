@@ -52,4 +52,41 @@ int stepselect_builds(int* out, int cap)
     return n;
 }
 
+// ---- glgym_evalF (tests/test_step_select_host.py, tests/test_evalf_build_inputs_host.py) ----
+// in: n rows of 9 ints, EvalfSelectIn's fields in their order; out: n rows of 7 ints: error (0/1), the build's 5 fields, grid
+void evalfselect_batch(int n, const int* in, int* out)
+{
+    for (int r = 0; r < n; ++r, in += 9, out += 7) {
+        const EvalfSelectIn s{in[0] != 0, in[1], in[2] != 0, in[3] != 0, in[4], in[5], in[6], in[7] != 0, in[8] != 0};
+        const EvalfChoice c = select_evalf(s);
+        out[0] = c.error != nullptr;
+        out[1] = c.build.family; out[2] = c.build.f64; out[3] = c.build.crop; out[4] = c.build.pipe; out[5] = c.build.sch;
+        out[6] = (int)c.grid;
+    }
+}
+
+const char* evalfselect_error_text()
+{
+    return select_evalf(EvalfSelectIn{false, RK4, true, true, 0, 1, 1, false, false}).error;
+}
+
+// the evalF build list as rows of 5 ints (at most cap rows are written); returns the number of builds
+int evalfselect_builds(int* out, int cap)
+{
+    int n = 0;
+    const auto row = [&](int family, bool f64, bool crop, bool pipe, int sch) {
+        if (n < cap) { int* o = out + 5 * n; o[0] = family; o[1] = f64; o[2] = crop; o[3] = pipe; o[4] = sch; }
+        ++n;
+    };
+    for (int sch = 0; sch < 4; ++sch) {
+#define ROW_QUAD(F64, PIPE, CROP, PAIR) row(PAIR ? QUAD_PAIR : QUAD, F64, CROP, PIPE, sch);
+        GL_EVALF_QUAD_BUILDS(ROW_QUAD)
+#undef ROW_QUAD
+#define ROW_ONE(CROP, PIPE) if (one_lane_build_exists(PIPE, sch)) row(ONE_LANE, false, CROP, PIPE, sch);
+        GL_EVALF_ONE_LANE_BUILDS(ROW_ONE)
+#undef ROW_ONE
+    }
+    return n;
+}
+
 }  // extern "C"

@@ -18,7 +18,8 @@ difference to one spacing of the dtype at x[25] -- a bound from the number forma
 exact.  Siblings -- epilogue builds against the plain build and the unfused sequence, PAIR against the sequential ladder, B = 1 against
 row 0 of B = 65 -- are compared bit for bit.
 
-Not reached: the fp64 quad builds have ODE_pipe compiled in and select it at run time; every case runs them on the default ODE.  The
+Not reached: the fp64 quad builds have ODE_pipe compiled in and select it at run time; every case runs them on the default ODE (the
+same run-time branch of glgym_evalF's fp64 builds is tied to the oracle by tests/test_gpu_evalf_builds.py, the evalF census).  The
 one-lane ODE_pipe build runs with all 65 rows refined and is compared with the level of the one-lane rk4 builds of the default ODE
 (siblings()).  The fp32 verified rk2 runs measure 3.9e-6 .. 4.0e-6 of the 5e-6 bound in every family alike: little margin.
 

@@ -29,6 +29,9 @@ def host(tmp_path_factory):
     lib.stepselect_batch.argtypes, lib.stepselect_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
     lib.stepselect_builds.argtypes, lib.stepselect_builds.restype = [C.c_void_p, C.c_int], C.c_int
     lib.stepselect_error_text.restype = C.c_char_p
+    lib.evalfselect_batch.argtypes, lib.evalfselect_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
+    lib.evalfselect_builds.argtypes, lib.evalfselect_builds.restype = [C.c_void_p, C.c_int], C.c_int
+    lib.evalfselect_error_text.restype = C.c_char_p
     return lib
 
 
@@ -103,5 +106,84 @@ def test_every_selected_build_is_listed_and_every_listed_build_is_selected(host,
     _, out = selected
     chosen = {tuple(r) for r in out[out[:, 0] == 0][:, 1:9].tolist()}
     listed = {tuple(r) for r in builds(host).tolist()}
+    assert chosen - listed == set(), sorted(chosen - listed)[:5]
+    assert listed - chosen == set(), sorted(listed - chosen)[:5]
+
+
+# ---- glgym_evalF: select_evalf and the list of the 29 evalF builds --------------------------------------------------------------------
+EVALF_FIELDS = ("f64", "scheme", "pipe", "crop", "layout", "B", "n_simd", "verify", "ladder_parallel")
+
+
+def evalf_inputs():
+    """The full product: [n, 9] int32."""
+    rows = itertools.product((0, 1), (RK4, RK2, RK3, LS5), (0, 1), (0, 1), (0, 1, 2), (1, 8, 65, 8192, 8193, 16384, 16385), (256, 1024),
+                             (0, 1), (0, 1))
+    return np.array(list(rows), dtype=np.int32)
+
+
+def evalf_restated(f64, scheme, pipe, crop, layout, B, n_simd, verify, ladder_parallel):
+    """(error, family, f64, crop, pipe compiled in, scheme, grid) by the documented rules (include/glgym.h at glgym_set_ladder_parallel
+    and glgym_step's layouts)."""
+    if pipe and (crop or scheme != RK4):
+        return (1, 0, 0, 0, 0, 0, 0)
+    free_lanes = 8 * B <= 64 * n_simd                      # at most one wavefront per SIMD at eight lanes per row
+    two_rungs = bool(verify and ladder_parallel and not crop and free_lanes)
+    if f64:                                                # four lanes per row always, ODE_pipe compiled in, per-row crop blocks taken
+        lanes = 8 if two_rungs else 4
+        return (0, QUAD_PAIR if two_rungs else QUAD, 1, crop, 1, scheme, -(-lanes * B // 64))
+    if pipe:                                               # the only fp32 kernel with the pipe equation
+        return (0, ONE_LANE, 0, 0, 1, RK4, -(-B // 64))
+    if two_rungs and layout != 1:                          # a forced one-lane layout keeps the sequential ladder
+        return (0, QUAD_PAIR, 0, 0, 0, scheme, -(-8 * B // 64))
+    if not crop and (layout == 2 or (layout == 0 and B <= 16 * n_simd)):
+        return (0, QUAD, 0, 0, 0, scheme, -(-4 * B // 64))
+    return (0, ONE_LANE, 0, crop, 0, scheme, -(-B // 64))
+
+
+def evalf_builds(host):
+    n = host.evalfselect_builds(None, 0)
+    out = np.zeros((n, 5), dtype=np.int32)
+    assert host.evalfselect_builds(out.ctypes.data, n) == n
+    return out
+
+
+@pytest.fixture(scope="module")
+def evalf_selected(host):
+    rows = evalf_inputs()
+    out = np.full((len(rows), 7), -7, dtype=np.int32)
+    host.evalfselect_batch(len(rows), rows.ctypes.data, out.ctypes.data)
+    return rows, out
+
+
+def test_evalf_selection_matches_the_documented_rules(evalf_selected):
+    rows, out = evalf_selected
+    assert len(rows) == 2 * 4 * 2 * 2 * 3 * 7 * 2 * 2 * 2
+    want = np.array([evalf_restated(*r) for r in rows.tolist()], dtype=np.int32)
+    err = want[:, 0] == 1
+    assert np.array_equal(out[:, 0], want[:, 0])
+    bad = np.nonzero((out[~err] != want[~err]).any(axis=1))[0]
+    assert len(bad) == 0, (dict(zip(EVALF_FIELDS, rows[~err][bad[0]].tolist())), out[~err][bad[0]].tolist(), want[~err][bad[0]].tolist())
+
+
+def test_evalf_error_text(host):
+    assert host.evalfselect_error_text() == (b"glgym_evalF: GLGYM_ODE_PIPE supports neither per-row parameter blocks nor schemes other "
+                                             b"than GLGYM_SCHEME_RK4")
+
+
+def test_evalf_build_list_is_the_29_kernels(host):
+    b = evalf_builds(host)
+    assert len(b) == 29 and len({tuple(r) for r in b.tolist()}) == 29
+    one, quad = b[b[:, 0] == ONE_LANE], b[b[:, 0] != ONE_LANE]
+    assert len(one) == 4 * 2 + 1 and len(quad) == 4 * 5
+    assert not one[:, 1].any() and (quad[:, 1] == 1).sum() == 4 * 3                  # one lane per row: fp32 only
+    assert (b[:, 0] == QUAD_PAIR).sum() == 4 * 2 and not b[b[:, 0] == QUAD_PAIR][:, 2].any()     # PAIR: both dtypes, never with crop blocks
+    assert b[b[:, 1] == 1][:, 3].all()                                               # ODE_pipe: compiled into every fp64 build ...
+    assert b[(b[:, 1] == 0) & (b[:, 3] == 1)].tolist() == [[ONE_LANE, 0, 0, 1, RK4]]  # ... and into one fp32 build
+
+
+def test_every_selected_evalf_build_is_listed_and_every_listed_build_is_selected(host, evalf_selected):
+    _, out = evalf_selected
+    chosen = {tuple(r) for r in out[out[:, 0] == 0][:, 1:6].tolist()}
+    listed = {tuple(r) for r in evalf_builds(host).tolist()}
     assert chosen - listed == set(), sorted(chosen - listed)[:5]
     assert listed - chosen == set(), sorted(listed - chosen)[:5]
