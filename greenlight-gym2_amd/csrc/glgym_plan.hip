@@ -26,6 +26,12 @@
 // h), three 16-byte stores per lane and plane.  utilities: the elites' grid and counting, one utility stored per candidate.  update: one
 // wavefront per (row, plane), lanes stride over the pairs, one pass over the plane's K rows, lane 0 steps mean, std and moments.
 //
+// The CMA-ES stages (glgym_plan_cma_sample / _cma_update; scalar logic in gl_cma.hpp, instantiated on the host by
+// tests/cmahost/cmahost.cpp).  sample: lane = child, the children of a block from one row, whose Cholesky factor sits in LDS (broadcast
+// reads); y = chol z is accumulated column by column in registers.  update: one block per row; the elites' y pass through LDS in tiles,
+// every sum over the elites runs sequentially in the thread that owns its output, the Cholesky factorisation with lanes on rows; the
+// new state waits in LDS until the row's status is known.
+//
 // Robust planning (glgym_plan_scenario / _aggregate; scalar logic in gl_scen.hpp, instantiated on the host by
 // tests/scenhost/scenhost.cpp).  scenario: lane = child, the prologue of one env-step of a scenario rollout -- the child's crop block
 // for this step and its row of the expanded action plane.  aggregate: one wavefront per candidate, its S <= 256 scenario returns
@@ -57,6 +63,7 @@
 #include "glgym_internal.h"
 
 #include "gl_cem.hpp"
+#include "gl_cma.hpp"
 #include "gl_es.hpp"
 #include "gl_mlp.hpp"
 #include "gl_plan.hpp"
@@ -360,6 +367,180 @@ __global__ __launch_bounds__(WAVE) void plan_es_update_kernel(glgym_plan_es_upda
     const uint64_t t = a.t_index + (a.t_base ? *a.t_base : 0ull);
     const bool keep = a.n_adm[p] < 2 || t == 0 || !gles::finite6(g) || !gles::finite6(s);
     gles::update_row(hp, t, keep, g, s, a.mean + o, a.std + o, a.m1 ? a.m1 + o : nullptr, a.m2 ? a.m2 + o : nullptr, a.mean_out + o, a.std_out + o);
+}
+
+// ---- the CMA-ES stages (gl_cma.hpp) -------------------------------------------------------------------------------------------------
+// grid = P * ceil(K / 256) blocks of four wavefronts: block (p, i) samples the children k = i*256 .. i*256 + 255 of row p, lane = child.
+// The row's factor is staged in LDS once per block (N*N doubles, at most 8 KB); every later read of it is a broadcast.  A lane keeps
+// its y in registers (unrolled indices, no scratch) and stores 6 consecutive floats per plane: 1 536 contiguous bytes per wavefront.
+constexpr int CMA_THREADS = 256;
+__global__ __launch_bounds__(CMA_THREADS) void plan_cma_sample_kernel(glgym_plan_cma_sample_args a, int n_chunks)
+{
+    __shared__ double s_chol[glcma::NMAX * glcma::NMAX];
+    const int p = blockIdx.x / n_chunks, tid = threadIdx.x, N = a.N;
+    const double* chol = a.chol + (size_t)p * N * N;
+    for (int i = tid; i < N * N; i += CMA_THREADS) s_chol[i] = chol[i];
+    __syncthreads();
+    const int k = (blockIdx.x - p * n_chunks) * CMA_THREADS + tid;
+    if (k >= a.K) return;                               // no barrier below
+    const uint64_t D = a.draw_index + (a.draw_base ? *a.draw_base : 0ull);
+    glcma::sample_child(p * a.K + k, p, a.P, a.K, N, D, a.seed, s_chol, a.mean, a.sigma[p], a.theta);
+}
+
+// grid = P, one block of four wavefronts per row.  The elites' y pass through LDS in tiles of min(256, 1 024 / N) elites (any E; a
+// thread stages up to four values of a tile, index loads first, so that their latencies overlap); thread d < N owns yw[d] and every
+// thread up to three entries (a, b <= a) of R -- the lower triangle's N (N + 1) / 2 entries are numbered row by row and dealt out
+// 256 at a time -- each summed over the elites in ascending order by its owner alone.  The sequential parts -- forward substitution,
+// the paths, the Cholesky factorisation -- run in wavefront 0 with lanes on rows (N <= 32 <= 64); a finished value reaches the other
+// lanes by a shuffle or through LDS.  Every new value waits in LDS or in a register until the row's status is known; then the block
+// commits all of them or none.  LDS: 8 KB of y, 2 KB of weights, 8 KB for the old and then the new factor, 8 KB of cov', a few vectors.
+// row a of entry idx of the lower triangle numbered row by row (entry idx = a (a + 1) / 2 + b, b <= a)
+__device__ __forceinline__ int cma_tri_row(int idx)
+{
+    int a = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
+    while (a * (a + 1) / 2 > idx) --a;
+    while ((a + 1) * (a + 2) / 2 <= idx) ++a;
+    return a;
+}
+
+__global__ __launch_bounds__(CMA_THREADS) void plan_cma_update_kernel(glgym_plan_cma_update_args a)
+{
+    constexpr int NM = glcma::NMAX, NT = CMA_THREADS, SLOTS = NM * NM, TE_MAX = 256, STAGE = SLOTS / NT;
+    constexpr int PER = (NM * (NM + 1) / 2 + NT - 1) / NT;
+    __shared__ double s_y[SLOTS];                       // [e][d] with rows of N: TE * N <= 1 024
+    __shared__ double s_w[TE_MAX];
+    __shared__ double s_chol[NM * NM];
+    __shared__ double s_cov[NM * NM];
+    __shared__ double s_pc[NM];
+    __shared__ float s_m[NM];
+    __shared__ double s_a0;
+    const glcma::Hyper hp{a.mu_eff, a.c_sigma, a.d_sigma, a.c_c, a.c_1, a.c_mu, a.chi_n, a.min_sigma, a.max_sigma};
+    const int p = blockIdx.x, tid = threadIdx.x, N = a.N, E = a.E, K = a.K, NN = N * N, n_tri = N * (N + 1) / 2;
+    const int TE = SLOTS / N < TE_MAX ? SLOTS / N : TE_MAX;
+    const uint64_t t = a.t_index + (a.t_base ? *a.t_base : 0ull);
+    const int32_t* elite = a.elite_k + (size_t)p * E;
+    const size_t n_child = (size_t)a.P * K, first = (size_t)p * K, oN = (size_t)p * N, oNN = (size_t)p * NN;
+    int bad_e = 0;
+    for (int e = tid; e < E; e += NT) bad_e |= (elite[e] < 0 || elite[e] >= K) ? 1 : 0;
+    const bool few = __syncthreads_or(bad_e) != 0 || a.n_elite[p] < E;
+    if (t == 0 || few) {                                // block-uniform
+        if (tid == 0) a.status[p] = t == 0 ? glcma::T_ZERO : glcma::FEW_ELITES;
+        return;
+    }
+    const double sigma = a.sigma[p];
+    for (int i = tid; i < NN; i += NT) s_chol[i] = a.chol[oNN + i];
+    if (tid < N) s_m[tid] = a.mean[((size_t)(tid / NU) * a.P + p) * NU + tid % NU];
+    __syncthreads();
+    double yw = 0.0, R[PER];
+    int ra[PER], rb[PER];                               // this thread's entries (a, b <= a) of the lower triangle; a = -1: none
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int idx = tid + r * NT;
+        R[r] = 0.0;
+        ra[r] = idx < n_tri ? cma_tri_row(idx) : -1;
+        rb[r] = idx < n_tri ? idx - ra[r] * (ra[r] + 1) / 2 : 0;
+    }
+    for (int e0 = 0; e0 < E; e0 += TE) {                // block-uniform trip count: every thread reaches both barriers
+        const int ne = E - e0 < TE ? E - e0 : TE, n_val = ne * N;
+        int kk[STAGE];
+        float xx[STAGE];
+#pragma unroll
+        for (int r = 0; r < STAGE; ++r) {
+            const int idx = tid + r * NT;
+            kk[r] = idx < n_val ? elite[e0 + idx / N] : 0;
+        }
+#pragma unroll
+        for (int r = 0; r < STAGE; ++r) {
+            const int idx = tid + r * NT, d = idx % N;
+            xx[r] = idx < n_val ? a.theta[((size_t)(d / NU) * n_child + first + kk[r]) * NU + d % NU] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < STAGE; ++r) {
+            const int idx = tid + r * NT;
+            if (idx < n_val) s_y[idx] = glcma::elite_y(xx[r], s_m[idx % N], sigma);
+        }
+        if (tid < ne) s_w[tid] = a.w_dev[e0 + tid];
+        __syncthreads();
+        if (tid < N)
+            for (int e = 0; e < ne; ++e) yw = glcma::add_yw(yw, s_w[e], s_y[e * N + tid]);
+#pragma unroll
+        for (int r = 0; r < PER; ++r)
+            if (ra[r] >= 0)
+                for (int e = 0; e < ne; ++e) R[r] = glcma::add_r(R[r], s_w[e], s_y[e * N + ra[r]], s_y[e * N + rb[r]]);
+        __syncthreads();                                // the tile has been read by everyone
+    }
+    // wavefront 0, lane d = component d: forward substitution, the paths, the mean, the step size
+    double ps_new = 0.0, pc_new = 0.0, sig_new = 0.0;
+    float mean_new = 0.f;
+    int bad = 0;
+    if (tid < WAVE) {                                   // wave-uniform
+        const int d = tid;
+        const bool mine = d < N;
+        double acc = mine ? yw : 0.0, zw = 0.0;
+        for (int j = 0; j < N; ++j) {
+            double zc = 0.0;
+            if (d == j) zc = acc / s_chol[d * N + d];
+            const double zj = __shfl(zc, j, WAVE);
+            if (d == j) zw = zj;
+            if (mine && d > j) acc = glcma::fsub_take(acc, s_chol[d * N + j], zj);
+        }
+        const double qs = glcma::q_of(hp.c_sigma, hp.mu_eff), qc = glcma::q_of(hp.c_c, hp.mu_eff);
+        ps_new = mine ? glcma::blend(hp.c_sigma, a.p_sigma[oN + d], glcma::times(qs, zw)) : 0.0;
+        double n2 = 0.0;
+        for (int j = 0; j < N; ++j) n2 = glcma::add_sq(n2, __shfl(ps_new, j, WAVE));
+        const double nrm = sqrt(n2);
+        const bool hs = glcma::h_sigma(hp, N, t, nrm);
+        pc_new = mine ? glcma::blend(hp.c_c, a.p_c[oN + d], hs ? glcma::times(qc, yw) : 0.0) : 0.0;
+        mean_new = mine ? glcma::new_mean(s_m[mine ? d : 0], sigma, yw) : 0.f;
+        sig_new = glcma::new_sigma(hp, sigma, nrm);
+        if (mine) s_pc[d] = pc_new;
+        if (tid == 0) s_a0 = glcma::a0_of(hp, hs);
+        bad = !(std::isfinite(ps_new) && std::isfinite(pc_new) && std::isfinite(mean_new) && std::isfinite(sig_new)) ? 1 : 0;
+    }
+    __syncthreads();                                    // p_c' and a0 are there; the old factor is not read again
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int ai = ra[r], bi = rb[r];
+        if (ai >= 0) {
+            const double v = glcma::cov_entry(hp, s_a0, a.cov[oNN + ai * N + bi], s_pc[ai], s_pc[bi], R[r]);
+            s_cov[ai * N + bi] = v;
+            s_cov[bi * N + ai] = v;
+            bad |= std::isfinite(v) ? 0 : 1;
+        }
+    }
+    for (int i = tid; i < NN; i += NT) s_chol[i] = 0.0;
+    int status = __syncthreads_or(bad) != 0 ? glcma::NOT_FINITE : glcma::UPDATED;
+    if (status == glcma::UPDATED) {                     // block-uniform
+        int pivot_bad = 0;
+        for (int j = 0; j < N; ++j) {                   // lanes on rows i >= j, j sequential
+            if (tid < WAVE) {
+                const int i = tid;
+                const bool work = i >= j && i < N;
+                const double v = work ? glcma::chol_take(s_cov[i * N + j], s_chol + i * N, s_chol + j * N, j) : 0.0;
+                const double s = __shfl(v, j, WAVE);
+                pivot_bad |= s > 0.0 ? 0 : 1;
+                const double piv = sqrt(s);
+                if (work) s_chol[i * N + j] = i == j ? piv : v / piv;
+            }
+            __syncthreads();                            // column j is there
+        }
+        int inf = 0;
+        for (int i = tid; i < NN; i += NT) inf |= std::isfinite(s_chol[i]) ? 0 : 1;
+        const bool np = __syncthreads_or(pivot_bad) != 0, nf = __syncthreads_or(inf) != 0;
+        status = np ? glcma::NOT_POSITIVE : (nf ? glcma::NOT_FINITE : glcma::UPDATED);
+    }
+    if (tid == 0) a.status[p] = status;
+    if (status != glcma::UPDATED) return;               // the row keeps its bits
+    for (int i = tid; i < NN; i += NT) {
+        a.cov[oNN + i] = s_cov[i];
+        a.chol[oNN + i] = s_chol[i];
+    }
+    if (tid < N) {
+        a.p_sigma[oN + tid] = ps_new;
+        a.p_c[oN + tid] = pc_new;
+        a.mean[((size_t)(tid / NU) * a.P + p) * NU + tid % NU] = mean_new;
+    }
+    if (tid == 0) a.sigma[p] = sig_new;
 }
 
 // grid = ceil(C / 256), lane = child c = (p*K + k)*S + s: nine Philox blocks keyed by (p*S + s, step) -- the S children of a candidate
@@ -720,6 +901,67 @@ int glgym_plan_es_update(glgym_handle h, const glgym_plan_es_update_args* a, voi
     if (!h) return refuse("null handle");
     DeviceGuard dev_guard(h);
     hipLaunchKernelGGL(plan_es_update_kernel, dim3(a->P, a->H), dim3(WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+// the CMA-ES stages (gl_cma.hpp): checked before the handle is looked at, one text per mistake
+static bool cma_shape_ok(const char* who, int32_t P, int32_t K, int32_t N)
+{
+    const std::string w(who);
+    if (P < 1 || K < 1) { g_err = w + ": P or K < 1"; return false; }
+    if (N < 1 || N > GLGYM_CMA_NMAX) { g_err = w + ": N outside 1..GLGYM_CMA_NMAX = " + std::to_string(GLGYM_CMA_NMAX); return false; }
+    if ((int64_t)P * K > INT32_MAX - 255) { g_err = w + ": P * K past INT32_MAX - 255 (the lane indices would wrap)"; return false; }
+    return true;
+}
+
+int glgym_plan_cma_sample(glgym_handle h, const glgym_plan_cma_sample_args* a, void* stream)
+{
+    const char* who = "glgym_plan_cma_sample";
+    if (!a) { g_err = std::string(who) + ": null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok(who, a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!cma_shape_ok(who, a->P, a->K, a->N)) return GLGYM_EINVAL;
+    if (!a->mean || !a->sigma || !a->chol || !a->theta) { g_err = std::string(who) + ": null mean, sigma, chol or theta"; return GLGYM_EINVAL; }
+    if (!h) { g_err = std::string(who) + ": null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    const int n_chunks = (a->K + CMA_THREADS - 1) / CMA_THREADS;
+    hipLaunchKernelGGL(plan_cma_sample_kernel, dim3((unsigned)((int64_t)a->P * n_chunks)), dim3(CMA_THREADS), 0, (hipStream_t)stream, *a, n_chunks);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+int glgym_plan_cma_update(glgym_handle h, const glgym_plan_cma_update_args* a, void* stream)
+{
+    const char* who = "glgym_plan_cma_update";
+    const auto refuse = [&](const std::string& why) { g_err = std::string(who) + ": " + why; return (int)GLGYM_EINVAL; };
+    if (!a) return refuse("null arguments");
+    if (!plan_size_ok(who, a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (!cma_shape_ok(who, a->P, a->K, a->N)) return GLGYM_EINVAL;
+    if (a->E < 1 || a->E > a->K) return refuse("E outside 1..K");
+    if (!a->theta || !a->elite_k || !a->n_elite || !a->w || !a->w_dev || !a->mean || !a->sigma || !a->cov || !a->chol || !a->p_sigma ||
+        !a->p_c || !a->status)
+        return refuse("null theta, elite_k, n_elite, w, w_dev, mean, sigma, cov, chol, p_sigma, p_c or status");
+    const struct { const char* name; double v; } consts[] = {{"mu_eff", a->mu_eff}, {"c_sigma", a->c_sigma}, {"d_sigma", a->d_sigma},
+        {"c_c", a->c_c}, {"c_1", a->c_1}, {"c_mu", a->c_mu}, {"chi_n", a->chi_n}, {"min_sigma", a->min_sigma}, {"max_sigma", a->max_sigma}};
+    for (const auto& c : consts)
+        if (!std::isfinite(c.v)) return refuse(std::string(c.name) + " is not finite");
+    for (int32_t e = 0; e < a->E; ++e) {
+        if (!std::isfinite(a->w[e])) return refuse("weight " + std::to_string(e) + " is not finite");
+        if (a->w[e] < 0.0) return refuse("weight " + std::to_string(e) + " is negative");
+    }
+    if (a->c_sigma < 0.0 || a->c_sigma > 1.0) return refuse("c_sigma outside [0, 1]");
+    if (a->c_c < 0.0 || a->c_c > 1.0) return refuse("c_c outside [0, 1]");
+    if (a->c_1 < 0.0 || a->c_1 > 1.0) return refuse("c_1 outside [0, 1]");
+    if (a->c_mu < 0.0 || a->c_mu > 1.0) return refuse("c_mu outside [0, 1]");
+    if (a->c_1 + a->c_mu > 1.0) return refuse("c_1 + c_mu > 1");
+    if (!(a->d_sigma > 0.0)) return refuse("d_sigma not > 0");
+    if (!(a->chi_n > 0.0)) return refuse("chi_n not > 0");
+    if (!(a->mu_eff > 0.0)) return refuse("mu_eff not > 0");
+    if (a->min_sigma < 0.0 || a->min_sigma > a->max_sigma) return refuse("min_sigma negative or > max_sigma");
+    if (a->t_index == 0) return refuse("t_index = 0 (the generation count starts at 1)");
+    if (!h) return refuse("null handle");
+    DeviceGuard dev_guard(h);
+    hipLaunchKernelGGL(plan_cma_update_kernel, dim3(a->P), dim3(CMA_THREADS), 0, (hipStream_t)stream, *a);
     HIPCHK(hipGetLastError());
     return GLGYM_OK;
 }

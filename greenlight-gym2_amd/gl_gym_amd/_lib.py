@@ -211,6 +211,27 @@ class PlanEsUpdateArgs(C.Structure):
                 ("m2", C.c_void_p), ("mean", C.c_void_p), ("std", C.c_void_p), ("mean_out", C.c_void_p), ("std_out", C.c_void_p)]
 
 
+# CMA-ES with a full covariance matrix (include/glgym.h glgym_plan_cma_sample / _cma_update)
+CMA_NMAX = 32
+CMA_CONSTANTS = ("mu_eff", "c_sigma", "d_sigma", "c_c", "c_1", "c_mu", "chi_n")
+CMA_STATUS = {0: "updated", 1: "too few elites", 2: "not finite", 3: "not positive definite", 4: "t = 0"}
+
+
+class PlanCmaSampleArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("mean", C.c_void_p),
+                ("sigma", C.c_void_p), ("chol", C.c_void_p), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p),
+                ("theta", C.c_void_p)]
+
+
+class PlanCmaUpdateArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("E", C.c_int32),
+                ("theta", C.c_void_p), ("elite_k", C.c_void_p), ("n_elite", C.c_void_p), ("w", C.c_void_p), ("w_dev", C.c_void_p),
+                ("mu_eff", C.c_double), ("c_sigma", C.c_double), ("d_sigma", C.c_double), ("c_c", C.c_double), ("c_1", C.c_double),
+                ("c_mu", C.c_double), ("chi_n", C.c_double), ("min_sigma", C.c_double), ("max_sigma", C.c_double),
+                ("t_index", C.c_uint64), ("t_base", C.c_void_p), ("mean", C.c_void_p), ("sigma", C.c_void_p), ("cov", C.c_void_p),
+                ("chol", C.c_void_p), ("p_sigma", C.c_void_p), ("p_c", C.c_void_p), ("status", C.c_void_p)]
+
+
 # robust planning (include/glgym.h glgym_plan_scenario / _rollout_scenarios / _aggregate)
 MAX_SCENARIOS = 256
 
@@ -368,6 +389,8 @@ PROTOTYPES = {
     "glgym_plan_es_sample": (C.c_int, [C.c_void_p, C.POINTER(PlanEsSampleArgs), C.c_void_p]),
     "glgym_plan_es_utilities": (C.c_int, [C.c_void_p, C.POINTER(PlanEsUtilitiesArgs), C.c_void_p]),
     "glgym_plan_es_update": (C.c_int, [C.c_void_p, C.POINTER(PlanEsUpdateArgs), C.c_void_p]),
+    "glgym_plan_cma_sample": (C.c_int, [C.c_void_p, C.POINTER(PlanCmaSampleArgs), C.c_void_p]),
+    "glgym_plan_cma_update": (C.c_int, [C.c_void_p, C.POINTER(PlanCmaUpdateArgs), C.c_void_p]),
     "glgym_plan_scenario": (C.c_int, [C.c_void_p, C.POINTER(PlanScenarioArgs), C.c_void_p]),
     "glgym_plan_rollout_scenarios": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutScenariosArgs), C.c_void_p]),
     "glgym_plan_aggregate": (C.c_int, [C.c_void_p, C.POINTER(PlanAggregateArgs), C.c_void_p]),

@@ -42,11 +42,17 @@ Evolution strategy (glgym_plan_es_sample / _es_utilities / _es_update; _EsStages
 mirrored pairs around the mean, centred ranks over the whole population, a search-gradient step on the mean (Adam or SGD) and the
 separable-NES update of the per-parameter spread -- with sample_mirrored(), utilities() and es_update() as the single stages.  The CEM
 refits an independent Gaussian to the best few of K, which suits a handful of set-points; the ES uses every return and suits the
-hundreds of weights of a net."""
+hundreds of weights of a net.
+
+CMA-ES (glgym_plan_cma_sample / _cma_update; _CmaStages below): RuleSearch.cma() keeps a full covariance matrix per greenhouse over its
+at most 32 tuned constants -- the separable searches above cannot follow constants that interact -- with sample_cma() and cma_update()
+as the single stages.  PolicySearch and Planner have none: even a linear policy has 144 parameters."""
 from __future__ import annotations
 
 import ctypes as C
 from typing import Any, Dict, Optional
+
+import numpy as np
 
 from . import _lib as L
 
@@ -671,6 +677,131 @@ _ES_DOC = """Evolution strategy: n_iter x (sample_mirrored -> rollout -> utiliti
         to plan.draw_base_t for fresh noise and, with resume=True, to es_t_base for the next Adam steps."""
 
 
+# ---- CMA-ES with a full covariance matrix over theta (include/glgym.h glgym_plan_cma_sample / _cma_update) ---------------------------
+class _CmaStages:
+    """The CMA-ES stages for RuleSearch.  `search` supplies env, B, K, D, Ht, plan, its two population blocks (_blocks, _cur), the block
+    of its last rollout (_theta), elites, rollout, select, mean_t and _draw.  Built at the first CMA call, which is the only one that
+    allocates: sigma_t [B] f64, cov_t / chol_t [B, N, N] f64, p_sigma_t / p_c_t [B, N] f64, status_t [B] i32, the weights on the device
+    (one array per n_elite, kept), and t_base_t, the device word added to every generation count.  A policy net is not served: even a
+    linear policy has 144 parameters, and a 144 x 144 matrix per row is another design."""
+
+    def __init__(self, search):
+        torch, dev = search.torch, search.env.device
+        self.s, self.P, self.N = search, int(search.B), int(search.D)
+        if not 1 <= self.N <= L.CMA_NMAX:
+            raise ValueError(f"CMA-ES keeps a full covariance matrix: 1 .. {L.CMA_NMAX} tuned constants, got {self.N}")
+        z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)  # noqa: E731
+        self.sigma_t, self.cov_t, self.chol_t = z(self.P), z(self.P, self.N, self.N), z(self.P, self.N, self.N)
+        self.p_sigma_t, self.p_c_t = z(self.P, self.N), z(self.P, self.N)
+        self.status_t = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self.t_base_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._eye = torch.eye(self.N, dtype=torch.float64, device=dev).expand(self.P, self.N, self.N)
+        self._weights = {}                                           # w as bytes -> (host array, device tensor)
+        self.t = 0                                                   # updates since the last restart
+        self.restart(0.3)
+
+    def restart(self, init_sigma):
+        self.sigma_t.fill_(float(init_sigma))
+        self.cov_t.copy_(self._eye)
+        self.chol_t.copy_(self._eye)
+        self.p_sigma_t.zero_()
+        self.p_c_t.zero_()
+        self.t = 0
+
+    def weights(self, w):
+        """The weights on both sides of the call; a new vector allocates once (not inside a capture: call cma_update eagerly first)."""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        key = w.tobytes()
+        if key not in self._weights:
+            self._weights[key] = (w, self.s.torch.as_tensor(w, device=self.s.env.device))
+        return self._weights[key]
+
+    def sample(self, seed=0, draw_index=0):
+        s, e = self.s, self.s.env
+        if int(seed) < 0 or int(draw_index) < 0:
+            raise ValueError("seed and draw_index must be >= 0")
+        dst = 0 if s._cur is None else 1 - s._cur
+        a = L.make_plan_args(L.PlanCmaSampleArgs, self.P, s.K, self.N, s.mean_t.data_ptr(), self.sigma_t.data_ptr(), self.chol_t.data_ptr(),
+                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), s.plan.draw_base_t.data_ptr(), s._blocks[dst].data_ptr())
+        L.check(e._lib.glgym_plan_cma_sample(e._h, C.byref(a), e._stream()), "glgym_plan_cma_sample")
+        s._cur = dst
+        s._elites = (s._elites[0], None) if s._elites else None      # no elite of an overwritten block is carried
+        return s._blocks[dst]
+
+    @staticmethod
+    def check_hyper(N, E, hp, min_sigma, max_sigma):
+        """ValueError with the meaning of glgym_plan_cma_update's refusal; -> the weights as a float64 array."""
+        inf = float("inf")
+        w = np.asarray(hp["w"], dtype=np.float64).reshape(-1)
+        if w.size != E:
+            raise ValueError(f"w must hold n_elite = {E} weights, got {w.size}")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("the weights must be finite and >= 0")
+        for k in L.CMA_CONSTANTS:
+            if not -inf < float(hp[k]) < inf:
+                raise ValueError(f"{k} must be finite")
+        for k in ("c_sigma", "c_c", "c_1", "c_mu"):
+            if not 0.0 <= float(hp[k]) <= 1.0:
+                raise ValueError(f"{k} must lie in [0, 1]")
+        if float(hp["c_1"]) + float(hp["c_mu"]) > 1.0:
+            raise ValueError("c_1 + c_mu must not exceed 1")
+        for k in ("d_sigma", "chi_n", "mu_eff"):
+            if not float(hp[k]) > 0.0:
+                raise ValueError(f"{k} must be > 0")
+        if not 0.0 <= float(min_sigma) <= float(max_sigma) < inf:
+            raise ValueError("min_sigma and max_sigma must be finite with 0 <= min_sigma <= max_sigma")
+        return w
+
+    def update(self, E, hp, min_sigma, max_sigma):
+        s, e = self.s, self.s.env
+        w = self.check_hyper(self.N, E, hp, min_sigma, max_sigma)
+        if s._theta is None or s._elites is None or s._elites[0] != E:
+            raise ValueError("cma_update needs a rollout and its elites()")
+        w_host, w_dev = self.weights(w)
+        a = L.make_plan_args(L.PlanCmaUpdateArgs, self.P, s.K, self.N, E, s._theta.data_ptr(), s.elite_k_t.data_ptr(), s.n_elite_t.data_ptr(),
+                             w_host.ctypes.data, w_dev.data_ptr(), *(float(hp[k]) for k in L.CMA_CONSTANTS), float(min_sigma),
+                             float(max_sigma), self.t + 1, self.t_base_t.data_ptr(), s.mean_t.data_ptr(), self.sigma_t.data_ptr(),
+                             self.cov_t.data_ptr(), self.chol_t.data_ptr(), self.p_sigma_t.data_ptr(), self.p_c_t.data_ptr(),
+                             self.status_t.data_ptr())
+        L.check(e._lib.glgym_plan_cma_update(e._h, C.byref(a), e._stream()), "glgym_plan_cma_update")
+        self.t += 1
+        return self.status_t
+
+    def run(self, n_iter, E, init_sigma, min_sigma, max_sigma, seed, mean, resume, overrides):
+        s = self.s
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise ValueError("n_iter must be at least 1")
+        if not 1 <= E <= s.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {s.K}")
+        unknown = sorted(set(overrides) - {"w", *L.CMA_CONSTANTS})
+        if unknown:
+            raise TypeError(f"unexpected arguments {unknown}; the constants are w and {L.CMA_CONSTANTS}")
+        hp = {**s.cma_defaults(self.N, s.K, E), **overrides}
+        self.check_hyper(self.N, E, hp, min_sigma, max_sigma)
+        if not 0.0 < float(init_sigma) < float("inf") or int(seed) < 0:
+            raise ValueError("init_sigma must be finite and > 0, seed >= 0")
+        if resume and mean is not None:
+            raise ValueError("resume=True continues from mean_t and the CMA state: it takes no mean")
+        if not resume:
+            if mean is not None:
+                if mean.numel() not in (s.Ht * L.NU, s.Ht * self.P * L.NU):
+                    raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
+                s.mean_t.copy_(mean.reshape(s.Ht, -1, L.NU))
+            else:
+                s._es_start()
+            self.restart(init_sigma)
+        for _ in range(n_iter):
+            block = self.sample(seed=seed, draw_index=s._draw)
+            s._draw += 1
+            s.rollout(block)
+            s.elites(E)
+            self.update(E, hp, min_sigma, max_sigma)
+        sel = s.select()
+        return {"best_theta": sel["best_theta"], "best_params": sel["best_params"], "best_return": sel["best_return"], "best_k": sel["best_k"],
+                "mean": s.mean_t, "sigma": self.sigma_t, "cov": self.cov_t, "status": self.status_t}
+
+
 class RuleSearch:
     """Closed-loop rollouts of the rule-based controller, and the tuning of its constants by the cross-entropy method, on the device
     (TomatoVecEnv.rule_search).  A candidate is not a control sequence but a FEEDBACK LAW: a row of K per greenhouse of the float32 block
@@ -722,6 +853,7 @@ class RuleSearch:
         self._base_theta = torch.as_tensor(self.params.encode(self.base), device=dev) if self.params.inside(self.base) else None
         self._draw = 0
         self._es_stages = None
+        self._cma_stages = None
         self.scenario_returns = getattr(p, "scenario_returns", None)
         self.scenario_failed = getattr(p, "scenario_failed", None)
 
@@ -946,6 +1078,76 @@ class RuleSearch:
         return self._es().run(n_iter, lr, lr_std, init_std, min_std, max_std, std_decay, optimizer, betas, eps, seed, mean, resume)
 
     es.__doc__ = _ES_DOC
+
+    # ---- CMA-ES with a full covariance matrix over theta (_CmaStages) -----------------------------------------------------------------
+    def _cma(self):
+        if self._cma_stages is None:
+            self._cma_stages = _CmaStages(self)
+        return self._cma_stages
+
+    @staticmethod
+    def cma_defaults(N: int, K: int, E: int) -> Dict[str, Any]:
+        """Hansen's default constants for N components, K candidates and E elites: {"w": float64 [E], w_i ~ ln(E + 1/2) - ln i,
+        normalised; "mu_eff" = 1 / sum w^2; "c_sigma", "d_sigma", "c_c", "c_1", "c_mu", "chi_n"}."""
+        N, K, E = int(N), int(K), int(E)
+        if N < 1 or not 1 <= E <= K:
+            raise ValueError("cma_defaults needs N >= 1 and 1 <= E <= K")
+        w = np.log(E + 0.5) - np.log(np.arange(1, E + 1, dtype=np.float64))
+        w = w / w.sum()
+        mu = 1.0 / float(np.sum(w * w))
+        c_sigma = (mu + 2.0) / (N + mu + 5.0)
+        c_1 = 2.0 / ((N + 1.3) ** 2 + mu)
+        return {"w": w, "mu_eff": mu, "c_sigma": c_sigma,
+                "d_sigma": 1.0 + 2.0 * max(0.0, float(np.sqrt((mu - 1.0) / (N + 1.0))) - 1.0) + c_sigma,
+                "c_c": (4.0 + mu / N) / (N + 4.0 + 2.0 * mu / N), "c_1": c_1,
+                "c_mu": min(1.0 - c_1, 2.0 * (mu - 2.0 + 1.0 / mu) / ((N + 2.0) ** 2 + mu)),
+                "chi_n": float(np.sqrt(N)) * (1.0 - 1.0 / (4.0 * N) + 1.0 / (21.0 * N * N))}
+
+    @property
+    def cma_t_base(self):
+        """The device word added to every cma_update generation count (int64 [1])."""
+        return self._cma().t_base_t
+
+    @property
+    def cma_state(self) -> Dict[str, Any]:
+        """The CMA state next to mean_t, device tensors updated in place: sigma [B], cov, chol [B, D, D], p_sigma, p_c [B, D] f64,
+        status [B] i32 (of the last cma_update: 0 updated, 1 too few elites, 2 not finite, 3 not positive definite, 4 t = 0)."""
+        st = self._cma()
+        return {"sigma": st.sigma_t, "cov": st.cov_t, "chol": st.chol_t, "p_sigma": st.p_sigma_t, "p_c": st.p_c_t, "status": st.status_t}
+
+    def sample_cma(self, seed: int = 0, draw_index: int = 0):
+        """glgym_plan_cma_sample: the population theta = clip(mean_t + sigma * chol z) from this object's mean_t and CMA state, into the
+        block the previous population does not occupy; returns it.  No reserved candidate.  ValueError with more than 32 constants."""
+        return self._cma().sample(seed, draw_index)
+
+    def cma_update(self, n_elite: Optional[int] = None, min_sigma: float = 1e-6, max_sigma: float = 1.0, **overrides):
+        """elites(n_elite) of the last rollout, then glgym_plan_cma_update in place on mean_t and the CMA state; returns status [B] i32.
+        n_elite defaults to K // 2; the constants are cma_defaults(D, K, n_elite) unless overridden by name."""
+        E = max(1, self.K // 2) if n_elite is None else int(n_elite)
+        st = self._cma()
+        unknown = sorted(set(overrides) - {"w", *L.CMA_CONSTANTS})
+        if unknown:
+            raise TypeError(f"unexpected arguments {unknown}; the constants are w and {L.CMA_CONSTANTS}")
+        if self._theta is None:
+            raise ValueError("cma_update needs a rollout")
+        self.elites(E)
+        return st.update(E, {**self.cma_defaults(self.D, self.K, E), **overrides}, min_sigma, max_sigma)
+
+    def cma(self, n_iter: int, n_elite: Optional[int] = None, init_sigma: float = 0.3, min_sigma: float = 1e-6, max_sigma: float = 1.0,
+            seed: int = 0, mean=None, resume: bool = False, **overrides) -> Dict[str, Any]:
+        """Tune the controller by CMA-ES with a full covariance matrix: n_iter x (sample_cma -> rollout -> elites -> cma_update), then
+        select() on the last population.  For the few, strongly interacting constants this class tunes (at most 32): the search
+        distribution of greenhouse b is N(mean, sigma^2 C) with a D x D matrix C, adapted by the rank-one and rank-mu updates, and a
+        step size sigma under cumulative step-size control.  The start is cem()'s: `mean`, or this object's default; sigma starts at
+        init_sigma, C at I.  n_elite defaults to K // 2; the constants are cma_defaults(D, K, n_elite) unless overridden by name (w,
+        mu_eff, c_sigma, d_sigma, c_c, c_1, c_mu, chi_n).  resume=True continues instead from mean_t, the CMA state and the
+        generation count of the previous call.  Every sample takes the next draw index of this object's lifetime.
+        Returns device tensors, overwritten by the next call: best_theta [B, Ht*6], best_params {name: [B]}, best_return, best_k, mean
+        [Ht, B, 6], sigma [B], cov [B, D, D] f64, status [B] i32 of the last update (0: updated; otherwise the row kept its state).
+        No host synchronisation and, after the first call, no allocation: a whole cma() can be captured in a graph; between replays
+        add n_iter to plan.draw_base_t for fresh noise and, with resume=True, to cma_t_base for the next generation counts."""
+        E = max(1, self.K // 2) if n_elite is None else int(n_elite)
+        return self._cma().run(n_iter, E, init_sigma, min_sigma, max_sigma, seed, mean, resume, overrides)
 
     def best_controller(self, b: int = 0):
         """The RuleBasedController of greenhouse b's best candidate of the last select() / cem(): base with the tuned constants

@@ -35,6 +35,8 @@
  *                     shooting, MPPI) and iterated (the cross-entropy method: sample, rank the elites, refit), all on the device
  *   glgym_plan_es_sample / _es_utilities / _es_update <- no counterpart: an evolution strategy over the same blocks (mirrored
  *                     sampling, centred ranks of the whole population, a search-gradient step on mean and spread), for policy search
+ *   glgym_plan_cma_sample / _cma_update <- no counterpart: CMA-ES with a full covariance matrix per row (a correlated sample, rank-one
+ *                     and rank-mu update, step-size control, a Cholesky factorisation), for the few constants of the rule-based controller
  *   glgym_plan_scenario / _rollout_scenarios / _aggregate <- the draw of noise.py:3-23 (parametric_crop_uncertainty) inside the
  *                     planning horizon, with common random numbers across candidates, and a risk score over the sampled futures
  *
@@ -166,7 +168,8 @@ typedef struct {
  * glgym_plan_fork, glgym_plan_accumulate, glgym_plan_rollout, glgym_plan_select; glgym_step_obs; glgym_step_obs_reset;
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
- * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build */
+ * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build; glgym_plan_cma_sample,
+ * glgym_plan_cma_update */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -680,6 +683,94 @@ typedef struct {
 int glgym_plan_es_sample(glgym_handle h, const glgym_plan_es_sample_args* a, void* stream);
 int glgym_plan_es_utilities(glgym_handle h, const glgym_plan_es_utilities_args* a, void* stream);
 int glgym_plan_es_update(glgym_handle h, const glgym_plan_es_update_args* a, void* stream);
+
+/* ---- CMA-ES with a full covariance matrix over few, strongly interacting components (csrc/gl_cma.hpp, csrc/glgym_plan.hip) ------
+ * One iteration is glgym_plan_cma_sample -> a rollout -> glgym_plan_elites -> glgym_plan_cma_update.  For the N <= GLGYM_CMA_NMAX
+ * searched components of a rule-based controller (glgym_plan_rollout_rule); a policy net's hundreds of weights stay with the
+ * separable stages above.  Same layouts and conventions as the ES stages: the block theta [Ht][P*K][6] f32 with Ht = ceil(N / 6),
+ * component i at plane h = i / 6, slot j = i % 6; mean [Ht][P][6] f32; struct_size first; every argument is checked, GLGYM_EINVAL with
+ * a glgym_last_error text, before the handle is looked at and before anything is launched; asynchronous on `stream`, no allocation,
+ * no host synchronisation (capturable), plain vector stores, no atomics.  Opt-in: no other entry point changes.  Row p is one search
+ * distribution with K candidates c = p*K + k and E elites.  1 <= N <= GLGYM_CMA_NMAX, 1 <= E <= K, P*K <= INT32_MAX - 255.
+ * Arithmetic in double, every product and every sum rounded on its own, in the orders stated here.
+ *
+ * State per row, the caller's, updated in place: mean; sigma [P] f64 (the step size); cov [P][N][N] f64, symmetric, both triangles
+ * stored (start: I); chol [P][N][N] f64, its lower Cholesky factor, the upper triangle zero (start: I); the evolution paths p_sigma
+ * and p_c [P][N] f64 (start: 0).
+ *
+ * glgym_plan_cma_sample, one lane per child, the children of a block from one row.  z_i is component i of the normals of
+ * glgym_plan_sample's stream: z_{6h+j} = e_j of (c, h, D = draw_index + *draw_base, seed).  y_i = sum_{j <= i} chol[p][i][j] * z_j,
+ * from 0.0, j ascending, each product rounded, then added.  theta[h][c][j] = (float) clip(mean[h][p][j] + sigma[p] * y_i, -1, 1)
+ * (product, then sum); the padding slots i >= N store 0.0f.  No reserved candidate, no carry, no colouring: with chol = I and std =
+ * sigma the rows are bit for bit those of glgym_plan_sample (beta = 0, carry = 0) for k >= 1. */
+#define GLGYM_CMA_NMAX 32
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, N;
+    const float* mean;           /* [Ht][P][6] */
+    const double* sigma;         /* [P] */
+    const double* chol;          /* [P][N][N] */
+    uint64_t seed;
+    uint64_t draw_index;         /* which population this is */
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    float* theta;                /* [Ht][P*K][6] out */
+} glgym_plan_cma_sample_args;
+
+/* One block per row.  It reads the STORED population (clipping and float32 rounding included) and no RNG.  x_e is the row of elite e
+ * = elite_k[p][e] (glgym_plan_elites), e < E; t = t_index + *t_base; "old" is the row's state on entry.
+ *   1. y_e[d] = ((double) x_e[d] - (double) mean[d]) / sigma                          (one subtraction, one division)
+ *   2. yw[d] = sum_e w[e] * y_e[d]                                                    (from 0.0, e ascending)
+ *   3. zw = chol_old^-1 yw by forward substitution: zw[i] = (yw[i] - sum_{j<i} chol[i][j] * zw[j]) / chol[i][i], each product
+ *      subtracted in turn, j ascending
+ *   4. q_s = sqrt((c_sigma * (2 - c_sigma)) * mu_eff);  p_sigma'[d] = (1 - c_sigma) * p_sigma[d] + q_s * zw[d]
+ *   5. n2 = sum_d p_sigma'[d] * p_sigma'[d] (from 0.0, d ascending);  nrm = sqrt(n2)
+ *   6. g = 1 - (1 - c_sigma)^(2t), the power by glgym_plan_es_update's square-and-multiply;
+ *      h_sigma = nrm / sqrt(g) < (1.4 + 2 / (N + 1)) * chi_n
+ *   7. q_c = sqrt((c_c * (2 - c_c)) * mu_eff);  p_c'[d] = (1 - c_c) * p_c[d] + (h_sigma ? q_c * yw[d] : 0.0)
+ *   8. a0 = ((1 - c_1) - c_mu) + (h_sigma ? 0.0 : (c_1 * c_c) * (2 - c_c))
+ *   9. for b <= a: R[a][b] = sum_e (w[e] * y_e[a]) * y_e[b] (from 0.0, e ascending);
+ *      cov'[a][b] = (a0 * cov[a][b] + c_1 * (p_c'[a] * p_c'[b])) + c_mu * R[a][b];  cov'[b][a] is a copy
+ *  10. mean'[d] = (float) clip((double) mean[d] + sigma * yw[d], -1, 1)
+ *  11. sigma' = min(max(sigma * exp((c_sigma / d_sigma) * (nrm / chi_n - 1)), min_sigma), max_sigma)      (exp is the device library's)
+ *  12. chol' = the Cholesky factor of cov', row-oriented: for j = 0 .. N-1: s = cov'[j][j] - sum_{k<j} chol'[j][k] * chol'[j][k],
+ *      chol'[j][j] = sqrt(s); for i > j: chol'[i][j] = (cov'[i][j] - sum_{k<j} chol'[i][k] * chol'[j][k]) / chol'[j][j]; each
+ *      product subtracted in turn, k ascending; the upper triangle is 0.
+ * A row is updated whole or not at all; status[p] says which, the first of these that applies:
+ *   4  t = 0
+ *   1  n_elite[p] < E, or one of the E elite indices outside 0..K-1
+ *   2  one of p_sigma', p_c', cov', mean', sigma' is not finite (a NaN in an elite's theta, say)
+ *   3  a pivot s is not > 0
+ *   2  an entry of chol' is not finite
+ *   0  updated
+ * In every case but 0 each piece of the row's state keeps its bits.
+ * The weights are given twice: w, E doubles in HOST memory, read and checked by the call, and w_dev, the same E doubles in DEVICE
+ * memory, which the kernel reads (the call copies nothing, so that it can be captured).  The library computes no logarithm: the
+ * caller supplies the weights and the constants (Hansen's defaults: gl_gym_amd.planner.RuleSearch.cma_defaults).
+ * Refused: N outside 1..GLGYM_CMA_NMAX; E outside 1..K; P < 1; P*K past INT32_MAX - 255; a constant or weight that is not finite; a
+ * negative weight; c_sigma, c_c, c_1 or c_mu outside [0, 1]; c_1 + c_mu > 1; d_sigma, chi_n or mu_eff not > 0; min_sigma negative or
+ * > max_sigma; t_index = 0; a NULL pointer (t_base may be NULL). */
+typedef struct {
+    int32_t struct_size;
+    int32_t P, K, N, E;
+    const float* theta;          /* [Ht][P*K][6]: the population the elites belong to */
+    const int32_t* elite_k;      /* [P][E]: glgym_plan_elites */
+    const int32_t* n_elite;      /* [P] */
+    const double* w;             /* [E] HOST: the recombination weights, >= 0 */
+    const double* w_dev;         /* [E] device: the same values */
+    double mu_eff, c_sigma, d_sigma, c_c, c_1, c_mu, chi_n, min_sigma, max_sigma;
+    uint64_t t_index;            /* >= 1: the generation count */
+    const uint64_t* t_base;      /* device word added to t_index, or NULL */
+    float* mean;                 /* [Ht][P][6] in / out */
+    double* sigma;               /* [P] in / out */
+    double* cov;                 /* [P][N][N] in / out */
+    double* chol;                /* [P][N][N] in / out */
+    double* p_sigma;             /* [P][N] in / out */
+    double* p_c;                 /* [P][N] in / out */
+    int32_t* status;             /* [P] out */
+} glgym_plan_cma_update_args;
+
+int glgym_plan_cma_sample(glgym_handle h, const glgym_plan_cma_sample_args* a, void* stream);
+int glgym_plan_cma_update(glgym_handle h, const glgym_plan_cma_update_args* a, void* stream);
 
 /* ---- robust planning: scenario rollouts under crop noise, risk-aware scores (csrc/gl_scen.hpp, csrc/glgym_plan.hip) ----------
  * With uncertainty_scale > 0 the environment multiplies the 34 crop parameters p[128..161] by 1 + U(-scale/2, scale/2) at every

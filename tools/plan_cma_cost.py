@@ -1,0 +1,362 @@
+#!/usr/bin/env python3
+"""What the CMA-ES stages cost, measured on the GPU -> profiles/plan_cma_cost.txt.
+
+    python tools/plan_cma_cost.py [--parent-pkg DIR] [--out profiles/plan_cma_cost.txt] [--iters 8]
+
+fp32, ls5; device events, warmed up, medians of alternating samples.
+(a) Recorded, no requirement: glgym_plan_cma_sample and glgym_plan_elites + glgym_plan_cma_update on their own at 64 greenhouses x 1 024
+    candidates and at 8 x 8 192, with N = 5 (the set-points of examples/tune_rule_based.py) and N = 29 (the whole controller) tuned
+    constants and E = K / 2, each against the same stage written with torch ops in float64 -- randn, bmm, clamp; topk, gather, einsum,
+    a triangular solve and torch.linalg.cholesky_ex (if this torch build has it on the device; otherwise the report says it has not and
+    the torch update is timed without it).  And each stage's share of one cma() iteration at 48 closed-loop steps.
+(b) Requirement, ratio <= 1.05: one RuleSearch.cem iteration and one Planner.rollout of this build against the parent commit's, on the
+    same inputs (their code is unchanged), with each side's run-to-run spread and the sums of the returns.
+(c) Recorded, no requirement: on the five set-points and the setting of examples/tune_rule_based.py, after --iters iterations of each
+    from the default controller, one seed: the best candidate's return and the return of the controller at the mean, under cma and cem.
+--parent-pkg DIR: the greenlight-gym2_amd directory of a checkout of the PARENT commit with its library built; its side of (b) runs in
+child processes on that build.  Without it they run on this build, the report says so and gives no verdict.
+No fallback: without a GPU this fails."""
+import argparse
+import statistics
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+SHAPES = ((64, 1024), (8, 8192))
+H0 = 48
+N_SAMPLES, N_WARM = 7, 2
+SEASON = 10
+TUNE5 = {"temp_setpoint_day": (17.0, 23.0), "temp_setpoint_night": (14.0, 19.0), "co2_day": (400.0, 1200.0), "rh_max": (75.0, 95.0),
+         "lamps_off": (12.0, 22.0)}
+CEM = dict(n_elite=32, init_std=0.5, min_std=0.05, alpha=0.1)
+
+
+def setup(pkg):
+    sys.path.insert(0, str(pkg))
+    import torch
+    from gl_gym_amd.tomato_env import TomatoVecEnv
+    from gl_gym_amd.utils import synthetic_weather
+    return torch, TomatoVecEnv, synthetic_weather
+
+
+def parent_env(TomatoVecEnv, w, P, stride=96):
+    """The P parent environments every side starts from: seeded reset, four steps under the default controller."""
+    from gl_gym_amd.baseline import RuleBasedController
+    starts = list(range(0, stride * P, stride))
+    env = TomatoVecEnv(P, weather=w, dtype="float32", season_length=SEASON, start_rows=starts, start_days=[s / 96.0 for s in starts], seed=5,
+                       auto_reset=False)
+    env.reset_tensor()
+    for _ in range(4):
+        env.step_tensor(controller=RuleBasedController(), want_obs=False)
+    return env
+
+
+def tune29():
+    """Every constant of the controller within 10 % of its default (a proportional band's interval must not contain 0)."""
+    from gl_gym_amd import _lib as L
+    from gl_gym_amd.baseline import RuleBasedController
+    base, tune = RuleBasedController(), {}
+    for n in L.RULE_FIELDS:
+        v = float(getattr(base, n))
+        r = 0.1 * abs(v) + (0.0 if n in L.RULE_BANDS else 0.01)
+        tune[n] = (v - r, v + r)
+    return tune
+
+
+def timed(torch, fn, n=3):
+    """Device time of fn() in ms, mean of n windows between events."""
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return sum(a.elapsed_time(b) for a, b in ev) / n
+
+
+def cem_iteration(rs):
+    def run():
+        rs._draw = 0                                          # the same population every time
+        rs.cem(1, CEM["n_elite"], init_std=CEM["init_std"], min_std=CEM["min_std"], alpha=CEM["alpha"], seed=1)
+    return run
+
+
+def worker(pkg, P, K, H, kind, block_file):
+    """Planner.rollout(actions_t) (kind "actions") or one RuleSearch.cem iteration (kind "cem") on the build under pkg; answers "time"
+    on stdin with one sample."""
+    torch, TomatoVecEnv, synthetic_weather = setup(pkg)
+    env = parent_env(TomatoVecEnv, synthetic_weather(n_rows=35040), P)
+    if kind == "actions":
+        block = torch.load(block_file).to(env.device).contiguous()
+        plan = env.planner(K, H)
+        run = lambda: plan.rollout(actions_t=block)  # noqa: E731
+    else:
+        search = env.rule_search(K, H, tune=TUNE5)
+        plan, run = search.plan, cem_iteration(search)
+    for _ in range(N_WARM):
+        timed(torch, run, 1)
+    print(f"ready {float(plan.ret_t.sum()):.17g}", flush=True)
+    for line in sys.stdin:
+        if line.strip() != "time":
+            break
+        print(f"ms {timed(torch, run):.6f}", flush=True)
+
+
+class Other:
+    """The other side of a comparison: a child process on the parent commit's build, or (without --parent-pkg) this build."""
+
+    def __init__(self, torch, pkg, P, K, H, kind, block, local_run, local_plan):
+        self.torch, self.child, self.tmp = torch, None, None
+        if pkg:
+            self.tmp = tempfile.NamedTemporaryFile(suffix=".pt")
+            if block is not None:
+                torch.save(block.cpu(), self.tmp.name)
+            self.child = subprocess.Popen([sys.executable, __file__, "--worker", str(Path(pkg).resolve()), str(P), str(K), str(H), kind, self.tmp.name],
+                                          stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+            ready = self.child.stdout.readline().split()
+            assert ready and ready[0] == "ready", "the parent-commit worker did not start"
+            self.sum = float(ready[1])
+        else:
+            self.run = local_run
+            for _ in range(N_WARM):
+                timed(torch, local_run, 1)
+            self.sum = float(local_plan.ret_t.sum())
+
+    def sample(self):
+        if not self.child:
+            return timed(self.torch, self.run)
+        self.child.stdin.write("time\n")
+        self.child.stdin.flush()
+        return float(self.child.stdout.readline().split()[1])
+
+    def close(self):
+        if self.child:
+            self.child.stdin.write("quit\n")
+            self.child.stdin.flush()
+            self.child.wait(timeout=60)
+
+
+def spread(v):
+    return (max(v) - min(v)) / statistics.median(v)
+
+
+def compare(torch, mine, other, n=3):
+    for _ in range(N_WARM):
+        timed(torch, mine, 1)
+    a, b = [], []
+    for _ in range(N_SAMPLES):
+        a.append(timed(torch, mine, n))
+        b.append(other.sample() if hasattr(other, "sample") else timed(torch, other, n))
+    return a, b
+
+
+def has_device_cholesky(torch, dev):
+    try:
+        a = torch.eye(4, dtype=torch.float64, device=dev).expand(2, 4, 4).contiguous()
+        L_, info = torch.linalg.cholesky_ex(a)
+        torch.cuda.synchronize()
+        return bool((info == 0).all()) and bool(torch.isfinite(L_).all())
+    except Exception as exc:                                  # noqa: BLE001  (whatever this build raises: it is reported)
+        return f"{type(exc).__name__}: {str(exc).splitlines()[0][:120]}"
+
+
+def stage_costs(torch, rs, say, chol_ok):
+    """(a) at the shape of rs: the stages through rs's own methods against torch ops on tensors of the same shapes; -> medians in ms."""
+    from gl_gym_amd import _lib as L
+    P, K, N, Ht, dev = rs.B, rs.K, rs.D, rs.Ht, rs.env.device
+    E = K // 2
+    st, plan = rs._cma(), rs.plan
+    hp = rs.cma_defaults(N, K, E)
+    rs._es_start()
+    st.restart(0.3)
+    g = torch.Generator().manual_seed(4)
+    plan._score_t.copy_(torch.randn(P * K, generator=g, dtype=torch.float64).to(dev))
+    plan._score_failed_t.copy_((torch.rand(P * K, generator=g) < 0.02).to(torch.uint8).to(dev))
+    rs._cur = 1
+    block = rs.sample_cma(seed=1, draw_index=0)
+    rs._theta, rs._rolled = block, rs._cur                    # the stages on their own: no rollout in between
+    say(f"P = {P} rows x K = {K} candidates, N = {N} constants (Ht = {Ht} planes), E = {E} elites")
+    score, failed = plan._score_t.view(P, K), plan._score_failed_t.view(P, K)
+    w = torch.as_tensor(hp["w"], device=dev)
+    t = {k: v.clone() for k, v in dict(sigma=st.sigma_t, cov=st.cov_t, chol=st.chol_t, ps=st.p_sigma_t, pc=st.p_c_t).items()}
+    t["mean"] = rs.mean_t.permute(1, 0, 2).reshape(P, Ht * L.NU)[:, :N].double().contiguous()
+    keep = {}
+    cs, cc, c1, cmu, mu = (hp[k] for k in ("c_sigma", "c_c", "c_1", "c_mu", "mu_eff"))
+    qs, qc = (cs * (2 - cs) * mu) ** 0.5, (cc * (2 - cc) * mu) ** 0.5
+
+    def hip_sample():
+        rs._cur = 1                                           # always into block 0
+        rs.sample_cma(seed=1, draw_index=0)
+
+    def th_sample():
+        z = torch.randn(P, K, N, dtype=torch.float64, device=dev)
+        y = torch.bmm(z, t["chol"].transpose(1, 2))
+        x = (t["mean"][:, None, :] + t["sigma"][:, None, None] * y).clamp_(-1, 1).float()
+        out = torch.zeros(P * K, Ht * L.NU, dtype=torch.float32, device=dev)
+        out[:, :N] = x.view(P * K, N)
+        keep["block"] = out.view(P * K, Ht, L.NU).permute(1, 0, 2).contiguous()
+
+    def hip_update():
+        st.t = 0
+        rs.cma_update(E)
+
+    def th_update():
+        x = block.permute(1, 0, 2).reshape(P, K, Ht * L.NU)[:, :, :N].double()
+        adm = (failed == 0) & torch.isfinite(score)
+        top = torch.topk(torch.where(adm, score, float("-inf")), E, dim=1).indices
+        xe = torch.gather(x, 1, top[:, :, None].expand(P, E, N))
+        y = (xe - t["mean"][:, None, :]) / t["sigma"][:, None, None]
+        yw = torch.einsum("e,pen->pn", w, y)
+        R = torch.einsum("e,pea,peb->pab", w, y, y)
+        zw = torch.linalg.solve_triangular(t["chol"], yw[:, :, None], upper=False)[:, :, 0]
+        t["ps"] = (1 - cs) * t["ps"] + qs * zw
+        nrm = t["ps"].norm(dim=1)
+        hs = (nrm / (1 - (1 - cs) ** 2) ** 0.5 < (1.4 + 2 / (N + 1)) * hp["chi_n"]).double()
+        t["pc"] = (1 - cc) * t["pc"] + hs[:, None] * qc * yw
+        a0 = (1 - c1 - cmu) + (1 - hs) * c1 * cc * (2 - cc)
+        t["cov"] = a0[:, None, None] * t["cov"] + c1 * t["pc"][:, :, None] * t["pc"][:, None, :] + cmu * R
+        t["mean"] = (t["mean"] + t["sigma"][:, None] * yw).clamp_(-1, 1)
+        t["sigma"] = (t["sigma"] * torch.exp((cs / hp["d_sigma"]) * (nrm / hp["chi_n"] - 1))).clamp_(1e-6, 1.0)
+        if chol_ok is True:
+            t["chol"] = torch.linalg.cholesky_ex(t["cov"])[0]
+
+    th_update()
+    hip_update()
+    d_mean = float((t["mean"] - rs.mean_t.permute(1, 0, 2).reshape(P, Ht * L.NU)[:, :N].double()).abs().max())
+    d_cov = float((t["cov"] - st.cov_t).abs().max())
+    say(f"  torch form against the kernels after one update from the same state: largest difference of a new mean {d_mean:.1e} (float32 "
+        f"storage), of an entry of cov {d_cov:.1e}")
+    out = {}
+    for name, label, hip, th, inner in (("sample", "glgym_plan_cma_sample              ", hip_sample, th_sample, 5),
+                                        ("update", "glgym_plan_elites + _cma_update    ", hip_update, th_update, 5)):
+        for fn in (hip, th):
+            timed(torch, fn, 2)
+        a, b = compare(torch, hip, th, inner)
+        ma, mb = statistics.median(a), statistics.median(b)
+        out[name] = ma
+        say(f"  {label} us: " + " ".join(f"{v * 1e3:.1f}" for v in a) + f"   median {ma * 1e3:.1f} (spread {spread(a) * 100:.0f} %)")
+        say("  the same with torch ops             us: " + " ".join(f"{v * 1e3:.1f}" for v in b) + f"   median {mb * 1e3:.1f} (spread {spread(b) * 100:.0f} %)")
+        say(f"    ratio kernels / torch = {ma / mb:.3f}" + ("   (the kernels are NOT faster than their torch form)" if ma >= mb else ""))
+        keep.pop("block", None)
+    say(f"  rows updated by the last timed update: {int((st.status_t == 0).sum())} of {P} (the timed updates repeat on one population, so the state drifts)")
+
+    def iteration():
+        rs._draw = 0
+        rs.cma(1, E, seed=1)
+
+    for _ in range(N_WARM):
+        timed(torch, iteration, 1)
+    it = statistics.median([timed(torch, iteration, 1) for _ in range(5)])
+    say(f"  one cma() iteration at H = {rs.H} closed-loop steps ({P * K} children): {it:.3f} ms; the sample is {out['sample'] / it * 100:.3f} % of it, "
+        f"elites + update {out['update'] / it * 100:.3f} %")
+    say()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-pkg", default=None, help="built greenlight-gym2_amd directory of the parent commit")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "plan_cma_cost.txt"))
+    ap.add_argument("--iters", type=int, default=8)
+    ap.add_argument("--worker", nargs=6, default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(Path(args.worker[0]), *(int(v) for v in args.worker[1:4]), args.worker[4], args.worker[5])
+    torch, TomatoVecEnv, synthetic_weather = setup(ROOT / "greenlight-gym2_amd")
+    if not torch.cuda.is_available():
+        sys.exit("plan_cma_cost.py needs a GPU (no fallback)")
+    where = ("child processes on the parent commit's build (--parent-pkg)" if args.parent_pkg else "THIS build (no --parent-pkg given)")
+    lines = [f"CMA-ES with a full covariance matrix on the device: cost on {torch.cuda.get_device_name(0)} (tools/plan_cma_cost.py)",
+             f"fp32 ls5-128; device events, {N_WARM} warm-up windows, {N_SAMPLES} alternating samples; spread = (max - min) / median of a side's "
+             f"samples; the other side of (b) runs in {where}", ""]
+    say = lambda s="": (print(s, flush=True), lines.append(s))  # noqa: E731
+    w = synthetic_weather(n_rows=35040)
+
+    # ---- (a) the stages on their own, and their share of an iteration ------------------------------------------------------------------
+    chol_ok = has_device_cholesky(torch, "cuda:0")
+    say("(a) the stages against torch ops in float64 (randn, bmm, clamp / topk, gather, einsum, solve_triangular, linalg.cholesky_ex), recorded, "
+        "no requirement")
+    say("    torch.linalg.cholesky_ex on the device: " + ("available, part of the torch update" if chol_ok is True else
+                                                          f"NOT available in this torch build ({chol_ok}); the torch update is timed without it"))
+    envs = {}
+    for P, K in SHAPES:
+        envs[P] = parent_env(TomatoVecEnv, w, P)
+        for tune in (TUNE5, tune29()):
+            rs = envs[P].rule_search(K, H0, tune=tune)
+            stage_costs(torch, rs, say, chol_ok)
+            del rs
+            torch.cuda.empty_cache()
+    envs[8].close()
+    env = envs[64]
+    P, K, H = 64, 1024, H0
+    n = P * K
+
+    # ---- (b) the untouched paths against the parent commit's: requirement <= 1.05 ---------------------------------------------------------
+    rs = env.rule_search(K, H, tune=TUNE5)
+    other = Other(torch, args.parent_pkg, P, K, H, "cem", None, cem_iteration(rs), rs.plan)
+    mine = cem_iteration(rs)
+    mine()
+    my_sum = float(rs.plan.ret_t.sum())
+    a, b = compare(torch, mine, other)
+    other.close()
+    r_cem = statistics.median(a) / statistics.median(b)
+    verdict = lambda r: f"   (requirement <= 1.05: {'met' if r <= 1.05 else 'NOT MET'})" if args.parent_pkg else ""  # noqa: E731
+    say(f"(b) one RuleSearch.cem iteration at (P, K, H) = ({P}, {K}, {H}), this build / the parent commit's, ms: " + " ".join(f"{v:.3f}" for v in a)
+        + "  /  " + " ".join(f"{v:.3f}" for v in b))
+    say(f"      sum of the {n} returns {my_sum:.17g} / {other.sum:.17g} ({'equal' if my_sum == other.sum else 'DIFFERENT'})")
+    same = my_sum == other.sum
+    say(f"      medians {statistics.median(a):.3f} / {statistics.median(b):.3f} ms; spreads {spread(a) * 100:.1f} % / {spread(b) * 100:.1f} %; "
+        f"ratio = {r_cem:.4f}" + verdict(r_cem))
+    del rs
+    torch.cuda.empty_cache()
+    plan = env.planner(K, H)
+    g = torch.Generator().manual_seed(3)
+    fresh = (torch.rand(H, n, 6, generator=g) * 2 - 1).to(env.device).contiguous()
+    other = Other(torch, args.parent_pkg, P, K, H, "actions", fresh, lambda: plan.rollout(actions_t=fresh), plan)
+    a, b = compare(torch, lambda: plan.rollout(actions_t=fresh), other)
+    other.close()
+    my_sum = float(plan.ret_t.sum())
+    same = same and my_sum == other.sum
+    r_plan = statistics.median(a) / statistics.median(b)
+    say("    Planner.rollout(actions_t = uniform random actions), this build / the parent commit's, ms: " + " ".join(f"{v:.3f}" for v in a) + "  /  "
+        + " ".join(f"{v:.3f}" for v in b))
+    say(f"      sum of the {n} returns {my_sum:.17g} / {other.sum:.17g} ({'equal' if my_sum == other.sum else 'DIFFERENT'})")
+    say(f"      medians {statistics.median(a):.3f} / {statistics.median(b):.3f} ms; spreads {spread(a) * 100:.1f} % / {spread(b) * 100:.1f} %; "
+        f"ratio = {r_plan:.4f}" + verdict(r_plan))
+    say()
+    del plan, fresh
+    env.close()
+    torch.cuda.empty_cache()
+
+    # ---- (c) cma against cem on the example's problem --------------------------------------------------------------------------------------
+    from gl_gym_amd.baseline import RuleBasedController
+    B, Kc, Hc = 4, 64, 96
+    ex = parent_env(TomatoVecEnv, w, B, stride=96 * 30)
+    base = RuleBasedController()
+    search = ex.rule_search(Kc, Hc, tune=TUNE5, base=base)
+    at = lambda theta: search.rollout(theta.clamp(-1.0, 1.0).repeat_interleave(Kc, dim=1))[0][:, 0].mean().item()  # noqa: E731
+    default = float(search.rollout(search.theta_of(base))[0][:, 0].mean())
+    say(f"(c) examples/tune_rule_based.py's five set-points: {B} greenhouses a month apart, K = {Kc} candidate controllers, H = {Hc} closed-loop "
+        f"steps, {args.iters} iterations of each from the default controller (which scores {default:.4f}), seed 666; score = the mean return over the "
+        f"greenhouses; recorded, no requirement; one seed")
+    out = search.cma(args.iters, seed=666)
+    best, sig, upd = float(out["best_return"].mean()), out["sigma"].cpu().numpy(), int((out["status"] == 0).sum())
+    say(f"    cma (n_elite {Kc // 2}, init_sigma 0.3, Hansen's defaults): the last population's best {best:.4f}; the MEAN controller scores "
+        f"{at(out['mean']):.4f}; final sigma {' '.join(f'{v:.3f}' for v in sig)}; rows updated in the last generation {upd} of {B}")
+    for n_elite, init_std in ((Kc // 8, 0.5), (Kc // 2, 0.3)):
+        out = search.cem(args.iters, n_elite, init_std=init_std, carry=2, seed=666)
+        best = float(out["best_return"].mean())
+        say(f"    cem (n_elite {n_elite}, init_std {init_std}, alpha 0.1, carry 2): the last population's best {best:.4f}; the MEAN controller scores "
+            f"{at(out['mean']):.4f}")
+    say()
+    ex.close()
+    ok = r_cem <= 1.05 and r_plan <= 1.05 and same
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text("\n".join(lines) + "\n")
+    return 0 if (ok or not args.parent_pkg) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
