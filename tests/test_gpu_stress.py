@@ -6,7 +6,8 @@ outside air): a wet cover pinned to the top air at up to 750 1/s while its drive
 map can be silently wrong or report a failed integration, at rates that were MEASURED in round 3 (three seeds, 19 500 such tuples:
 fp64 2 gross + 10 failed, fp32 5 + 5; scipy's BDF at the reference's tolerances lands on the same wrong branch on the gross ones,
 DESIGN.md 2.5).  The thresholds are those rates with head-room for one seed: they catch a regression, they do not claim the corner
-is solved."""
+is solved.  The truth here comes from the kernel under test, so this is a regression guard only: tests/test_gpu_holdout_stress.py judges
+the kernels on the same five kinds, from held-out seeds, against a truth no integrator of the project produced, tuple by tuple."""
 import sys
 from pathlib import Path
 
