@@ -28,7 +28,7 @@ from the perturbed radiation, and vapour pressure, not relative humidity, is wha
 The parent environment is only read: its state, random streams, draw counter, episode counters, metrics() and step_flags_t are after
 a rollout what they were before.
 
-Iterated sampling (the cross-entropy method, glgym_plan_sample / _elites / _refit): cem() draws the candidates on the device from a
+Iterated sampling (the cross-entropy method, glgym_plan_sample / _elites / _refit; _CemStages below): cem() draws the candidates on the device from a
 Gaussian per (horizon step, greenhouse, actuator), simulates them, ranks each greenhouse's returns, refits mean and spread to the best
 n_elite, and repeats; sample(), elites() and refit() are the single stages, shift() the receding-horizon warm start.
 
@@ -46,10 +46,17 @@ hundreds of weights of a net.
 
 CMA-ES (glgym_plan_cma_sample / _cma_update; _CmaStages below): RuleSearch.cma() keeps a full covariance matrix per greenhouse over its
 at most 32 tuned constants -- the separable searches above cannot follow constants that interact -- with sample_cma() and cma_update()
-as the single stages.  PolicySearch and Planner have none: even a linear policy has 144 parameters."""
+as the single stages.  PolicySearch and Planner have none: even a linear policy has 144 parameters.
+
+How the code is shared.  One stage object per algorithm holds its library calls, argument checks and loop: _CemStages (Planner and both
+searches; it also owns the two population blocks every sampler writes into), _EsStages, _CmaStages.  _ThetaSearch is the base of
+RuleSearch and PolicySearch: the Planner they roll out on, theta in place or staged, the distribution, select, the start of a search
+(_start) and the CEM / ES methods; a subclass adds its argument checks, its rollout call and its defaults.  The three rollouts build
+their arguments with Planner._rollout_args and Planner._scenario_args."""
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -148,15 +155,10 @@ class Planner:
         self.mean_sequence_t = z(self.H, self.B, L.NU, dtype=torch.float32)
         self._actions_buf = self._controls_T = None                  # staging, allocated at first use
         self._actions = None                                         # the [H, C, 6] block of the last rollout (select reads it)
-        # the cross-entropy method's buffers, allocated at first use: two action blocks (a population is sampled into the one the
-        # previous population does not occupy, so that its elites can be carried over), elite indices, the distribution
-        self._cem_blocks = None
-        self._cem_cur = None                                         # which block holds the population sampled last
-        self._rolled = None                                          # which of the two blocks the last rollout simulated, if one of them
-        self._elites = None                                          # (E, block) of the last elites(): row length of elite_k_t, and the
-                                                                     # block it ranks if the next sample() may carry from it, else None
-        self.elite_k_t = self.n_elite_t = self.cem_mean_t = self.cem_std_t = None
         self.draw_base_t = z(1, dtype=torch.int64)                   # device word added to every draw index: add to it between replays
+        # the cross-entropy method's population state; its buffers, the elite indices and the distribution are allocated at first use
+        self._cem = _CemStages(self, self.B, self.H, self.draw_base_t, "horizon x num_envs x 6")
+        self.elite_k_t = self.n_elite_t = self.cem_mean_t = self.cem_std_t = None
         self._draw = 0                                               # draw index of cem()'s next population
         # what select() and elites() score: the children's own returns, or with scenarios the candidates' aggregated ones
         self._score_t, self._score_failed_t = self.ret_t, self.failed_t
@@ -246,12 +248,11 @@ class Planner:
                 raise ValueError(f"actions_t must hold horizon x (num_envs * n_candidates) x 6 = {n} values, got {tuple(actions_t.shape)}")
             if actions_t.dtype == torch.float32 and actions_t.is_cuda and actions_t.device == e.device and actions_t.is_contiguous():
                 self._actions = actions_t.view(self.H, self.J, L.NU)
-                self._rolled = next((i for i, b in enumerate(self._cem_blocks or ()) if actions_t is b), None)
             else:
                 if self._actions_buf is None:
                     self._actions_buf = torch.zeros(self.H, self.J, L.NU, dtype=torch.float32, device=e.device)
                 self._actions_buf.copy_(actions_t.reshape(self.H, self.J, L.NU))
-                self._actions, self._rolled = self._actions_buf, None
+                self._actions = self._actions_buf
             act_ptr = self._actions.data_ptr()
         else:
             if controls_t.numel() != n:
@@ -259,31 +260,44 @@ class Planner:
             if self._controls_T is None:
                 self._controls_T = torch.zeros(self.H, L.NU, self.ld, dtype=e.tdtype, device=e.device)
             self._controls_T[:, :, :self.C].copy_(controls_t.reshape(self.H, self.C, L.NU).transpose(1, 2))
-            self._actions = self._rolled = None
+            self._actions = None
             ctl_ptr = self._controls_T.data_ptr()
+        self._cem.note_rollout(actions_t)                            # one of the CEM's own blocks is always read in place
+        self._fork_children()
+        a = self._rollout_args(act_ptr, ctl_ptr)
+        if self.S:
+            sc = L.make_plan_args(L.PlanRolloutScenariosArgs, *self._scenario_args(), self.stage_t.data_ptr(), a)
+            L.check(e._lib.glgym_plan_rollout_scenarios(e._h, C.byref(sc), e._stream()), "glgym_plan_rollout_scenarios")
+        else:
+            L.check(e._lib.glgym_plan_rollout(e._h, C.byref(a), e._stream()), "glgym_plan_rollout")
+        return self._results()
+
+    # what the three rollouts (this one, RuleSearch's, PolicySearch's) share
+    def _fork_children(self):
+        """fork(), then with weather_sigma the scenarios' windows."""
         self.fork()
         if self.weather_window_t is not None:
             self._weather()
-        a = L.make_plan_args(L.PlanRolloutArgs, self.H, self.gamma, self._step_args(), act_ptr, ctl_ptr, self.ret_t.data_ptr(),
-                             self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.alive_t.data_ptr(), self.failed_t.data_ptr())
-        B, K = self.B, self.K
-        if self.S:
-            sc = L.make_plan_args(L.PlanRolloutScenariosArgs, B, K, self.S, 1 if self.noise == "hold" else 0, self.noise_scale,
-                                  self.scenario_seed & (2 ** 64 - 1), self._scen_draw, self.scenario_base_t.data_ptr(), self.stage_t.data_ptr(), a)
-            L.check(e._lib.glgym_plan_rollout_scenarios(e._h, C.byref(sc), e._stream()), "glgym_plan_rollout_scenarios")
-            return self._aggregate()
-        L.check(e._lib.glgym_plan_rollout(e._h, C.byref(a), e._stream()), "glgym_plan_rollout")
-        return self._results()
+
+    def _rollout_args(self, act_ptr, ctl_ptr):
+        """The glgym_plan_rollout_args over the children's buffers and accumulators, reading actions / controls planes at these pointers."""
+        return L.make_plan_args(L.PlanRolloutArgs, self.H, self.gamma, self._step_args(), act_ptr, ctl_ptr, self.ret_t.data_ptr(),
+                                self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.alive_t.data_ptr(), self.failed_t.data_ptr())
+
+    def _scenario_args(self):
+        """(B, K, S, hold, noise_scale, seed, draw, scenario_base) as the scenario rollouts take them; all zero without scenarios."""
+        if not self.S:
+            return (0, 0, 0, 0, 0.0, 0, 0, None)
+        return (self.B, self.K, self.S, 1 if self.noise == "hold" else 0, self.noise_scale, self.scenario_seed & (2 ** 64 - 1),
+                self._scen_draw, self.scenario_base_t.data_ptr())
 
     def _results(self):
-        """The five tensors rollout() returns without scenarios: views of the children's accumulators."""
-        B, K = self.B, self.K
-        return (self.ret_t.view(B, K), self.alive_t.view(B, K), self.n_steps_t.view(B, K), self.viol_T[:, :self.C].view(3, B, K),
-                self.failed_t.view(B, K))
-
-    def _aggregate(self):
-        """glgym_plan_aggregate over the S scenario runs of every candidate -> the five tensors rollout() returns with scenarios."""
+        """The five tensors a rollout returns: views of the children's accumulators, or with scenarios glgym_plan_aggregate over the S
+        runs of every candidate."""
         e, B, K = self.env, self.B, self.K
+        if not self.S:
+            return (self.ret_t.view(B, K), self.alive_t.view(B, K), self.n_steps_t.view(B, K), self.viol_T[:, :self.C].view(3, B, K),
+                    self.failed_t.view(B, K))
         g = L.make_plan_args(L.PlanAggregateArgs, self.J, self.S, self.n_tail, self.ld, self.ld_cand, self.ret_t.data_ptr(),
                              self.failed_t.data_ptr(), self.viol_T.data_ptr(), self.n_steps_t.data_ptr(), self.ret_cand_t.data_ptr(),
                              self.failed_cand_t.data_ptr(), self.viol_cand_T.data_ptr(), self.steps_cand_t.data_ptr())
@@ -328,83 +342,29 @@ class Planner:
 
     # ---- the cross-entropy method ------------------------------------------------------------------------------------------
     def _cem_alloc(self):
-        if self._cem_blocks is None:
-            torch, dev = self.torch, self.env.device
-            self._cem_blocks = [torch.zeros(self.H, self.J, L.NU, dtype=torch.float32, device=dev) for _ in range(2)]
-            self.elite_k_t = torch.full((self.J,), -1, dtype=torch.int32, device=dev)       # rows of E <= K entries: [B, E] is a view
-            self.n_elite_t = torch.zeros(self.B, dtype=torch.int32, device=dev)
-            self.cem_mean_t = torch.zeros(self.H, self.B, L.NU, dtype=torch.float32, device=dev)
-            self.cem_std_t = torch.zeros(self.H, self.B, L.NU, dtype=torch.float32, device=dev)
-
-    def _drop_carry(self):
-        if self._elites:
-            self._elites = (self._elites[0], None)
-
-    def _check_dist(self, mean_t, std_t):
-        torch, n = self.torch, self.H * self.B * L.NU
-        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
-            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.env.device or not t.is_contiguous()
-                    or t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of horizon x num_envs x 6 = {n} values on the environment's device")
+        """The first CEM call allocates (a random-shooting planner never does): the population blocks, the elite indices, the distribution."""
+        if self.cem_mean_t is None:
+            self.elite_k_t, self.n_elite_t = self._cem.alloc()
+            self.cem_mean_t = self.torch.zeros(self.H, self.B, L.NU, dtype=self.torch.float32, device=self.env.device)
+            self.cem_std_t = self.torch.zeros_like(self.cem_mean_t)
 
     def sample(self, mean_t, std_t, beta: float = 0.0, seed: int = 0, draw_index: int = 0, carry: int = 0):
         """glgym_plan_sample: draw the population [H, B*K, 6] from N(mean_t, std_t) [H, B, 6] with lag-1 correlation beta along the
         horizon, clipped to [-1, 1], into the planner's action block that the previous population does not occupy; returns it (pass it
         to rollout()).  Candidate 0 is the clipped mean; with carry >= 1, and elites() of the previous sampled population at hand,
         candidates 1 .. carry are its best sequences.  Noise: Philox keyed by seed, counter (child, step, draw_index + draw_base_t)."""
-        self._check_dist(mean_t, std_t)
-        if not 0.0 <= float(beta) < 1.0:
-            raise ValueError("beta must be in [0, 1)")
-        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
-            raise ValueError("carry, seed and draw_index must be >= 0")
-        n_elites, src = self._elites or (0, None)
-        carried = int(carry) if src is not None else 0           # nothing ranked to carry from: every candidate but 0 is sampled
-        if carried > n_elites:
-            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
-        self._cem_alloc()
-        e = self.env
-        dst = 0 if self._cem_cur is None else 1 - self._cem_cur      # src, when set, is _cem_cur: the other block
-        prev = self._cem_blocks[src].data_ptr() if carried else None
-        a = L.make_plan_args(L.PlanSampleArgs, self.B, self.K, self.H, mean_t.data_ptr(), std_t.data_ptr(), float(beta),
-                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.draw_base_t.data_ptr(),
-                             self._cem_blocks[dst].data_ptr(), carried, n_elites if carried else 0, prev,
-                             self.elite_k_t.data_ptr() if carried else None, self.n_elite_t.data_ptr() if carried else None)
-        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
-        self._cem_cur = dst
-        self._elites = (n_elites, None) if self._elites else None    # they rank another population than the one sampled last
-        return self._cem_blocks[dst]
+        return self._cem.sample(mean_t, std_t, beta, seed, draw_index, carry)
 
     def elites(self, n_elite: int):
         """glgym_plan_elites on the last rollout: (elite_k [B, n_elite] i32 -- the admissible candidates by return, best first, ties to
         the lower index, padded with -1 --, n_elite [B] i32).  Views of planner buffers, overwritten by the next call."""
-        E = int(n_elite)
-        if not 1 <= E <= self.K:
-            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
-        self._cem_alloc()
-        e = self.env
-        a = L.make_plan_args(L.PlanElitesArgs, self.B, self.K, E, self._score_t.data_ptr(), self._score_failed_t.data_ptr(), self.elite_k_t.data_ptr(),
-                             self.n_elite_t.data_ptr())
-        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
-        self._elites = (E, self._rolled if self._rolled == self._cem_cur else None)
-        return self.elite_k_t[:self.B * E].view(self.B, E), self.n_elite_t
+        return self._cem.elites(self._score_t, self._score_failed_t, n_elite)
 
     def refit(self, mean_t, std_t, alpha: float, min_std: float):
         """glgym_plan_refit, in place on mean_t / std_t [H, B, 6]: mean <- alpha*mean + (1-alpha)*(the elites' mean), std <-
         max(alpha*std + (1-alpha)*(their standard deviation, ddof 0), min_std), over the elites() of the last rollout's actions.  A
         greenhouse without an elite keeps its row."""
-        self._check_dist(mean_t, std_t)
-        if not 0.0 <= float(alpha) < 1.0:
-            raise ValueError("alpha must be in [0, 1)")
-        if not 0.0 <= float(min_std) < float("inf"):
-            raise ValueError("min_std must be finite and >= 0")
-        if self._actions is None or self._elites is None:
-            raise ValueError("refit needs a rollout of actions_t and its elites()")
-        e = self.env
-        a = L.make_plan_args(L.PlanRefitArgs, self.B, self.K, self.H, self._elites[0], self._actions.data_ptr(), self.elite_k_t.data_ptr(),
-                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
-                             mean_t.data_ptr(), std_t.data_ptr())
-        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
-        return mean_t, std_t
+        return self._cem.refit(self._actions, mean_t, std_t, alpha, min_std)
 
     def cem(self, n_iter: int, n_elite: int, init_std: float = 0.5, min_std: float = 0.05, alpha: float = 0.1, beta: float = 0.0,
             carry: int = 0, seed: int = 0, mean_t=None, std_t=None) -> Dict[str, Any]:
@@ -418,35 +378,21 @@ class Planner:
         first call, no allocation: a whole cem() can be captured in a graph (add n_iter to draw_base_t between replays for fresh
         noise).  With scenarios every iteration scores its population on the SAME futures (a carried elite keeps its score); call
         new_scenarios(), or add to scenario_base_t between replays, for other ones."""
-        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
-        if n_iter < 1:
-            raise ValueError("n_iter must be at least 1")
-        if not 1 <= E <= self.K:
-            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
-        if not 0 <= carry <= E:
-            raise ValueError("carry must be in 0 .. n_elite")
-        if not 0.0 <= float(beta) < 1.0 or not 0.0 <= float(alpha) < 1.0:
-            raise ValueError("alpha and beta must be in [0, 1)")
-        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
-            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
+        st = self._cem
+        n_iter, E, carry = st.check_hyper(n_iter, n_elite, carry, init_std, min_std, alpha, beta, seed)
         self._cem_alloc()
         if mean_t is not None or std_t is not None:
-            self._check_dist(mean_t if mean_t is not None else std_t, std_t if std_t is not None else mean_t)
+            st.check_dist(mean_t if mean_t is not None else std_t, std_t if std_t is not None else mean_t)
         if mean_t is None:
             self.cem_mean_t.zero_()
-            self._drop_carry()
+            st.drop_carry()
         elif mean_t.data_ptr() != self.cem_mean_t.data_ptr():
             self.cem_mean_t.copy_(mean_t.view(self.H, self.B, L.NU))
         if std_t is None:
             self.cem_std_t.fill_(float(init_std))
         elif std_t.data_ptr() != self.cem_std_t.data_ptr():
             self.cem_std_t.copy_(std_t.view(self.H, self.B, L.NU))
-        for _ in range(n_iter):
-            block = self.sample(self.cem_mean_t, self.cem_std_t, beta=beta, seed=seed, draw_index=self._draw, carry=carry)
-            self._draw += 1
-            self.rollout(block)
-            elite_k, n_el = self.elites(E)
-            self.refit(self.cem_mean_t, self.cem_std_t, alpha, min_std)
+        elite_k, n_el = st.run(self.cem_mean_t, self.cem_std_t, n_iter, E, alpha, min_std, beta, carry, seed)
         sel = self.select(sequence=True)
         return {"mean_sequence": self.cem_mean_t, "std_sequence": self.cem_std_t, "best_sequence": sel["best_sequence"],
                 "best_action": sel["best_action"], "best_return": sel["best_return"], "best_k": sel["best_k"], "elite_k": elite_k,
@@ -463,7 +409,7 @@ class Planner:
             if self.H > 1:
                 t[:-1].copy_(t[1:].clone())
             t[-1].fill_(last)
-        self._drop_carry()
+        self._cem.drop_carry()
         return self.cem_mean_t, self.cem_std_t
 
 
@@ -513,6 +459,7 @@ class RuleParams:
                 raise ValueError(f"base: the proportional band {n} is 0 (the rules divide by it)")
 
     def struct(self):
+        """The glgym_rule_space: the base controller's 29 constants, and field index, lo and hi of every tuned one."""
         s = L.RuleSpace()
         s.base = L.RuleCfg(*[float(getattr(self.base, n)) for n in L.RULE_FIELDS])
         s.D = self.D
@@ -531,6 +478,7 @@ class RuleParams:
         return self.np.array([float(getattr(src, n)) for n in self.names], dtype=self.np.float64)
 
     def inside(self, controller_or_dict) -> bool:
+        """Whether every tuned constant of the controller (or dict) lies within its bounds: whether encode() takes it."""
         v = self.values(controller_or_dict)
         return bool(((self.lo <= v) & (v <= self.hi)).all())
 
@@ -557,19 +505,145 @@ class RuleParams:
         return {n: v[:, i].copy() for i, n in enumerate(self.names)}
 
 
+# ---- the cross-entropy method's stages (include/glgym.h glgym_plan_sample / _elites / _refit) ----------------------------------------
+class _CemStages:
+    """sample, elites and refit over a population block [Hd, P*K, 6], in one place for Planner (Hd = H, P = B, its own beta) and the
+    theta searches (Hd = Ht, P = B or 1, beta = 0), and the population state every sampler shares: `blocks`, the two blocks (a
+    population is sampled into the one the previous population does not occupy, so that its elites can be carried over); `cur`, which of
+    them holds the population sampled last; `rolled`, which of them the last rollout simulated, if one of them; `ranked`, (E, block) of
+    the last elites(): the row length of elite_k_t, and the block it ranks if the next sample() may carry from it, else None.
+    `owner` supplies env, torch, K, rollout, elites, refit, _draw and _cem_alloc, which is called before the first launch and has
+    alloc() allocate: Planner at its first CEM call, the searches in __init__.  What a rollout leaves behind -- its block and the scores
+    -- stays with the owner and is passed to elites() and refit().  The owner holds the stages, the stages only a weak reference back:
+    without a reference cycle a dropped planner frees its device buffers at once, not at the next garbage collection."""
+
+    def __init__(self, owner, P, Hd, draw_base_t, dist_doc):
+        self.o, self.P, self.Hd, self.draw_base_t, self.dist_doc = weakref.proxy(owner), int(P), int(Hd), draw_base_t, dist_doc
+        self.blocks = self.cur = self.rolled = self.ranked = None
+        self.elite_k_t = self.n_elite_t = None
+
+    def alloc(self):
+        """-> (elite_k_t [P*K] i32: rows of E <= K entries, [P, E] is a view; n_elite_t [P] i32), after the two blocks."""
+        torch, dev, J = self.o.torch, self.o.env.device, self.P * self.o.K
+        self.blocks = [torch.zeros(self.Hd, J, L.NU, dtype=torch.float32, device=dev) for _ in range(2)]
+        self.elite_k_t = torch.full((J,), -1, dtype=torch.int32, device=dev)
+        self.n_elite_t = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        return self.elite_k_t, self.n_elite_t
+
+    # the population state, for every sampler (sample below, _EsStages.sample_mirrored, _CmaStages.sample) and every rollout
+    def free(self):
+        """Index of the block the next population goes into."""
+        return 0 if self.cur is None else 1 - self.cur
+
+    def occupy(self, dst):
+        """A population was sampled into blocks[dst]: the elites at hand rank another one, and none of them is carried."""
+        self.cur = dst
+        self.drop_carry()
+        return self.blocks[dst]
+
+    def drop_carry(self):
+        if self.ranked:
+            self.ranked = (self.ranked[0], None)
+
+    def note_rollout(self, block_t):
+        """The owner's rollout reads block_t (None: something else than a tensor read in place)."""
+        self.rolled = next((i for i, b in enumerate(self.blocks or ()) if block_t is b), None)
+
+    def check_dist(self, mean_t, std_t):
+        torch, n = self.o.torch, self.Hd * self.P * L.NU
+        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
+            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.o.env.device or not t.is_contiguous()
+                    or t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {self.dist_doc} = {n} values on the environment's device")
+
+    def sample(self, mean_t, std_t, beta=0.0, seed=0, draw_index=0, carry=0):
+        self.check_dist(mean_t, std_t)
+        if not 0.0 <= float(beta) < 1.0:
+            raise ValueError("beta must be in [0, 1)")
+        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
+            raise ValueError("carry, seed and draw_index must be >= 0")
+        n_elites, src = self.ranked or (0, None)
+        carried = int(carry) if src is not None else 0               # nothing ranked to carry from: every candidate but 0 is sampled
+        if carried > n_elites:
+            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
+        self.o._cem_alloc()
+        e, dst = self.o.env, self.free()                             # src, when set, is cur: the other block
+        a = L.make_plan_args(L.PlanSampleArgs, self.P, self.o.K, self.Hd, mean_t.data_ptr(), std_t.data_ptr(), float(beta),
+                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.draw_base_t.data_ptr(),
+                             self.blocks[dst].data_ptr(), carried, n_elites if carried else 0,
+                             self.blocks[src].data_ptr() if carried else None, self.elite_k_t.data_ptr() if carried else None,
+                             self.n_elite_t.data_ptr() if carried else None)
+        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
+        return self.occupy(dst)
+
+    def elites(self, score_t, score_failed_t, n_elite):
+        E = int(n_elite)
+        if not 1 <= E <= self.o.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.o.K}")
+        self.o._cem_alloc()
+        e = self.o.env
+        a = L.make_plan_args(L.PlanElitesArgs, self.P, self.o.K, E, score_t.data_ptr(), score_failed_t.data_ptr(), self.elite_k_t.data_ptr(),
+                             self.n_elite_t.data_ptr())
+        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
+        self.ranked = (E, self.rolled if self.rolled == self.cur else None)
+        return self.elite_k_t[:self.P * E].view(self.P, E), self.n_elite_t
+
+    def refit(self, block_t, mean_t, std_t, alpha, min_std):
+        """block_t: the block of the owner's last rollout, None if it read none."""
+        self.check_dist(mean_t, std_t)
+        if not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf"):
+            raise ValueError("min_std must be finite and >= 0")
+        if block_t is None or self.ranked is None:
+            raise ValueError("refit needs a rollout (of actions or theta, not of raw controls) and its elites()")
+        e = self.o.env
+        a = L.make_plan_args(L.PlanRefitArgs, self.P, self.o.K, self.Hd, self.ranked[0], block_t.data_ptr(), self.elite_k_t.data_ptr(),
+                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
+                             mean_t.data_ptr(), std_t.data_ptr())
+        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
+        return mean_t, std_t
+
+    def check_hyper(self, n_iter, n_elite, carry, init_std, min_std, alpha, beta, seed):
+        """ValueError on what cem() refuses; -> (n_iter, n_elite, carry) as ints."""
+        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
+        if n_iter < 1:
+            raise ValueError("n_iter must be at least 1")
+        if not 1 <= E <= self.o.K:
+            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.o.K}")
+        if not 0 <= carry <= E:
+            raise ValueError("carry must be in 0 .. n_elite")
+        if not 0.0 <= float(beta) < 1.0 or not 0.0 <= float(alpha) < 1.0:
+            raise ValueError("alpha and beta must be in [0, 1)")
+        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
+            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
+        return n_iter, E, carry
+
+    def run(self, mean_t, std_t, n_iter, n_elite, alpha, min_std, beta, carry, seed):
+        """n_iter x (sample -> rollout -> elites -> refit) on the owner's distribution; -> the last elites()."""
+        o = self.o
+        for _ in range(n_iter):
+            block = self.sample(mean_t, std_t, beta, seed, o._draw, carry)
+            o._draw += 1
+            o.rollout(block)
+            ranked = o.elites(n_elite)
+            o.refit(mean_t, std_t, alpha, min_std)
+        return ranked
+
+
 # ---- evolution strategy over theta (include/glgym.h glgym_plan_es_sample / _es_utilities / _es_update) -------------------------------
 class _EsStages:
-    """The evolution strategy's stages for RuleSearch and PolicySearch, in one place.  `search` supplies env, K, Ht, plan, its two
-    population blocks (_blocks, _cur), the block of its last rollout (_theta), _check_dist, rollout, select, mean_t / std_t and _draw;
-    P is the number of distribution rows, score_t / score_failed_t [P*K] what its rollouts leave behind.  Built at the first ES call,
-    which is the only one that allocates: u_t [P*K] f64, n_adm_t [P] i32, the Adam moments m1_t / m2_t [Ht, P, 6] f64, and t_base_t,
-    the device word added to every step count (as plan.draw_base_t is to every draw index)."""
+    """The evolution strategy's stages for the theta searches, in one place.  `search` (a _ThetaSearch) supplies env, K, Ht, plan, the
+    population state (_cem: the two blocks and which one is free), the block of its last rollout (_theta), rollout, select, _start,
+    mean_t / std_t and _draw, P, the number of distribution rows, and score_t / score_failed_t [P*K], what its rollouts leave behind.
+    Built at the first ES call, which is the only one that allocates: u_t [P*K] f64, n_adm_t [P] i32, the Adam moments m1_t / m2_t
+    [Ht, P, 6] f64, and t_base_t, the device word added to every step count (as plan.draw_base_t is to every draw index)."""
 
-    def __init__(self, search, P, score_t, score_failed_t):
+    def __init__(self, search):
         torch, dev = search.torch, search.env.device
         if search.K < 2 or search.K % 2:
             raise ValueError(f"the evolution strategy draws mirrored pairs: n_candidates must be even and >= 2, got {search.K}")
-        self.s, self.P, self.score_t, self.score_failed_t = search, int(P), score_t, score_failed_t
+        self.s, self.P, self.score_t, self.score_failed_t = search, search.P, search.score_t, search.score_failed_t
         self.u_t = torch.zeros(self.P * search.K, dtype=torch.float64, device=dev)
         self.n_adm_t = torch.zeros(self.P, dtype=torch.int32, device=dev)
         self.m1_t = torch.zeros(search.Ht, self.P, L.NU, dtype=torch.float64, device=dev)
@@ -585,16 +659,14 @@ class _EsStages:
 
     def sample_mirrored(self, mean_t, std_t, seed=0, draw_index=0):
         s, e = self.s, self.s.env
-        s._check_dist(mean_t, std_t)
+        s._cem.check_dist(mean_t, std_t)
         if int(seed) < 0 or int(draw_index) < 0:
             raise ValueError("seed and draw_index must be >= 0")
-        dst = 0 if s._cur is None else 1 - s._cur
+        dst = s._cem.free()
         a = L.make_plan_args(L.PlanEsSampleArgs, self.P, s.K, s.Ht, mean_t.data_ptr(), std_t.data_ptr(), int(seed) & (2 ** 64 - 1),
-                             int(draw_index) & (2 ** 64 - 1), s.plan.draw_base_t.data_ptr(), s._blocks[dst].data_ptr())
+                             int(draw_index) & (2 ** 64 - 1), s.plan.draw_base_t.data_ptr(), s._cem.blocks[dst].data_ptr())
         L.check(e._lib.glgym_plan_es_sample(e._h, C.byref(a), e._stream()), "glgym_plan_es_sample")
-        s._cur = dst
-        s._elites = (s._elites[0], None) if s._elites else None      # no elite of an overwritten block is carried
-        return s._blocks[dst]
+        return s._cem.occupy(dst)
 
     def utilities(self):
         s, e = self.s, self.s.env
@@ -624,7 +696,7 @@ class _EsStages:
 
     def update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
         s, e = self.s, self.s.env
-        s._check_dist(mean_t, std_t)
+        s._cem.check_dist(mean_t, std_t)
         b1, b2 = self.check_hyper(lr, lr_std, std_decay, min_std, max_std, optimizer, betas, eps)
         if self._scored is None or self._scored is not s._theta:
             raise ValueError("es_update needs a rollout and its utilities()")
@@ -647,12 +719,7 @@ class _EsStages:
         if resume and mean is not None:
             raise ValueError("resume=True continues from mean_t / std_t: it takes no mean")
         if not resume:
-            if mean is not None:
-                if mean.numel() not in (s.Ht * L.NU, s.Ht * self.P * L.NU):
-                    raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
-                s.mean_t.copy_(mean.reshape(s.Ht, -1, L.NU))
-            else:
-                s._es_start()
+            s._start(mean)
             s.std_t.fill_(float(init_std))
             self.restart()
         for _ in range(n_iter):
@@ -679,11 +746,12 @@ _ES_DOC = """Evolution strategy: n_iter x (sample_mirrored -> rollout -> utiliti
 
 # ---- CMA-ES with a full covariance matrix over theta (include/glgym.h glgym_plan_cma_sample / _cma_update) ---------------------------
 class _CmaStages:
-    """The CMA-ES stages for RuleSearch.  `search` supplies env, B, K, D, Ht, plan, its two population blocks (_blocks, _cur), the block
-    of its last rollout (_theta), elites, rollout, select, mean_t and _draw.  Built at the first CMA call, which is the only one that
-    allocates: sigma_t [B] f64, cov_t / chol_t [B, N, N] f64, p_sigma_t / p_c_t [B, N] f64, status_t [B] i32, the weights on the device
-    (one array per n_elite, kept), and t_base_t, the device word added to every generation count.  A policy net is not served: even a
-    linear policy has 144 parameters, and a 144 x 144 matrix per row is another design."""
+    """The CMA-ES stages for RuleSearch.  `search` supplies env, B, K, D, Ht, plan, the population state (_cem: the two blocks, which
+    one is free, the elites), the block of its last rollout (_theta), elites, rollout, select, _start, mean_t and _draw.  Built at the
+    first CMA call, which is the only one that allocates: sigma_t [B] f64, cov_t / chol_t [B, N, N] f64, p_sigma_t / p_c_t [B, N] f64,
+    status_t [B] i32, the weights on the device (one array per n_elite, kept), and t_base_t, the device word added to every generation
+    count.  A policy net is not served: even a linear policy has 144 parameters, and a 144 x 144 matrix per row is another design
+    (DESIGN.md section 2.18)."""
 
     def __init__(self, search):
         torch, dev = search.torch, search.env.device
@@ -720,13 +788,12 @@ class _CmaStages:
         s, e = self.s, self.s.env
         if int(seed) < 0 or int(draw_index) < 0:
             raise ValueError("seed and draw_index must be >= 0")
-        dst = 0 if s._cur is None else 1 - s._cur
+        dst = s._cem.free()
         a = L.make_plan_args(L.PlanCmaSampleArgs, self.P, s.K, self.N, s.mean_t.data_ptr(), self.sigma_t.data_ptr(), self.chol_t.data_ptr(),
-                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), s.plan.draw_base_t.data_ptr(), s._blocks[dst].data_ptr())
+                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), s.plan.draw_base_t.data_ptr(),
+                             s._cem.blocks[dst].data_ptr())
         L.check(e._lib.glgym_plan_cma_sample(e._h, C.byref(a), e._stream()), "glgym_plan_cma_sample")
-        s._cur = dst
-        s._elites = (s._elites[0], None) if s._elites else None      # no elite of an overwritten block is carried
-        return s._blocks[dst]
+        return s._cem.occupy(dst)
 
     @staticmethod
     def check_hyper(N, E, hp, min_sigma, max_sigma):
@@ -755,7 +822,7 @@ class _CmaStages:
     def update(self, E, hp, min_sigma, max_sigma):
         s, e = self.s, self.s.env
         w = self.check_hyper(self.N, E, hp, min_sigma, max_sigma)
-        if s._theta is None or s._elites is None or s._elites[0] != E:
+        if s._theta is None or s._cem.ranked is None or s._cem.ranked[0] != E:
             raise ValueError("cma_update needs a rollout and its elites()")
         w_host, w_dev = self.weights(w)
         a = L.make_plan_args(L.PlanCmaUpdateArgs, self.P, s.K, self.N, E, s._theta.data_ptr(), s.elite_k_t.data_ptr(), s.n_elite_t.data_ptr(),
@@ -784,12 +851,7 @@ class _CmaStages:
         if resume and mean is not None:
             raise ValueError("resume=True continues from mean_t and the CMA state: it takes no mean")
         if not resume:
-            if mean is not None:
-                if mean.numel() not in (s.Ht * L.NU, s.Ht * self.P * L.NU):
-                    raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
-                s.mean_t.copy_(mean.reshape(s.Ht, -1, L.NU))
-            else:
-                s._es_start()
+            s._start(mean)
             self.restart(init_sigma)
         for _ in range(n_iter):
             block = self.sample(seed=seed, draw_index=s._draw)
@@ -802,7 +864,158 @@ class _CmaStages:
                 "mean": s.mean_t, "sigma": self.sigma_t, "cov": self.cov_t, "status": self.status_t}
 
 
-class RuleSearch:
+class _ThetaSearch:
+    """What the searches over a feedback law's parameters share (RuleSearch, PolicySearch).  A candidate is a row of the float32 block
+    theta [Ht, J, 6], Ht = ceil(D / 6), J = P*K: K candidates for each of P distribution rows [Ht, P, 6] (mean_t / std_t).  A Planner
+    (self.plan) owns the children's buffers, the fork, the accumulators, the scenarios and the weather windows.  theta has the layout of
+    an action block of horizon Ht, so the CEM stages are the library's, called with H = Ht and beta = 0 (_CemStages); _EsStages and,
+    where a subclass offers it, _CmaStages sample into the same two population blocks.
+
+    A subclass checks its own arguments (after _check_scenario_kwargs, before the environment is touched by this constructor), gives
+    D, Ht and P, and writes rollout(): _take(theta_t), plan._fork_children(), its library call on plan._rollout_args() and
+    plan._scenario_args(), then plan._results().  It may override _es_start (where a search starts without a mean), replace score_t /
+    score_failed_t [P*K] (what elites, utilities and select rank: by default the plan's) and best_k_t / best_ret_t [P], and wrap cem /
+    es with its own defaults."""
+
+    SCENARIO_KEYS = ("n_scenarios", "n_tail", "noise", "noise_scale", "scenario_seed", "weather_sigma", "weather_phi")
+
+    @classmethod
+    def _check_scenario_kwargs(cls, scenario_kwargs):
+        unknown = sorted(set(scenario_kwargs) - set(cls.SCENARIO_KEYS))
+        if unknown:
+            raise TypeError(f"unexpected arguments {unknown}; the scenario arguments are {cls.SCENARIO_KEYS}")
+
+    def __init__(self, env, n_candidates, horizon, gamma, scenario_kwargs, D, Ht, P):
+        self.plan = p = Planner(env, n_candidates, horizon, gamma=gamma, crop="nominal", **scenario_kwargs)
+        self.env, self.torch = env, env.torch
+        torch, dev = env.torch, env.device
+        self.B, self.K, self.H, self.C, self.S = p.B, p.K, p.H, p.C, p.S
+        self.D, self.Ht, self.P = int(D), int(Ht), int(P)            # P distributions: rows of mean / std, calls of the stages
+        self.J = self.P * self.K                                     # rows of theta
+        Ht, P = self.Ht, self.P
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
+        self._theta_buf = None
+        self._theta = None                                           # the [Ht, J, 6] block of the last rollout
+        self._cem = _CemStages(self, P, Ht, p.draw_base_t, f"ceil(D / 6) x {P} x 6")
+        self.elite_k_t, self.n_elite_t = self._cem.alloc()
+        self.mean_t, self.std_t = z(Ht, P, L.NU), z(Ht, P, L.NU)
+        self.best_sequence_t = z(Ht, P, L.NU)
+        self.best_theta_t = z(P, Ht * L.NU)
+        self.score_t, self.score_failed_t = p._score_t, p._score_failed_t
+        self.best_k_t, self.best_ret_t = p.best_k_t, p.best_ret_t
+        self._draw = 0
+        self._es_stages = None
+        self.scenario_returns = getattr(p, "scenario_returns", None)
+        self.scenario_failed = getattr(p, "scenario_failed", None)
+
+    def _cem_alloc(self):
+        """Nothing left to do: __init__ has allocated."""
+
+    def _take(self, theta_t):
+        """The front half of a rollout: theta_t as the block _theta -- a contiguous float32 tensor on the environment's device is read in
+        place, anything else is staged -- and the population block it is, if one."""
+        torch, e, p = self.torch, self.env, self.plan
+        n = self.Ht * self.J * L.NU
+        if theta_t.numel() != n:
+            raise ValueError(f"theta_t must hold ceil(D / 6) x {self.J} x 6 = {n} values, got {tuple(theta_t.shape)}")
+        if theta_t.dtype == torch.float32 and theta_t.is_cuda and theta_t.device == e.device and theta_t.is_contiguous():
+            self._theta = theta_t.view(self.Ht, self.J, L.NU)
+        else:
+            if self._theta_buf is None:
+                self._theta_buf = torch.zeros(self.Ht, self.J, L.NU, dtype=torch.float32, device=e.device)
+            self._theta_buf.copy_(theta_t.reshape(self.Ht, self.J, L.NU))
+            self._theta = self._theta_buf
+        self._cem.note_rollout(theta_t)                              # one of the population blocks is always read in place
+        p._actions = None                                            # the plan's own select / refit have nothing to read
+        p._cem.note_rollout(None)
+
+    def new_scenarios(self):
+        """Planner.new_scenarios: other futures from the next scenario rollout on."""
+        self.plan.new_scenarios()
+
+    def _es_start(self):
+        self.mean_t.zero_()
+
+    def _start(self, mean):
+        """Where cem(), es() and cma() start: `mean` [Ht, P, 6] or [Ht, 1, 6] copied into mean_t, without one _es_start()."""
+        if mean is None:
+            self._es_start()
+            return
+        if mean.numel() not in (self.Ht * L.NU, self.Ht * self.P * L.NU):
+            raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
+        self.mean_t.copy_(mean.reshape(self.Ht, -1, L.NU))
+
+    # ---- the cross-entropy method over theta (_CemStages) ------------------------------------------------------------------------------
+    def sample(self, mean_t, std_t, seed: int = 0, draw_index: int = 0, carry: int = 0):
+        """glgym_plan_sample with H = Ht, beta = 0: the population theta [Ht, J, 6] from N(mean_t, std_t) [Ht, P, 6], clipped to
+        [-1, 1], into the block the previous population does not occupy; returns it.  Candidate 0 is the clipped mean; with carry >= 1
+        and elites() of the previous sampled population at hand, candidates 1 .. carry are its best rows."""
+        return self._cem.sample(mean_t, std_t, 0.0, seed, draw_index, carry)
+
+    def elites(self, n_elite: int):
+        """glgym_plan_elites on the last rollout's scores: (elite_k [P, n_elite] i32, n_elite [P] i32), as Planner.elites."""
+        return self._cem.elites(self.score_t, self.score_failed_t, n_elite)
+
+    def refit(self, mean_t, std_t, alpha: float, min_std: float):
+        """glgym_plan_refit with H = Ht, in place on mean_t / std_t [Ht, P, 6], over the elites() of the last rollout's theta."""
+        return self._cem.refit(self._theta, mean_t, std_t, alpha, min_std)
+
+    def select(self) -> Dict[str, Any]:
+        """glgym_plan_select with H = Ht on the last rollout's scores: {"best_k" [P] i32 (-1: every candidate failed), "best_return"
+        [P] f64, "best_theta" [P, Ht*6] f32 (component i at [., i]; zeros without an admissible candidate)}.  Device tensors,
+        overwritten by the next call; no allocation."""
+        if self._theta is None:
+            raise ValueError("select needs a rollout")
+        e = self.env
+        a = L.make_plan_args(L.PlanSelectArgs, self.P, self.K, self.Ht, self.score_t.data_ptr(), self.score_failed_t.data_ptr(),
+                             self._theta.data_ptr(), self.best_k_t.data_ptr(), self.best_ret_t.data_ptr(), None,
+                             self.best_sequence_t.data_ptr(), 0.0, None)
+        L.check(e._lib.glgym_plan_select(e._h, C.byref(a), e._stream()), "glgym_plan_select")
+        self.best_theta_t.view(self.P, self.Ht, L.NU).copy_(self.best_sequence_t.permute(1, 0, 2))
+        return {"best_k": self.best_k_t, "best_return": self.best_ret_t, "best_theta": self.best_theta_t}
+
+    def _cem_search(self, n_iter, n_elite, init_std, min_std, alpha, carry, seed, mean):
+        """cem() of the subclasses: what select() returns, and mean, std, elite_k, n_elite."""
+        st = self._cem
+        n_iter, E, carry = st.check_hyper(n_iter, n_elite, carry, init_std, min_std, alpha, 0.0, seed)
+        self._start(mean)
+        self.std_t.fill_(float(init_std))
+        st.ranked = None                                             # nothing is carried into the first population
+        elite_k, n_el = st.run(self.mean_t, self.std_t, n_iter, E, alpha, min_std, 0.0, carry, seed)
+        out = dict(self.select())
+        out.update(mean=self.mean_t, std=self.std_t, elite_k=elite_k, n_elite=n_el)
+        return out
+
+    # ---- the evolution strategy over theta (_EsStages) -------------------------------------------------------------------------------
+    def _es(self):
+        if self._es_stages is None:
+            self._es_stages = _EsStages(self)
+        return self._es_stages
+
+    @property
+    def es_t_base(self):
+        """The device word added to every es_update step count (int64 [1])."""
+        return self._es().t_base_t
+
+    def sample_mirrored(self, mean_t, std_t, seed: int = 0, draw_index: int = 0):
+        """glgym_plan_es_sample with H = Ht: the population theta in mirrored pairs (rows 2m and 2m + 1 of a distribution row:
+        clip(mean + std e) and clip(mean - std e)), into the block the previous population does not occupy; returns it.  No reserved
+        candidate.  ValueError if n_candidates is odd."""
+        return self._es().sample_mirrored(mean_t, std_t, seed, draw_index)
+
+    def utilities(self):
+        """glgym_plan_es_utilities on the last rollout's scores: (u [P, K] f64 -- centred ranks 0.5 .. -0.5 over the admissible
+        candidates, -0.5 for the others, all 0 with fewer than two -- and n_adm [P] i32)."""
+        return self._es().utilities()
+
+    def es_update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
+        """glgym_plan_es_update with H = Ht, in place on mean_t / std_t, over the utilities() of the last rollout's theta.  The Adam
+        moments and the step count are this object's (es() restarts them)."""
+        return self._es().update(mean_t, std_t, lr, lr_std, std_decay, min_std=min_std, max_std=max_std, optimizer=optimizer, betas=betas,
+                                 eps=eps)
+
+
+class RuleSearch(_ThetaSearch):
     """Closed-loop rollouts of the rule-based controller, and the tuning of its constants by the cross-entropy method, on the device
     (TomatoVecEnv.rule_search).  A candidate is not a control sequence but a FEEDBACK LAW: a row of K per greenhouse of the float32 block
     theta [Ht, B*K, 6], Ht = ceil(D / 6), which decodes to the D tuned constants (RuleParams; the others come from `base`).  rollout()
@@ -817,45 +1030,24 @@ class RuleSearch:
     Limits.  dt must be a multiple of 450 s (check_rule_dt): the children's clocks are derived by the product form.  The steps are
     raw-control steps: under the default verify mode "auto" they run verified (TomatoVecEnv.set_verify).  The environment is only read."""
 
-    SCENARIO_KEYS = ("n_scenarios", "n_tail", "noise", "noise_scale", "scenario_seed", "weather_sigma", "weather_phi")
-
     def __init__(self, env, n_candidates: int, horizon: int, tune, base=None, gamma: float = 1.0, **scenario_kwargs):
-        unknown = sorted(set(scenario_kwargs) - set(self.SCENARIO_KEYS))
-        if unknown:
-            raise TypeError(f"unexpected arguments {unknown}; the scenario arguments are {self.SCENARIO_KEYS}")
+        self._check_scenario_kwargs(scenario_kwargs)
         check_rule_dt(env.dt)
         self.params = RuleParams(tune, base)
         self.base = self.params.base
-        self.plan = p = Planner(env, n_candidates, horizon, gamma=gamma, crop="nominal", **scenario_kwargs)
-        self.env, self.torch = env, env.torch
-        torch, dev = env.torch, env.device
-        self.B, self.K, self.H, self.J, self.C, self.S = p.B, p.K, p.H, p.J, p.C, p.S
-        self.D, self.Ht, self.names = self.params.D, self.params.Ht, self.params.names
+        super().__init__(env, n_candidates, horizon, gamma, scenario_kwargs, self.params.D, self.params.Ht, env.B)
+        torch, dev, B = env.torch, env.device, self.B
+        self.names = self.params.names
         self._space = self.params.struct()
-        Ht, B, J = self.Ht, self.B, self.J
-        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
         self._lo_t = torch.as_tensor(self.params.lo, device=dev).view(self.D, 1)
         self._span_t = torch.as_tensor(self.params.hi - self.params.lo, device=dev).view(self.D, 1)
-        self._plane_T = z(1, L.NU, p.ld, dtype=env.tdtype)           # the one control plane of record=False
+        self._plane_T = torch.zeros(1, L.NU, self.plan.ld, dtype=env.tdtype, device=dev)   # the one control plane of record=False
         self.controls_T = self.controls = None                       # record=True: [H, 6, ld] and its [H, C, 6] view
-        self._theta_buf = None
-        self._theta = None                                           # the [Ht, J, 6] block of the last rollout
-        self._blocks = [z(Ht, J, L.NU) for _ in range(2)]            # populations: sampled into the one the previous does not occupy
-        self._cur = self._rolled = self._elites = None
-        self.elite_k_t = torch.full((J,), -1, dtype=torch.int32, device=dev)
-        self.n_elite_t = z(B, dtype=torch.int32)
-        self.mean_t, self.std_t = z(Ht, B, L.NU), z(Ht, B, L.NU)
-        self.best_sequence_t = z(Ht, B, L.NU)
-        self.best_theta_t = z(B, Ht * L.NU)
-        self._dec_t = z(B, Ht * L.NU, dtype=torch.float64)
-        self._params_T = z(self.D, B, dtype=torch.float64)
+        self._dec_t = torch.zeros(B, self.Ht * L.NU, dtype=torch.float64, device=dev)
+        self._params_T = torch.zeros(self.D, B, dtype=torch.float64, device=dev)
         self.best_params = {n: self._params_T[i] for i, n in enumerate(self.names)}
         self._base_theta = torch.as_tensor(self.params.encode(self.base), device=dev) if self.params.inside(self.base) else None
-        self._draw = 0
-        self._es_stages = None
         self._cma_stages = None
-        self.scenario_returns = getattr(p, "scenario_returns", None)
-        self.scenario_failed = getattr(p, "scenario_failed", None)
 
     # ------------------------------------------------------------------------------------------------
     def encode(self, controller_or_dict):
@@ -884,118 +1076,30 @@ class RuleSearch:
         ones, scenario_returns / scenario_failed [B, K, S] holding the single runs.  record=True keeps the controls of every step:
         controls_T [H, 6, ld] and controls, its [H, C, 6] view (child c = (b*K + k)*S + s)."""
         torch, e, p = self.torch, self.env, self.plan
-        n = self.Ht * self.J * L.NU
-        if theta_t.numel() != n:
-            raise ValueError(f"theta_t must hold ceil(D / 6) x (num_envs * n_candidates) x 6 = {n} values, got {tuple(theta_t.shape)}")
-        if theta_t.dtype == torch.float32 and theta_t.is_cuda and theta_t.device == e.device and theta_t.is_contiguous():
-            self._theta = theta_t.view(self.Ht, self.J, L.NU)
-            self._rolled = next((i for i, b in enumerate(self._blocks) if theta_t is b), None)
-        else:
-            if self._theta_buf is None:
-                self._theta_buf = torch.zeros(self.Ht, self.J, L.NU, dtype=torch.float32, device=e.device)
-            self._theta_buf.copy_(theta_t.reshape(self.Ht, self.J, L.NU))
-            self._theta, self._rolled = self._theta_buf, None
+        self._take(theta_t)
         if record and self.controls_T is None:
             self.controls_T = torch.zeros(self.H, L.NU, p.ld, dtype=e.tdtype, device=e.device)
             self.controls = self.controls_T[:, :, :self.C].permute(0, 2, 1)
         planes = self.controls_T if record else self._plane_T
-        p._actions = p._rolled = None
-        p.fork()
-        if p.weather_window_t is not None:
-            p._weather()
-        a = L.make_plan_args(L.PlanRolloutArgs, self.H, p.gamma, p._step_args(), None, planes.data_ptr(), p.ret_t.data_ptr(),
-                             p.viol_T.data_ptr(), p.n_steps_t.data_ptr(), p.alive_t.data_ptr(), p.failed_t.data_ptr())
-        if self.S:
-            scen = (self.B, self.K, self.S, 1 if p.noise == "hold" else 0, p.noise_scale, p.scenario_seed & (2 ** 64 - 1), p._scen_draw,
-                    p.scenario_base_t.data_ptr())
-        else:
-            scen = (0, 0, 0, 0, 0.0, 0, 0, None)
-        r = L.make_plan_args(L.PlanRolloutRuleArgs, 1 if record else 0, a, self._space, self._theta.data_ptr(), p.start_day_t.data_ptr(),
-                             self.J, *scen)
+        p._fork_children()
+        r = L.make_plan_args(L.PlanRolloutRuleArgs, 1 if record else 0, p._rollout_args(None, planes.data_ptr()), self._space,
+                             self._theta.data_ptr(), p.start_day_t.data_ptr(), self.J, *p._scenario_args())
         L.check(e._lib.glgym_plan_rollout_rule(e._h, C.byref(r), e._stream()), "glgym_plan_rollout_rule")
-        return p._aggregate() if self.S else p._results()
-
-    def new_scenarios(self):
-        self.plan.new_scenarios()
-
-    # ---- the cross-entropy method over theta: the Planner's library stages with H = Ht ---------------------------------------
-    def _check_dist(self, mean_t, std_t):
-        torch, n = self.torch, self.Ht * self.B * L.NU
-        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
-            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.env.device or not t.is_contiguous()
-                    or t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of ceil(D / 6) x num_envs x 6 = {n} values on the environment's device")
-
-    def sample(self, mean_t, std_t, seed: int = 0, draw_index: int = 0, carry: int = 0):
-        """glgym_plan_sample with H = Ht, beta = 0: the population theta [Ht, B*K, 6] from N(mean_t, std_t) [Ht, B, 6], clipped to
-        [-1, 1], into the block the previous population does not occupy; returns it.  Candidate 0 is the clipped mean; with carry >= 1
-        and elites() of the previous sampled population at hand, candidates 1 .. carry are its best rows."""
-        self._check_dist(mean_t, std_t)
-        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
-            raise ValueError("carry, seed and draw_index must be >= 0")
-        n_elites, src = self._elites or (0, None)
-        carried = int(carry) if src is not None else 0
-        if carried > n_elites:
-            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
-        e = self.env
-        dst = 0 if self._cur is None else 1 - self._cur
-        a = L.make_plan_args(L.PlanSampleArgs, self.B, self.K, self.Ht, mean_t.data_ptr(), std_t.data_ptr(), 0.0,
-                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.plan.draw_base_t.data_ptr(),
-                             self._blocks[dst].data_ptr(), carried, n_elites if carried else 0,
-                             self._blocks[src].data_ptr() if carried else None, self.elite_k_t.data_ptr() if carried else None,
-                             self.n_elite_t.data_ptr() if carried else None)
-        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
-        self._cur = dst
-        self._elites = (n_elites, None) if self._elites else None
-        return self._blocks[dst]
-
-    def elites(self, n_elite: int):
-        """glgym_plan_elites on the last rollout's scores: (elite_k [B, n_elite] i32, n_elite [B] i32), as Planner.elites."""
-        E = int(n_elite)
-        if not 1 <= E <= self.K:
-            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
-        e, p = self.env, self.plan
-        a = L.make_plan_args(L.PlanElitesArgs, self.B, self.K, E, p._score_t.data_ptr(), p._score_failed_t.data_ptr(),
-                             self.elite_k_t.data_ptr(), self.n_elite_t.data_ptr())
-        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
-        self._elites = (E, self._rolled if self._rolled == self._cur else None)
-        return self.elite_k_t[:self.B * E].view(self.B, E), self.n_elite_t
-
-    def refit(self, mean_t, std_t, alpha: float, min_std: float):
-        """glgym_plan_refit with H = Ht, in place on mean_t / std_t [Ht, B, 6], over the elites() of the last rollout's theta."""
-        self._check_dist(mean_t, std_t)
-        if not 0.0 <= float(alpha) < 1.0:
-            raise ValueError("alpha must be in [0, 1)")
-        if not 0.0 <= float(min_std) < float("inf"):
-            raise ValueError("min_std must be finite and >= 0")
-        if self._theta is None or self._elites is None:
-            raise ValueError("refit needs a rollout and its elites()")
-        e = self.env
-        a = L.make_plan_args(L.PlanRefitArgs, self.B, self.K, self.Ht, self._elites[0], self._theta.data_ptr(), self.elite_k_t.data_ptr(),
-                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
-                             mean_t.data_ptr(), std_t.data_ptr())
-        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
-        return mean_t, std_t
+        return p._results()
 
     def select(self) -> Dict[str, Any]:
         """glgym_plan_select with H = Ht on the last rollout: {"best_k" [B] i32 (-1: every candidate failed), "best_return" [B] f64,
         "best_theta" [B, Ht*6] f32 (component i of greenhouse b at [b, i]; zeros without an admissible candidate), "best_params"
         {name: [B] f64}}.  Device tensors, overwritten by the next call; no allocation."""
-        if self._theta is None:
-            raise ValueError("select needs a rollout")
-        e, p = self.env, self.plan
-        a = L.make_plan_args(L.PlanSelectArgs, self.B, self.K, self.Ht, p._score_t.data_ptr(), p._score_failed_t.data_ptr(),
-                             self._theta.data_ptr(), p.best_k_t.data_ptr(), p.best_ret_t.data_ptr(), None,
-                             self.best_sequence_t.data_ptr(), 0.0, None)
-        L.check(e._lib.glgym_plan_select(e._h, C.byref(a), e._stream()), "glgym_plan_select")
-        self.best_theta_t.view(self.B, self.Ht, L.NU).copy_(self.best_sequence_t.permute(1, 0, 2))
+        out = super().select()
         # the header's decode with in-place operations: t = clamp, half = 0.5 * (t + 1), v = lo + span * half
         d = self._dec_t
         d.copy_(self.best_theta_t)
         d.nan_to_num_(nan=-1.0).clamp_(-1.0, 1.0).add_(1.0).mul_(0.5)
         self.torch.mul(d[:, :self.D].t(), self._span_t, out=self._params_T)
         self._params_T.add_(self._lo_t)
-        return {"best_k": p.best_k_t, "best_return": p.best_ret_t, "best_theta": self.best_theta_t, "best_params": self.best_params}
+        out["best_params"] = self.best_params
+        return out
 
     def cem(self, n_iter: int, n_elite: int, init_std: float = 0.5, min_std: float = 0.05, alpha: float = 0.1, carry: int = 0,
             seed: int = 0, mean=None) -> Dict[str, Any]:
@@ -1007,70 +1111,13 @@ class RuleSearch:
         Returns device tensors, overwritten by the next call: best_theta [B, Ht*6], best_params {name: [B]}, best_return, best_k,
         mean, std [Ht, B, 6], elite_k [B, n_elite], n_elite [B].  No host synchronisation and, after the first call, no allocation: a
         whole cem() can be captured in a graph (add n_iter to plan.draw_base_t between replays for fresh noise)."""
-        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
-        if n_iter < 1:
-            raise ValueError("n_iter must be at least 1")
-        if not 1 <= E <= self.K:
-            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
-        if not 0 <= carry <= E:
-            raise ValueError("carry must be in 0 .. n_elite")
-        if not 0.0 <= float(alpha) < 1.0:
-            raise ValueError("alpha must be in [0, 1)")
-        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
-            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
-        if mean is not None:
-            if mean.numel() not in (self.Ht * L.NU, self.Ht * self.B * L.NU):
-                raise ValueError(f"mean must hold ceil(D / 6) x (1 or num_envs) x 6 values, got {tuple(mean.shape)}")
-            self.mean_t.copy_(mean.reshape(self.Ht, -1, L.NU))
-        elif self._base_theta is not None:
-            self.mean_t.copy_(self._base_theta)
-        else:
-            self.mean_t.zero_()
-        self.std_t.fill_(float(init_std))
-        self._elites = None
-        for _ in range(n_iter):
-            block = self.sample(self.mean_t, self.std_t, seed=seed, draw_index=self._draw, carry=carry)
-            self._draw += 1
-            self.rollout(block)
-            elite_k, n_el = self.elites(E)
-            self.refit(self.mean_t, self.std_t, alpha, min_std)
-        sel = self.select()
-        return {"best_theta": sel["best_theta"], "best_params": sel["best_params"], "best_return": sel["best_return"], "best_k": sel["best_k"],
-                "mean": self.mean_t, "std": self.std_t, "elite_k": elite_k, "n_elite": n_el}
-
-    # ---- the evolution strategy over theta (_EsStages) -------------------------------------------------------------------------------
-    def _es(self):
-        if self._es_stages is None:
-            self._es_stages = _EsStages(self, self.B, self.plan._score_t, self.plan._score_failed_t)
-        return self._es_stages
+        return self._cem_search(n_iter, n_elite, init_std, min_std, alpha, carry, seed, mean)
 
     def _es_start(self):
         if self._base_theta is not None:
             self.mean_t.copy_(self._base_theta)
         else:
             self.mean_t.zero_()
-
-    @property
-    def es_t_base(self):
-        """The device word added to every es_update step count (int64 [1])."""
-        return self._es().t_base_t
-
-    def sample_mirrored(self, mean_t, std_t, seed: int = 0, draw_index: int = 0):
-        """glgym_plan_es_sample with H = Ht: the population theta in mirrored pairs (rows 2m and 2m + 1 of a distribution row:
-        clip(mean + std e) and clip(mean - std e)), into the block the previous population does not occupy; returns it.  No reserved
-        candidate.  ValueError if n_candidates is odd."""
-        return self._es().sample_mirrored(mean_t, std_t, seed, draw_index)
-
-    def utilities(self):
-        """glgym_plan_es_utilities on the last rollout's scores: (u [P, K] f64 -- centred ranks 0.5 .. -0.5 over the admissible
-        candidates, -0.5 for the others, all 0 with fewer than two -- and n_adm [P] i32)."""
-        return self._es().utilities()
-
-    def es_update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
-        """glgym_plan_es_update with H = Ht, in place on mean_t / std_t, over the utilities() of the last rollout's theta.  The Adam
-        moments and the step count are this object's (es() restarts them)."""
-        return self._es().update(mean_t, std_t, lr, lr_std, std_decay, min_std=min_std, max_std=max_std, optimizer=optimizer, betas=betas,
-                                 eps=eps)
 
     def es(self, n_iter: int, lr: float, lr_std: float = 0.1, init_std: float = 0.3, min_std: float = 0.02, max_std: float = 1.0,
            std_decay: float = 1.0, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, mean=None,
@@ -1291,7 +1338,7 @@ class MLPSpec:
         return out
 
 
-class PolicySearch:
+class PolicySearch(_ThetaSearch):
     """Closed-loop rollouts of MLP policies and gradient-free policy search by the cross-entropy method on the device
     (TomatoVecEnv.policy_search).  A candidate is a FEEDBACK LAW: a row of the float32 block theta [Ht, J, 6] holding the D parameters
     of an MLPSpec net.  rollout() forks the environment's greenhouses into B*K children (x S scenarios) and runs observation -> policy
@@ -1310,12 +1357,8 @@ class PolicySearch:
     window keeps the parent's timestep, and the observation's current-row and forecast indices (w_off + timestep - 1 ...) would leave
     the window.  The steps are action steps (u <- clip(u + 0.1 a)); the environment is only read."""
 
-    SCENARIO_KEYS = ("n_scenarios", "n_tail", "noise", "noise_scale", "scenario_seed", "weather_sigma", "weather_phi")
-
     def __init__(self, env, n_candidates: int, horizon: int, spec: MLPSpec, share: str = "greenhouse", gamma: float = 1.0, **scenario_kwargs):
-        unknown = sorted(set(scenario_kwargs) - set(self.SCENARIO_KEYS))
-        if unknown:
-            raise TypeError(f"unexpected arguments {unknown}; the scenario arguments are {self.SCENARIO_KEYS}")
+        self._check_scenario_kwargs(scenario_kwargs)
         if scenario_kwargs.get("weather_sigma") is not None:
             raise ValueError("policy rollouts do not take weather_sigma: a child on a private weather window keeps the parent's timestep, and "
                              "the observation's current-row and forecast indices (w_off + timestep - 1 ...) would leave the window")
@@ -1326,15 +1369,10 @@ class PolicySearch:
         if spec.in_dim != env.obs_dim:
             raise ValueError(f"spec.in_dim = {spec.in_dim}, the environment's observations have {env.obs_dim} columns")
         self.spec, self.share = spec, share
-        self.plan = p = Planner(env, n_candidates, horizon, gamma=gamma, crop="nominal", **scenario_kwargs)
-        self.env, self.torch = env, env.torch
+        # P distributions: every greenhouse's own, or one for all
+        super().__init__(env, n_candidates, horizon, gamma, scenario_kwargs, spec.D, spec.Ht, env.B if share == "greenhouse" else 1)
         torch, dev = env.torch, env.device
-        self.B, self.K, self.H, self.C, self.S = p.B, p.K, p.H, p.C, p.S
-        self.D, self.Ht = spec.D, spec.Ht
-        self.P = self.B if share == "greenhouse" else 1              # distributions: rows of mean / std, calls of the CEM stages
-        self.J = self.P * self.K                                     # rows of theta
         self.row_mode = L.POLICY_ROW_CHILD if share == "greenhouse" else L.POLICY_ROW_CANDIDATE
-        Ht, P, J = self.Ht, self.P, self.J
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
         self._mean_t = torch.as_tensor(spec.mean, device=dev) if spec.mean is not None else None
         self._inv_std_t = torch.as_tensor(spec.inv_std, device=dev) if spec.inv_std is not None else None
@@ -1343,24 +1381,9 @@ class PolicySearch:
         self.obs_t = z(self.C, spec.in_dim)                          # the children's observations: the last step's afterwards
         self._plane_t = z(1, self.C, L.NU)                           # the one action plane of record=False
         self.actions = None                                          # record=True: [H, C, 6], child c = (b*K + k)*S + s
-        self._theta_buf = None
-        self._theta = None                                           # the [Ht, J, 6] block of the last rollout
-        self._blocks = [z(Ht, J, L.NU) for _ in range(2)]            # populations: sampled into the one the previous does not occupy
-        self._cur = self._rolled = self._elites = None
-        self.elite_k_t = torch.full((J,), -1, dtype=torch.int32, device=dev)
-        self.n_elite_t = z(P, dtype=torch.int32)
-        self.mean_t, self.std_t = z(Ht, P, L.NU), z(Ht, P, L.NU)
-        self.best_k_t, self.best_ret_t = z(P, dtype=torch.int32), z(P, dtype=torch.float64)
-        self.best_sequence_t = z(Ht, P, L.NU)
-        self.best_theta_t = z(P, Ht * L.NU)
+        self.best_k_t, self.best_ret_t = z(self.P, dtype=torch.int32), z(self.P, dtype=torch.float64)   # own ones: P may be 1
         if share == "all":
             self.score_t, self.score_failed_t = z(self.K, dtype=torch.float64), z(self.K, dtype=torch.uint8)
-        else:
-            self.score_t, self.score_failed_t = p._score_t, p._score_failed_t
-        self._draw = 0
-        self._es_stages = None
-        self.scenario_returns = getattr(p, "scenario_returns", None)
-        self.scenario_failed = getattr(p, "scenario_failed", None)
 
     # ------------------------------------------------------------------------------------------------
     def encode(self, module_or_arrays):
@@ -1375,33 +1398,16 @@ class PolicySearch:
         scenario_returns / scenario_failed [B, K, S] holding the single runs.  With share="all" score_t / score_failed_t [K] hold the
         policies' scores afterwards.  record=True keeps the actions of every step: actions [H, C, 6] (child c = (b*K + k)*S + s)."""
         torch, e, p = self.torch, self.env, self.plan
-        n = self.Ht * self.J * L.NU
-        if theta_t.numel() != n:
-            raise ValueError(f"theta_t must hold ceil(D / 6) x {self.J} x 6 = {n} values, got {tuple(theta_t.shape)}")
-        if theta_t.dtype == torch.float32 and theta_t.is_cuda and theta_t.device == e.device and theta_t.is_contiguous():
-            self._theta = theta_t.view(self.Ht, self.J, L.NU)
-            self._rolled = next((i for i, b in enumerate(self._blocks) if theta_t is b), None)
-        else:
-            if self._theta_buf is None:
-                self._theta_buf = torch.zeros(self.Ht, self.J, L.NU, dtype=torch.float32, device=e.device)
-            self._theta_buf.copy_(theta_t.reshape(self.Ht, self.J, L.NU))
-            self._theta, self._rolled = self._theta_buf, None
+        self._take(theta_t)
         if record and self.actions is None:
             self.actions = torch.zeros(self.H, self.C, L.NU, dtype=torch.float32, device=e.device)
         planes = self.actions if record else self._plane_t
-        p._actions = p._rolled = None
-        p.fork()
-        a = L.make_plan_args(L.PlanRolloutArgs, self.H, p.gamma, p._step_args(), None, None, p.ret_t.data_ptr(), p.viol_T.data_ptr(),
-                             p.n_steps_t.data_ptr(), p.alive_t.data_ptr(), p.failed_t.data_ptr())
-        if self.S:
-            scen = (self.B, self.K, self.S, 1 if p.noise == "hold" else 0, p.noise_scale, p.scenario_seed & (2 ** 64 - 1), p._scen_draw,
-                    p.scenario_base_t.data_ptr())
-        else:
-            scen = (0, 0, 0, 0, 0.0, 0, 0, None)
-        r = L.make_plan_args(L.PlanRolloutPolicyArgs, 1 if record else 0, a, self._net, self._theta.data_ptr(), p.start_day_t.data_ptr(),
-                             self.obs_t.data_ptr(), planes.data_ptr(), e.Np, self.row_mode, self.J, *scen)
+        p._fork_children()                                           # never with weather windows: __init__ refuses weather_sigma
+        r = L.make_plan_args(L.PlanRolloutPolicyArgs, 1 if record else 0, p._rollout_args(None, None), self._net, self._theta.data_ptr(),
+                             p.start_day_t.data_ptr(), self.obs_t.data_ptr(), planes.data_ptr(), e.Np, self.row_mode, self.J,
+                             *p._scenario_args())
         L.check(e._lib.glgym_plan_rollout_policy(e._h, C.byref(r), e._stream()), "glgym_plan_rollout_policy")
-        out = p._aggregate() if self.S else p._results()
+        out = p._results()
         if self.share == "all":
             torch.mean(out[0], dim=0, out=self.score_t)
             torch.amax(out[4], dim=0, out=self.score_failed_t)
@@ -1415,82 +1421,6 @@ class PolicySearch:
         row = theta_row.to(device=self.env.device, dtype=self.torch.float32).reshape(self.Ht, 1, L.NU)
         return self.rollout(row.expand(self.Ht, self.J, L.NU).contiguous(), record=record)
 
-    def new_scenarios(self):
-        self.plan.new_scenarios()
-
-    # ---- the cross-entropy method over theta: the library's stages with H = Ht, P = B or 1 -----------------------------------
-    def _check_dist(self, mean_t, std_t):
-        torch, n = self.torch, self.Ht * self.P * L.NU
-        for name, t in (("mean_t", mean_t), ("std_t", std_t)):
-            if (t is None or t.dtype != torch.float32 or not t.is_cuda or t.device != self.env.device or not t.is_contiguous()
-                    or t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of ceil(D / 6) x {self.P} x 6 = {n} values on the environment's device")
-
-    def sample(self, mean_t, std_t, seed: int = 0, draw_index: int = 0, carry: int = 0):
-        """glgym_plan_sample with H = Ht, beta = 0: the population theta [Ht, J, 6] from N(mean_t, std_t) [Ht, P, 6], clipped to
-        [-1, 1], into the block the previous population does not occupy; returns it.  Candidate 0 is the clipped mean; with carry >= 1
-        and elites() of the previous sampled population at hand, candidates 1 .. carry are its best rows."""
-        self._check_dist(mean_t, std_t)
-        if int(carry) < 0 or int(seed) < 0 or int(draw_index) < 0:
-            raise ValueError("carry, seed and draw_index must be >= 0")
-        n_elites, src = self._elites or (0, None)
-        carried = int(carry) if src is not None else 0
-        if carried > n_elites:
-            raise ValueError(f"carry = {carry} exceeds the {n_elites} elites of the previous population")
-        e = self.env
-        dst = 0 if self._cur is None else 1 - self._cur
-        a = L.make_plan_args(L.PlanSampleArgs, self.P, self.K, self.Ht, mean_t.data_ptr(), std_t.data_ptr(), 0.0,
-                             int(seed) & (2 ** 64 - 1), int(draw_index) & (2 ** 64 - 1), self.plan.draw_base_t.data_ptr(),
-                             self._blocks[dst].data_ptr(), carried, n_elites if carried else 0,
-                             self._blocks[src].data_ptr() if carried else None, self.elite_k_t.data_ptr() if carried else None,
-                             self.n_elite_t.data_ptr() if carried else None)
-        L.check(e._lib.glgym_plan_sample(e._h, C.byref(a), e._stream()), "glgym_plan_sample")
-        self._cur = dst
-        self._elites = (n_elites, None) if self._elites else None
-        return self._blocks[dst]
-
-    def elites(self, n_elite: int):
-        """glgym_plan_elites on the last rollout's scores: (elite_k [P, n_elite] i32, n_elite [P] i32), as Planner.elites."""
-        E = int(n_elite)
-        if not 1 <= E <= self.K:
-            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
-        e = self.env
-        a = L.make_plan_args(L.PlanElitesArgs, self.P, self.K, E, self.score_t.data_ptr(), self.score_failed_t.data_ptr(),
-                             self.elite_k_t.data_ptr(), self.n_elite_t.data_ptr())
-        L.check(e._lib.glgym_plan_elites(e._h, C.byref(a), e._stream()), "glgym_plan_elites")
-        self._elites = (E, self._rolled if self._rolled == self._cur else None)
-        return self.elite_k_t[:self.P * E].view(self.P, E), self.n_elite_t
-
-    def refit(self, mean_t, std_t, alpha: float, min_std: float):
-        """glgym_plan_refit with H = Ht, in place on mean_t / std_t [Ht, P, 6], over the elites() of the last rollout's theta."""
-        self._check_dist(mean_t, std_t)
-        if not 0.0 <= float(alpha) < 1.0:
-            raise ValueError("alpha must be in [0, 1)")
-        if not 0.0 <= float(min_std) < float("inf"):
-            raise ValueError("min_std must be finite and >= 0")
-        if self._theta is None or self._elites is None:
-            raise ValueError("refit needs a rollout and its elites()")
-        e = self.env
-        a = L.make_plan_args(L.PlanRefitArgs, self.P, self.K, self.Ht, self._elites[0], self._theta.data_ptr(), self.elite_k_t.data_ptr(),
-                             self.n_elite_t.data_ptr(), float(alpha), float(min_std), mean_t.data_ptr(), std_t.data_ptr(),
-                             mean_t.data_ptr(), std_t.data_ptr())
-        L.check(e._lib.glgym_plan_refit(e._h, C.byref(a), e._stream()), "glgym_plan_refit")
-        return mean_t, std_t
-
-    def select(self) -> Dict[str, Any]:
-        """glgym_plan_select with H = Ht on the last rollout's scores: {"best_k" [P] i32 (-1: every candidate failed), "best_return"
-        [P] f64, "best_theta" [P, Ht*6] f32 (component i at [., i]; zeros without an admissible candidate)}.  Device tensors,
-        overwritten by the next call; no allocation."""
-        if self._theta is None:
-            raise ValueError("select needs a rollout")
-        e = self.env
-        a = L.make_plan_args(L.PlanSelectArgs, self.P, self.K, self.Ht, self.score_t.data_ptr(), self.score_failed_t.data_ptr(),
-                             self._theta.data_ptr(), self.best_k_t.data_ptr(), self.best_ret_t.data_ptr(), None,
-                             self.best_sequence_t.data_ptr(), 0.0, None)
-        L.check(e._lib.glgym_plan_select(e._h, C.byref(a), e._stream()), "glgym_plan_select")
-        self.best_theta_t.view(self.P, self.Ht, L.NU).copy_(self.best_sequence_t.permute(1, 0, 2))
-        return {"best_k": self.best_k_t, "best_return": self.best_ret_t, "best_theta": self.best_theta_t}
-
     def cem(self, n_iter: int, n_elite: int, init_std: float = 0.5, min_std: float = 0.02, alpha: float = 0.1, carry: int = 0,
             seed: int = 0, mean=None) -> Dict[str, Any]:
         """Policy search: n_iter x (sample -> rollout -> elites -> refit), then select() on the last population.  mean None: start
@@ -1501,65 +1431,7 @@ class PolicySearch:
         Returns device tensors, overwritten by the next call: best_theta [P, Ht*6], best_return, best_k [P], mean, std [Ht, P, 6],
         elite_k [P, n_elite], n_elite [P].  No host synchronisation and, after the first call, no allocation: a whole cem() can be
         captured in a graph (add n_iter to plan.draw_base_t between replays for fresh noise)."""
-        n_iter, E, carry = int(n_iter), int(n_elite), int(carry)
-        if n_iter < 1:
-            raise ValueError("n_iter must be at least 1")
-        if not 1 <= E <= self.K:
-            raise ValueError(f"n_elite must be in 1 .. n_candidates = {self.K}")
-        if not 0 <= carry <= E:
-            raise ValueError("carry must be in 0 .. n_elite")
-        if not 0.0 <= float(alpha) < 1.0:
-            raise ValueError("alpha must be in [0, 1)")
-        if not 0.0 <= float(min_std) < float("inf") or not 0.0 <= float(init_std) < float("inf") or int(seed) < 0:
-            raise ValueError("min_std and init_std must be finite and >= 0, seed >= 0")
-        if mean is not None:
-            if mean.numel() not in (self.Ht * L.NU, self.Ht * self.P * L.NU):
-                raise ValueError(f"mean must hold ceil(D / 6) x (1 or {self.P}) x 6 values, got {tuple(mean.shape)}")
-            self.mean_t.copy_(mean.reshape(self.Ht, -1, L.NU))
-        else:
-            self.mean_t.zero_()
-        self.std_t.fill_(float(init_std))
-        self._elites = None
-        for _ in range(n_iter):
-            block = self.sample(self.mean_t, self.std_t, seed=seed, draw_index=self._draw, carry=carry)
-            self._draw += 1
-            self.rollout(block)
-            elite_k, n_el = self.elites(E)
-            self.refit(self.mean_t, self.std_t, alpha, min_std)
-        sel = self.select()
-        return {"best_theta": sel["best_theta"], "best_return": sel["best_return"], "best_k": sel["best_k"], "mean": self.mean_t,
-                "std": self.std_t, "elite_k": elite_k, "n_elite": n_el}
-
-    # ---- the evolution strategy over theta (_EsStages) -------------------------------------------------------------------------------
-    def _es(self):
-        if self._es_stages is None:
-            self._es_stages = _EsStages(self, self.P, self.score_t, self.score_failed_t)
-        return self._es_stages
-
-    def _es_start(self):
-        self.mean_t.zero_()
-
-    @property
-    def es_t_base(self):
-        """The device word added to every es_update step count (int64 [1])."""
-        return self._es().t_base_t
-
-    def sample_mirrored(self, mean_t, std_t, seed: int = 0, draw_index: int = 0):
-        """glgym_plan_es_sample with H = Ht: the population theta in mirrored pairs (rows 2m and 2m + 1 of a distribution row:
-        clip(mean + std e) and clip(mean - std e)), into the block the previous population does not occupy; returns it.  No reserved
-        candidate.  ValueError if n_candidates is odd."""
-        return self._es().sample_mirrored(mean_t, std_t, seed, draw_index)
-
-    def utilities(self):
-        """glgym_plan_es_utilities on the last rollout's scores: (u [P, K] f64 -- centred ranks 0.5 .. -0.5 over the admissible
-        candidates, -0.5 for the others, all 0 with fewer than two -- and n_adm [P] i32)."""
-        return self._es().utilities()
-
-    def es_update(self, mean_t, std_t, lr, lr_std=0.0, std_decay=1.0, *, min_std, max_std=1.0, optimizer="adam", betas=(0.9, 0.999), eps=1e-8):
-        """glgym_plan_es_update with H = Ht, in place on mean_t / std_t, over the utilities() of the last rollout's theta.  The Adam
-        moments and the step count are this object's (es() restarts them)."""
-        return self._es().update(mean_t, std_t, lr, lr_std, std_decay, min_std=min_std, max_std=max_std, optimizer=optimizer, betas=betas,
-                                 eps=eps)
+        return self._cem_search(n_iter, n_elite, init_std, min_std, alpha, carry, seed, mean)
 
     def es(self, n_iter: int, lr: float, lr_std: float = 0.1, init_std: float = 0.1, min_std: float = 0.01, max_std: float = 1.0,
            std_decay: float = 1.0, optimizer: str = "adam", betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0, mean=None,

@@ -267,7 +267,7 @@ def test_cem_entry_points_refuse_bad_arguments():
     out = plan.cem(2, E, carry=1)
     lib, h, st = env._lib, env._h, env._stream()
     mean_t, std_t = out["mean_sequence"], out["std_sequence"]
-    cur, oth = plan._cem_blocks[plan._cem_cur], plan._cem_blocks[1 - plan._cem_cur]
+    cur, oth = plan._cem.blocks[plan._cem.cur], plan._cem.blocks[1 - plan._cem.cur]
     watched = [cur, oth, mean_t, std_t, plan.elite_k_t, plan.n_elite_t]
     before = [t.clone() for t in watched]
 
@@ -298,7 +298,7 @@ def test_cem_entry_points_refuse_bad_arguments():
         assert lib.glgym_plan_refit(h, C.byref(a), st) == L.EINVAL, field
     assert unchanged()
     # the planner's checks mirror them and leave everything as it was
-    state = (plan._draw, plan._cem_cur, plan._rolled, plan._elites)
+    state = (plan._draw, plan._cem.cur, plan._cem.rolled, plan._cem.ranked)
     for call in (lambda: plan.elites(K + 1), lambda: plan.elites(0), lambda: plan.sample(mean_t, std_t, beta=1.0),
                  lambda: plan.sample(mean_t, std_t, carry=-1), lambda: plan.sample(mean_t, std_t, carry=E + 1),
                  lambda: plan.sample(mean_t[:1], std_t), lambda: plan.sample(mean_t.double(), std_t),
@@ -308,7 +308,7 @@ def test_cem_entry_points_refuse_bad_arguments():
                  lambda: plan.cem(1, E, mean_t=mean_t[:2]), lambda: plan.shift(-1.0)):
         with pytest.raises(ValueError):
             call()
-    assert unchanged() and state == (plan._draw, plan._cem_cur, plan._rolled, plan._elites)
+    assert unchanged() and state == (plan._draw, plan._cem.cur, plan._cem.rolled, plan._cem.ranked)
     fresh = env.planner(K, H)
     with pytest.raises(ValueError):
         fresh.shift(0.5)

@@ -174,9 +174,9 @@ def stage_costs(torch, rs, say, chol_ok):
     g = torch.Generator().manual_seed(4)
     plan._score_t.copy_(torch.randn(P * K, generator=g, dtype=torch.float64).to(dev))
     plan._score_failed_t.copy_((torch.rand(P * K, generator=g) < 0.02).to(torch.uint8).to(dev))
-    rs._cur = 1
+    rs._cem.cur = 1
     block = rs.sample_cma(seed=1, draw_index=0)
-    rs._theta, rs._rolled = block, rs._cur                    # the stages on their own: no rollout in between
+    rs._theta, rs._cem.rolled = block, rs._cem.cur          # the stages on their own: no rollout in between
     say(f"P = {P} rows x K = {K} candidates, N = {N} constants (Ht = {Ht} planes), E = {E} elites")
     score, failed = plan._score_t.view(P, K), plan._score_failed_t.view(P, K)
     w = torch.as_tensor(hp["w"], device=dev)
@@ -187,7 +187,7 @@ def stage_costs(torch, rs, say, chol_ok):
     qs, qc = (cs * (2 - cs) * mu) ** 0.5, (cc * (2 - cc) * mu) ** 0.5
 
     def hip_sample():
-        rs._cur = 1                                           # always into block 0
+        rs._cem.cur = 1                                       # always into block 0
         rs.sample_cma(seed=1, draw_index=0)
 
     def th_sample():

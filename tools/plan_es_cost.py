@@ -175,7 +175,7 @@ def stage_costs(torch, ps, say, label):
     keep = {}
 
     def hip_sample():
-        ps._cur = 1                                           # always into block 0
+        ps._cem.cur = 1                                       # always into block 0
         ps.sample_mirrored(mean, std, seed=1, draw_index=0)
 
     def th_sample():
