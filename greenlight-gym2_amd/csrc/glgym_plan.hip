@@ -37,6 +37,14 @@
 // for this step and its row of the expanded action plane.  aggregate: one wavefront per candidate, its S <= 256 scenario returns
 // ranked by counting in LDS and summed in rank order by one lane.
 //
+// Constrained ranking (glgym_plan_constrain; scalar logic in gl_constr.hpp, instantiated on the host by tests/constrhost/constrhost.cpp).
+// candidates, more than 8 runs each: one wavefront per candidate, four to a block; the lanes stride over its R runs, the lane sums are
+// added in lane order by reading lane after lane (the lane index is uniform: no LDS, no barrier).  Up to 8 runs (the planner's S <= 8):
+// lane = candidate, the runs added in ascending r, which is the same sum bit for bit; a wavefront reads 64 x S consecutive doubles per
+// violation row.  groups: one block of 256 per ranking group; the smallest admissible feasible return by a strided pass and a
+// tree over LDS (a minimum has no order), then the scores.  Two launches, so that 8 192 candidates of ONE group do not run their
+// 64*S runs each on one workgroup.
+//
 // Weather-forecast scenarios (glgym_plan_weather; scalar logic in gl_wscen.hpp, instantiated on the host by
 // tests/wscenhost/wscenhost.cpp).  window: lane = (greenhouse-scenario ps, j') with j' < 8 fastest; lanes 0..6 run their column's
 // error recurrence over the horizon -- sequential in h by its nature, one Philox block per step --, lane 7 copies the columns the
@@ -64,6 +72,7 @@
 
 #include "gl_cem.hpp"
 #include "gl_cma.hpp"
+#include "gl_constr.hpp"
 #include "gl_es.hpp"
 #include "gl_mlp.hpp"
 #include "gl_plan.hpp"
@@ -599,6 +608,81 @@ __global__ __launch_bounds__(WAVE) void plan_aggregate_kernel(glgym_plan_aggrega
     }
 }
 
+// What the candidates' kernels leave for plan_constrain_groups_kernel: G in score[j] and failed_out | infeasible << 1 in failed_out[j]
+// (score never overlaps ret_cand; failed_out[j] is read, as failed_cand[j], by the thread that writes it).
+__device__ __forceinline__ void constrain_store(const glgym_plan_constrain_args& a, int j, int R, double total, int n_viol, bool nonfinite)
+{
+    const double G = glconstr::mean_excess(total, R);
+    const uint8_t flags = glconstr::flags_of(a.ret_cand[j], a.failed_cand[j], nonfinite, n_viol, a.n_allow);
+    a.score[j] = G;
+    a.failed_out[j] = flags;
+    if (a.excess) a.excess[j] = G;
+    if (a.n_viol) a.n_viol[j] = n_viol;
+    if (a.feasible) a.feasible[j] = (flags & glconstr::FLAG_INFEASIBLE) ? 0 : 1;
+}
+
+// R <= SMALL_R: grid = ceil(J / 256), lane = candidate, its runs added in ascending r (gl_constr.hpp: the defined sum, bit for bit)
+__global__ __launch_bounds__(256) void plan_constrain_few_runs_kernel(glgym_plan_constrain_args a, glconstr::Spec sp, int J)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= J) return;
+    const glconstr::Part part = glconstr::thread_runs(sp, j / a.K, j % a.K, a.viol, (size_t)a.ld, a.n_steps);
+    constrain_store(a, j, sp.O * sp.S, part.sum, part.n_viol, part.nonfinite);
+}
+
+// R > SMALL_R: grid = ceil(J / CONSTR_WAVES) blocks of CONSTR_WAVES wavefronts, one wavefront per candidate j = p*K + k
+constexpr int CONSTR_WAVES = 4;
+__global__ __launch_bounds__(CONSTR_WAVES * WAVE) void plan_constrain_candidates_kernel(glgym_plan_constrain_args a, glconstr::Spec sp, int J)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int j = blockIdx.x * CONSTR_WAVES + threadIdx.x / WAVE;
+    if (j >= J) return;                                 // wave-uniform
+    const int p = j / a.K, k = j - p * a.K;
+    const glconstr::Part part = glconstr::lane_runs(lane, sp, p, k, a.viol, (size_t)a.ld, a.n_steps);
+    double total = 0.0;
+    for (int l = 0; l < WAVE; ++l) total = glconstr::combine(total, __shfl(part.sum, l, WAVE));
+    int n_viol = part.n_viol;
+    for (int m = WAVE / 2; m > 0; m >>= 1) n_viol += __shfl_xor(n_viol, m, WAVE);
+    const bool nonfinite = __any(part.nonfinite);
+    if (lane == 0) constrain_store(a, j, sp.O * sp.S, total, n_viol, nonfinite);
+}
+
+// grid = P, one block of GROUP_THREADS per ranking group: threads stride over its K candidates
+__global__ __launch_bounds__(glconstr::GROUP_THREADS) void plan_constrain_groups_kernel(glgym_plan_constrain_args a)
+{
+    constexpr int T = glconstr::GROUP_THREADS;
+    __shared__ double s_min[T];
+    __shared__ int s_cnt[T];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const size_t first = (size_t)p * a.K;
+    double mn = __builtin_inf();
+    int cnt = 0;
+    for (int k = tid; k < a.K; k += T)
+        if (glconstr::counts_for_floor(a.failed_out[first + k])) {
+            const double r = a.ret_cand[first + k];
+            mn = r < mn ? r : mn;
+            ++cnt;
+        }
+    s_min[tid] = mn;
+    s_cnt[tid] = cnt;
+    __syncthreads();
+    for (int m = T / 2; m > 0; m >>= 1) {               // block-uniform trip count: every thread reaches the barrier
+        if (tid < m) {
+            s_min[tid] = s_min[tid + m] < s_min[tid] ? s_min[tid + m] : s_min[tid];
+            s_cnt[tid] += s_cnt[tid + m];
+        }
+        __syncthreads();
+    }
+    const int n_feasible = s_cnt[0];
+    const double floor_p = glconstr::floor_of(s_min[0], n_feasible);
+    for (int k = tid; k < a.K; k += T) {                // every flag was read before the first barrier; k belongs to this thread alone
+        const uint8_t flags = a.failed_out[first + k];
+        a.score[first + k] = glconstr::score_of(a.mode, a.ret_cand[first + k], a.score[first + k], flags, floor_p, a.rho);
+        a.failed_out[first + k] = flags & glconstr::FLAG_FAILED;
+    }
+    if (tid == 0 && a.n_feasible) a.n_feasible[p] = n_feasible;
+}
+
 // grid = ceil(P*S*8 / 256), lane = ps*8 + j'.  P*S*8 may pass 2^31: the index is taken in 64 bits, the last block's tail does nothing.
 template <class T>
 __global__ __launch_bounds__(256) void plan_weather_kernel(glgym_plan_weather_args a, int nd, double innov, int64_t n_lanes)
@@ -1009,6 +1093,52 @@ int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, voi
     if (!h) { g_err = "glgym_plan_aggregate: null handle"; return GLGYM_EINVAL; }
     DeviceGuard dev_guard(h);
     hipLaunchKernelGGL(plan_aggregate_kernel, dim3((unsigned)a->J), dim3(WAVE), 0, (hipStream_t)stream, *a);
+    HIPCHK(hipGetLastError());
+    return GLGYM_OK;
+}
+
+// constrained ranking (gl_constr.hpp).  As above, the arguments are checked before the handle is looked at.
+int glgym_plan_constrain(glgym_handle h, const glgym_plan_constrain_args* a, void* stream)
+{
+    if (!a) { g_err = "glgym_plan_constrain: null arguments"; return GLGYM_EINVAL; }
+    if (!plan_size_ok("glgym_plan_constrain", a->struct_size, sizeof *a)) return GLGYM_EINVAL;
+    if (a->P < 1 || a->O < 1 || a->K < 1 || a->S < 1 || (int64_t)a->P * a->O > INT32_MAX || (int64_t)a->P * a->O * a->K > INT32_MAX ||
+        (int64_t)a->P * a->O * a->K * a->S > INT32_MAX || (int64_t)a->ld < (int64_t)a->P * a->O * a->K * a->S) {
+        g_err = "glgym_plan_constrain: bad shape (P, O, K, S < 1, P*O*K*S > INT32_MAX, or ld < P*O*K*S)";
+        return GLGYM_EINVAL;
+    }
+    const int64_t R = (int64_t)a->O * a->S, J = (int64_t)a->P * a->K;
+    if ((a->per_step != 0 && a->per_step != 1) || a->n_allow < 0 || a->n_allow > R ||
+        (a->mode != GLGYM_CONSTRAIN_PENALTY && a->mode != GLGYM_CONSTRAIN_FEASIBLE_FIRST)) {
+        g_err = "glgym_plan_constrain: bad arguments (per_step not 0 | 1, n_allow outside 0 .. O*S, or an unknown mode)";
+        return GLGYM_EINVAL;
+    }
+    for (int i = 0; i < 3; ++i)
+        if (!(a->budget[i] >= 0.0) || !(a->weight[i] >= 0.0) || !std::isfinite(a->weight[i])) {
+            g_err = "glgym_plan_constrain: every budget must be >= 0 or +inf (not NaN), every weight finite and >= 0";
+            return GLGYM_EINVAL;
+        }
+    if (!(a->rho >= 0.0) || !std::isfinite(a->rho)) { g_err = "glgym_plan_constrain: rho must be finite and >= 0"; return GLGYM_EINVAL; }
+    if (!a->ret_cand || !a->failed_cand || !a->viol || !a->score || !a->failed_out || (a->per_step && !a->n_steps)) {
+        g_err = "glgym_plan_constrain: null pointer (ret_cand, failed_cand, viol, score, failed_out, or n_steps with per_step)";
+        return GLGYM_EINVAL;
+    }
+    const uintptr_t s0 = (uintptr_t)a->score, r0 = (uintptr_t)a->ret_cand, bytes = (uintptr_t)J * sizeof(double);
+    if (s0 < r0 + bytes && r0 < s0 + bytes) {
+        g_err = "glgym_plan_constrain: score overlaps ret_cand (the stage reads the returns after it has begun to write the scores)";
+        return GLGYM_EINVAL;
+    }
+    if (!h) { g_err = "glgym_plan_constrain: null handle"; return GLGYM_EINVAL; }
+    DeviceGuard dev_guard(h);
+    hipStream_t st = (hipStream_t)stream;
+    glconstr::Spec sp{a->O, a->K, a->S, a->per_step, {a->budget[0], a->budget[1], a->budget[2]}, {a->weight[0], a->weight[1], a->weight[2]}};
+    if (R <= glconstr::SMALL_R)
+        hipLaunchKernelGGL(plan_constrain_few_runs_kernel, dim3((unsigned)((J + 255) / 256)), dim3(256), 0, st, *a, sp, (int)J);
+    else
+        hipLaunchKernelGGL(plan_constrain_candidates_kernel, dim3((unsigned)((J + CONSTR_WAVES - 1) / CONSTR_WAVES)), dim3(CONSTR_WAVES * WAVE), 0,
+                           st, *a, sp, (int)J);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(plan_constrain_groups_kernel, dim3((unsigned)a->P), dim3(glconstr::GROUP_THREADS), 0, st, *a);
     HIPCHK(hipGetLastError());
     return GLGYM_OK;
 }

@@ -254,6 +254,18 @@ class PlanAggregateArgs(C.Structure):
                 ("failed_cand", C.c_void_p), ("viol_cand", C.c_void_p), ("steps_cand", C.c_void_p)]
 
 
+# constrained ranking (include/glgym.h glgym_plan_constrain)
+CONSTRAIN_MODES = {"penalty": 0, "feasible_first": 1}
+
+
+class PlanConstrainArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("P", C.c_int32), ("O", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("ld", C.c_int32),
+                ("per_step", C.c_int32), ("n_allow", C.c_int32), ("mode", C.c_int32), ("budget", C.c_double * 3),
+                ("weight", C.c_double * 3), ("rho", C.c_double), ("ret_cand", C.c_void_p), ("failed_cand", C.c_void_p),
+                ("viol", C.c_void_p), ("n_steps", C.c_void_p), ("score", C.c_void_p), ("failed_out", C.c_void_p),
+                ("feasible", C.c_void_p), ("excess", C.c_void_p), ("n_viol", C.c_void_p), ("n_feasible", C.c_void_p)]
+
+
 # weather-forecast scenarios (include/glgym.h glgym_plan_weather)
 WEATHER_COLUMNS = ("iGlob", "tOut", "vpOut", "co2Out", "wind", "tSky", "tSoOut")
 
@@ -394,6 +406,7 @@ PROTOTYPES = {
     "glgym_plan_scenario": (C.c_int, [C.c_void_p, C.POINTER(PlanScenarioArgs), C.c_void_p]),
     "glgym_plan_rollout_scenarios": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutScenariosArgs), C.c_void_p]),
     "glgym_plan_aggregate": (C.c_int, [C.c_void_p, C.POINTER(PlanAggregateArgs), C.c_void_p]),
+    "glgym_plan_constrain": (C.c_int, [C.c_void_p, C.POINTER(PlanConstrainArgs), C.c_void_p]),
     "glgym_plan_weather": (C.c_int, [C.c_void_p, C.POINTER(PlanWeatherArgs), C.c_void_p]),
     "glgym_rule_based": (C.c_int, [C.c_void_p, C.POINTER(RuleCfg), C.POINTER(RuleArgs), C.c_void_p]),
     "glgym_rule_rows": (C.c_int, [C.c_void_p, C.POINTER(RuleRowsArgs), C.c_void_p]),

@@ -48,6 +48,12 @@ CMA-ES (glgym_plan_cma_sample / _cma_update; _CmaStages below): RuleSearch.cma()
 at most 32 tuned constants -- the separable searches above cannot follow constants that interact -- with sample_cma() and cma_update()
 as the single stages.  PolicySearch and Planner have none: even a linear policy has 144 parameters.
 
+Violation budgets (Constraints below, glgym_plan_constrain; _ConstrainStage): all of the above rank on the return alone.  With
+constraints=Constraints(...) one more scoring stage runs behind every rollout -- after the scenario aggregate, on the per-run CO2,
+temperature and humidity violation sums -- and select, elites, utilities and the CMA update rank ITS scores: feasible candidates (at
+most n_allow runs over budget) by return, then infeasible ones by ascending excess, or return - rho * excess.  The tensors a rollout
+returns stay the raw ones; feasible, excess, n_violating and n_feasible are new views on the planner or search.
+
 How the code is shared.  One stage object per algorithm holds its library calls, argument checks and loop: _CemStages (Planner and both
 searches; it also owns the two population blocks every sampler writes into), _EsStages, _CmaStages.  _ThetaSearch is the base of
 RuleSearch and PolicySearch: the Planner they roll out on, theta in place or staged, the distribution, select, the start of a search
@@ -91,6 +97,98 @@ def _select_temperature(temperature) -> float:
     if 1.0 / t == float("inf"):
         raise ValueError("temperature must have a finite reciprocal (above 2^-1024, about 5.6e-309): 1 / temperature overflows")
     return t
+
+
+class Constraints:
+    """Violation budgets on a rollout's accumulated CO2, temperature and humidity violations, and how the candidates are ranked
+    under them (include/glgym.h glgym_plan_constrain).  co2 / temp / rh: the budget of each violation sum, >= 0, or inf for none;
+    per="step": on the sum divided by the steps the run accumulated ("at most x over the line on average"), per="total": on the sum
+    itself.  A run violates when its weighted excess over the budgets, sum_i weights[i] * max(0, measure_i - budget_i), is positive; a
+    candidate is feasible when at most n_allow of its runs do (its scenarios, and with PolicySearch(share="all") its greenhouses):
+    n_allow = 0 is a hard budget on every sampled future, n_allow = floor(eps * runs) a chance constraint.
+    mode="feasible_first": every feasible candidate outranks every infeasible one; feasible ones are ordered by return, infeasible
+    ones by ascending mean excess (the constrained cross-entropy ordering).  The score of an infeasible candidate is (the smallest
+    feasible return of its greenhouse, or 0 without one) - 1 - excess: at least 1 below every feasible score, which is all an MPPI mean
+    (select(temperature=...)) sees of the order.  mode="penalty": score = return - rho * excess.
+    Hand it to env.planner / env.rule_search / env.policy_search as constraints=..., or attach() it to a Planner built directly."""
+
+    def __init__(self, co2: float = float("inf"), temp: float = float("inf"), rh: float = float("inf"), per: str = "step",
+                 weights=(1.0, 1.0, 1.0), n_allow: int = 0, mode: str = "feasible_first", rho: float = 0.0):
+        inf = float("inf")
+        try:
+            self.budgets = tuple(float(v) for v in (co2, temp, rh))
+        except (TypeError, ValueError):
+            raise ValueError("co2, temp and rh must be numbers: budgets >= 0, or inf for no budget") from None
+        if not all(v >= 0.0 for v in self.budgets):
+            raise ValueError("co2, temp and rh must be >= 0, or inf for no budget (not NaN)")
+        if per not in ("step", "total"):
+            raise ValueError("per must be 'step' or 'total'")
+        try:
+            self.weights = tuple(float(v) for v in weights)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be three numbers (co2, temp, rh)") from None
+        if len(self.weights) != 3 or not all(0.0 <= v < inf for v in self.weights):
+            raise ValueError("weights must be three finite numbers >= 0 (co2, temp, rh)")
+        if isinstance(n_allow, bool) or int(n_allow) != n_allow or int(n_allow) < 0:
+            raise ValueError("n_allow must be an integer >= 0")
+        if mode not in L.CONSTRAIN_MODES:
+            raise ValueError(f"mode must be one of {sorted(L.CONSTRAIN_MODES)}")
+        if not 0.0 <= float(rho) < inf:
+            raise ValueError("rho must be finite and >= 0")
+        self.per, self.n_allow, self.mode, self.rho = per, int(n_allow), mode, float(rho)
+
+    def attach(self, planner: "Planner") -> "Planner":
+        """Rank the candidates of `planner` (a Planner without constraints yet) under these constraints from its next rollout on;
+        returns it.  ValueError if n_allow exceeds the planner's runs per candidate."""
+        planner._constrain(self)
+        return planner
+
+
+class _ConstrainStage:
+    """glgym_plan_constrain behind a rollout, in one place for Planner (P = B groups, O = 1) and PolicySearch(share="all") (P = 1,
+    O = B): the buffers, allocated once here -- score_con_t f64, failed_con_t / feasible_t u8, excess_t f64, n_viol_t i32 [P*K],
+    n_feasible_t i32 and best_feasible_t u8 [P] -- the argument block over them and over the owner's returns (ret_t / failed_t [P*K]),
+    per-run violations (viol_T [3, ld]) and step counts, and the two calls: run() after every rollout, best() after every select."""
+
+    def __init__(self, env, constraints, P, O, K, S, ld, ret_t, failed_t, viol_T, n_steps_t):
+        if not isinstance(constraints, Constraints):
+            raise TypeError("constraints must be a planner.Constraints")
+        c, torch, dev = constraints, env.torch, env.device
+        if c.n_allow > O * S:
+            raise ValueError(f"n_allow = {c.n_allow} exceeds the {O * S} runs of a candidate")
+        self.env, self.torch, self.constraints, self.P, self.K = env, torch, c, int(P), int(K)
+        J = self.P * self.K
+        z = lambda n, dtype: torch.zeros(n, dtype=dtype, device=dev)  # noqa: E731
+        self.score_con_t, self.excess_t = z(J, torch.float64), z(J, torch.float64)
+        self.failed_con_t, self.feasible_t = z(J, torch.uint8), z(J, torch.uint8)
+        self.n_viol_t, self.n_feasible_t = z(J, torch.int32), z(self.P, torch.int32)
+        self.best_feasible_t = z(self.P, torch.uint8)
+        self._idx_t, self._none_t = z(self.P, torch.int64), z(self.P, torch.bool)
+        self._inputs = (ret_t, failed_t, viol_T, n_steps_t)          # kept alive with the pointers below
+        self._args = L.make_plan_args(L.PlanConstrainArgs, self.P, int(O), self.K, int(S), int(ld), 1 if c.per == "step" else 0, c.n_allow,
+                                      L.CONSTRAIN_MODES[c.mode], (C.c_double * 3)(*c.budgets), (C.c_double * 3)(*c.weights), c.rho,
+                                      ret_t.data_ptr(), failed_t.data_ptr(), viol_T.data_ptr(), n_steps_t.data_ptr(),
+                                      self.score_con_t.data_ptr(), self.failed_con_t.data_ptr(), self.feasible_t.data_ptr(),
+                                      self.excess_t.data_ptr(), self.n_viol_t.data_ptr(), self.n_feasible_t.data_ptr())
+
+    def views(self, rows):
+        """(feasible, excess, n_violating) as [rows, K] views, and n_feasible [P]."""
+        return (self.feasible_t.view(rows, self.K), self.excess_t.view(rows, self.K), self.n_viol_t.view(rows, self.K), self.n_feasible_t)
+
+    def run(self):
+        e = self.env
+        L.check(e._lib.glgym_plan_constrain(e._h, C.byref(self._args), e._stream()), "glgym_plan_constrain")
+
+    def best(self, best_k_t, out):
+        """best_feasible [P] u8 = feasible[p, best_k[p]], 0 where best_k = -1, and n_feasible into the dict `out`; no allocation."""
+        torch = self.torch
+        self._idx_t.copy_(best_k_t)
+        torch.lt(self._idx_t, 0, out=self._none_t)
+        self._idx_t.clamp_(min=0)
+        torch.gather(self.feasible_t.view(self.P, self.K), 1, self._idx_t.view(self.P, 1), out=self.best_feasible_t.view(self.P, 1))
+        self.best_feasible_t.masked_fill_(self._none_t, 0)
+        out["best_feasible"], out["n_feasible"] = self.best_feasible_t, self.n_feasible_t
+        return out
 
 
 class Planner:
@@ -182,6 +280,22 @@ class Planner:
             self.weather_window_t = z(self.B * self.S * self.H, env.nd)       # row (b*S + s)*H + h: scenario s of greenhouse b at horizon step h
             self.weather_window = self.weather_window_t.view(self.B, self.S, self.H, env.nd)
         self.x, self.u = self.x_T[:, :self.C].t(), self.u_T[:, :self.C].t()
+        self.constraints = self._con = None                          # Constraints.attach / env.planner(constraints=...): _constrain
+
+    def _constrain(self, constraints):
+        """Put glgym_plan_constrain behind every rollout (_ConstrainStage: its buffers are allocated here, once) and have select, elites
+        and the searches rank its scores.  The runs of a candidate are its S scenarios (one run without scenarios): the stage reads the
+        per-run viol_T / n_steps_t, not the scenario means.  Afterwards, per rollout: feasible [B, K] u8, excess [B, K] f64,
+        n_violating [B, K] i32, n_feasible [B] i32 (read-only views), score_con_t / failed_con_t [B*K] what is ranked."""
+        if self._con is not None:
+            raise ValueError("this planner already has constraints")
+        self._con = con = _ConstrainStage(self.env, constraints, self.B, 1, self.K, self.S or 1, self.ld, self._score_t, self._score_failed_t,
+                                          self.viol_T, self.n_steps_t)
+        self.constraints = constraints
+        self.score_con_t, self.failed_con_t, self.feasible_t, self.excess_t = con.score_con_t, con.failed_con_t, con.feasible_t, con.excess_t
+        self.n_viol_t, self.n_feasible_t = con.n_viol_t, con.n_feasible_t
+        self.feasible, self.excess, self.n_violating, self.n_feasible = con.views(self.B)
+        self._score_t, self._score_failed_t = con.score_con_t, con.failed_con_t
 
     def set_layout(self, layout: str):
         """Kernel layout of float32 env-steps (TomatoVecEnv.set_layout; handle state, shared with the environment).  With "auto" the
@@ -293,9 +407,12 @@ class Planner:
 
     def _results(self):
         """The five tensors a rollout returns: views of the children's accumulators, or with scenarios glgym_plan_aggregate over the S
-        runs of every candidate."""
+        runs of every candidate.  With constraints glgym_plan_constrain comes last: the five tensors stay the raw ones, the scores that
+        select and elites rank go to score_con_t / failed_con_t."""
         e, B, K = self.env, self.B, self.K
         if not self.S:
+            if self._con is not None:
+                self._con.run()
             return (self.ret_t.view(B, K), self.alive_t.view(B, K), self.n_steps_t.view(B, K), self.viol_T[:, :self.C].view(3, B, K),
                     self.failed_t.view(B, K))
         g = L.make_plan_args(L.PlanAggregateArgs, self.J, self.S, self.n_tail, self.ld, self.ld_cand, self.ret_t.data_ptr(),
@@ -303,6 +420,8 @@ class Planner:
                              self.failed_cand_t.data_ptr(), self.viol_cand_T.data_ptr(), self.steps_cand_t.data_ptr())
         L.check(e._lib.glgym_plan_aggregate(e._h, C.byref(g), e._stream()), "glgym_plan_aggregate")
         self.torch.amin(self.alive_t.view(self.J, self.S), dim=1, out=self.alive_cand_t)
+        if self._con is not None:
+            self._con.run()
         return (self.ret_cand_t.view(B, K), self.alive_cand_t.view(B, K), self.steps_cand_t.view(B, K),
                 self.viol_cand_T[:, :self.J].view(3, B, K), self.failed_cand_t.view(B, K))
 
@@ -318,7 +437,9 @@ class Planner:
         non-finite), "best_return" [B] f64 (NaN then), "best_action" [B, 6] f32 = the best candidate's first action (zeros then)}, with
         sequence=True also "best_sequence" [H, B, 6], with temperature > 0 also "mean_sequence" [H, B, 6]: the MPPI mean with weights
         exp((return - max) / temperature) over the admissible candidates.  After a rollout of raw controls only best_k / best_return
-        are available.  Device tensors, overwritten by the next call."""
+        are available.  Device tensors, overwritten by the next call.
+        With constraints the candidates are ranked by their constrained scores, best_return is the best SCORE -- the candidate's
+        return whenever best_feasible = 1 -- and the dict gains "best_feasible" [B] u8 (0 when best_k = -1) and "n_feasible" [B] i32."""
         e = self.env
         has_a = self._actions is not None
         if not has_a and (sequence or temperature is not None):
@@ -338,6 +459,8 @@ class Planner:
             out["best_sequence"] = self.best_sequence_t
         if temperature is not None:
             out["mean_sequence"] = self.mean_sequence_t
+        if self._con is not None:
+            self._con.best(self.best_k_t, out)
         return out
 
     # ---- the cross-entropy method ------------------------------------------------------------------------------------------
@@ -394,9 +517,12 @@ class Planner:
             self.cem_std_t.copy_(std_t.view(self.H, self.B, L.NU))
         elite_k, n_el = st.run(self.cem_mean_t, self.cem_std_t, n_iter, E, alpha, min_std, beta, carry, seed)
         sel = self.select(sequence=True)
-        return {"mean_sequence": self.cem_mean_t, "std_sequence": self.cem_std_t, "best_sequence": sel["best_sequence"],
-                "best_action": sel["best_action"], "best_return": sel["best_return"], "best_k": sel["best_k"], "elite_k": elite_k,
-                "n_elite": n_el}
+        out = {"mean_sequence": self.cem_mean_t, "std_sequence": self.cem_std_t, "best_sequence": sel["best_sequence"],
+               "best_action": sel["best_action"], "best_return": sel["best_return"], "best_k": sel["best_k"], "elite_k": elite_k,
+               "n_elite": n_el}
+        if self._con is not None:                                    # with constraints: select()'s best_feasible and n_feasible as well
+            out.update(best_feasible=sel["best_feasible"], n_feasible=sel["n_feasible"])
+        return out
 
     def shift(self, fill_std: float):
         """Receding-horizon warm start on cem()'s distribution: mean[h] <- mean[h+1], last row 0; std[h] <- std[h+1], last row
@@ -860,8 +986,11 @@ class _CmaStages:
             s.elites(E)
             self.update(E, hp, min_sigma, max_sigma)
         sel = s.select()
-        return {"best_theta": sel["best_theta"], "best_params": sel["best_params"], "best_return": sel["best_return"], "best_k": sel["best_k"],
-                "mean": s.mean_t, "sigma": self.sigma_t, "cov": self.cov_t, "status": self.status_t}
+        out = {"best_theta": sel["best_theta"], "best_params": sel["best_params"], "best_return": sel["best_return"], "best_k": sel["best_k"],
+               "mean": s.mean_t, "sigma": self.sigma_t, "cov": self.cov_t, "status": self.status_t}
+        if "best_feasible" in sel:                                   # a search with constraints
+            out.update(best_feasible=sel["best_feasible"], n_feasible=sel["n_feasible"])
+        return out
 
 
 class _ThetaSearch:
@@ -885,8 +1014,12 @@ class _ThetaSearch:
         if unknown:
             raise TypeError(f"unexpected arguments {unknown}; the scenario arguments are {cls.SCENARIO_KEYS}")
 
-    def __init__(self, env, n_candidates, horizon, gamma, scenario_kwargs, D, Ht, P):
+    def __init__(self, env, n_candidates, horizon, gamma, scenario_kwargs, D, Ht, P, constraints=None):
         self.plan = p = Planner(env, n_candidates, horizon, gamma=gamma, crop="nominal", **scenario_kwargs)
+        self.constraints, self._con = constraints, None
+        if constraints is not None:                                  # a group per greenhouse: the plan's own stage, behind its _results
+            p._constrain(constraints)
+            self._con = p._con
         self.env, self.torch = env, env.torch
         torch, dev = env.torch, env.device
         self.B, self.K, self.H, self.C, self.S = p.B, p.K, p.H, p.C, p.S
@@ -907,6 +1040,14 @@ class _ThetaSearch:
         self._es_stages = None
         self.scenario_returns = getattr(p, "scenario_returns", None)
         self.scenario_failed = getattr(p, "scenario_failed", None)
+        if self._con is not None:
+            self.feasible, self.excess, self.n_violating, self.n_feasible = self._con.views(self.B)
+
+    @staticmethod
+    def _pop_constraints(scenario_kwargs):
+        """constraints=... travels beside the scenario keywords, not among them (SCENARIO_KEYS): -> (it or None, the others)."""
+        kw = dict(scenario_kwargs)
+        return kw.pop("constraints", None), kw
 
     def _cem_alloc(self):
         """Nothing left to do: __init__ has allocated."""
@@ -963,7 +1104,8 @@ class _ThetaSearch:
     def select(self) -> Dict[str, Any]:
         """glgym_plan_select with H = Ht on the last rollout's scores: {"best_k" [P] i32 (-1: every candidate failed), "best_return"
         [P] f64, "best_theta" [P, Ht*6] f32 (component i at [., i]; zeros without an admissible candidate)}.  Device tensors,
-        overwritten by the next call; no allocation."""
+        overwritten by the next call; no allocation.  With constraints best_return is the best constrained SCORE -- the return
+        whenever best_feasible = 1 -- and the dict gains "best_feasible" [P] u8 (0 when best_k = -1) and "n_feasible" [P] i32."""
         if self._theta is None:
             raise ValueError("select needs a rollout")
         e = self.env
@@ -972,7 +1114,10 @@ class _ThetaSearch:
                              self.best_sequence_t.data_ptr(), 0.0, None)
         L.check(e._lib.glgym_plan_select(e._h, C.byref(a), e._stream()), "glgym_plan_select")
         self.best_theta_t.view(self.P, self.Ht, L.NU).copy_(self.best_sequence_t.permute(1, 0, 2))
-        return {"best_k": self.best_k_t, "best_return": self.best_ret_t, "best_theta": self.best_theta_t}
+        out = {"best_k": self.best_k_t, "best_return": self.best_ret_t, "best_theta": self.best_theta_t}
+        if self._con is not None:                                    # as Planner.select: best_return is the best score
+            self._con.best(self.best_k_t, out)
+        return out
 
     def _cem_search(self, n_iter, n_elite, init_std, min_std, alpha, carry, seed, mean):
         """cem() of the subclasses: what select() returns, and mean, std, elite_k, n_elite."""
@@ -1031,11 +1176,12 @@ class RuleSearch(_ThetaSearch):
     raw-control steps: under the default verify mode "auto" they run verified (TomatoVecEnv.set_verify).  The environment is only read."""
 
     def __init__(self, env, n_candidates: int, horizon: int, tune, base=None, gamma: float = 1.0, **scenario_kwargs):
+        constraints, scenario_kwargs = self._pop_constraints(scenario_kwargs)
         self._check_scenario_kwargs(scenario_kwargs)
         check_rule_dt(env.dt)
         self.params = RuleParams(tune, base)
         self.base = self.params.base
-        super().__init__(env, n_candidates, horizon, gamma, scenario_kwargs, self.params.D, self.params.Ht, env.B)
+        super().__init__(env, n_candidates, horizon, gamma, scenario_kwargs, self.params.D, self.params.Ht, env.B, constraints)
         torch, dev, B = env.torch, env.device, self.B
         self.names = self.params.names
         self._space = self.params.struct()
@@ -1358,6 +1504,7 @@ class PolicySearch(_ThetaSearch):
     the window.  The steps are action steps (u <- clip(u + 0.1 a)); the environment is only read."""
 
     def __init__(self, env, n_candidates: int, horizon: int, spec: MLPSpec, share: str = "greenhouse", gamma: float = 1.0, **scenario_kwargs):
+        constraints, scenario_kwargs = self._pop_constraints(scenario_kwargs)
         self._check_scenario_kwargs(scenario_kwargs)
         if scenario_kwargs.get("weather_sigma") is not None:
             raise ValueError("policy rollouts do not take weather_sigma: a child on a private weather window keeps the parent's timestep, and "
@@ -1370,7 +1517,8 @@ class PolicySearch(_ThetaSearch):
             raise ValueError(f"spec.in_dim = {spec.in_dim}, the environment's observations have {env.obs_dim} columns")
         self.spec, self.share = spec, share
         # P distributions: every greenhouse's own, or one for all
-        super().__init__(env, n_candidates, horizon, gamma, scenario_kwargs, spec.D, spec.Ht, env.B if share == "greenhouse" else 1)
+        super().__init__(env, n_candidates, horizon, gamma, scenario_kwargs, spec.D, spec.Ht, env.B if share == "greenhouse" else 1,
+                         constraints if share == "greenhouse" else None)
         torch, dev = env.torch, env.device
         self.row_mode = L.POLICY_ROW_CHILD if share == "greenhouse" else L.POLICY_ROW_CANDIDATE
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)  # noqa: E731
@@ -1384,6 +1532,13 @@ class PolicySearch(_ThetaSearch):
         self.best_k_t, self.best_ret_t = z(self.P, dtype=torch.int32), z(self.P, dtype=torch.float64)   # own ones: P may be 1
         if share == "all":
             self.score_t, self.score_failed_t = z(self.K, dtype=torch.float64), z(self.K, dtype=torch.uint8)
+            self._mean_ret_t, self._any_failed_t = self.score_t, self.score_failed_t     # what rollout()'s two reductions write
+            if constraints is not None:                              # one group of K policies, each run on the B greenhouses (x S)
+                p, self.constraints = self.plan, constraints
+                self._con = con = _ConstrainStage(env, constraints, 1, self.B, self.K, self.S or 1, p.ld, self._mean_ret_t, self._any_failed_t,
+                                                  p.viol_T, p.n_steps_t)
+                self.score_t, self.score_failed_t = con.score_con_t, con.failed_con_t
+                self.feasible, self.excess, self.n_violating, self.n_feasible = con.views(1)
 
     # ------------------------------------------------------------------------------------------------
     def encode(self, module_or_arrays):
@@ -1409,8 +1564,10 @@ class PolicySearch(_ThetaSearch):
         L.check(e._lib.glgym_plan_rollout_policy(e._h, C.byref(r), e._stream()), "glgym_plan_rollout_policy")
         out = p._results()
         if self.share == "all":
-            torch.mean(out[0], dim=0, out=self.score_t)
-            torch.amax(out[4], dim=0, out=self.score_failed_t)
+            torch.mean(out[0], dim=0, out=self._mean_ret_t)
+            torch.amax(out[4], dim=0, out=self._any_failed_t)
+            if self._con is not None:
+                self._con.run()
         return out
 
     def evaluate(self, theta_row, record: bool = False):

@@ -454,16 +454,22 @@ class TomatoVecEnv:
         parameters.  Robust planning, keyword-only: n_scenarios=S simulates every candidate under S sampled futures of the crop block
         (noise_scale, default this environment's uncertainty_scale; noise="step" | "hold") and scores it by the mean of its n_tail
         worst returns (default S: the mean); scenario_seed keys the futures.  weather_sigma (7 floats or a dict by column name) with
-        weather_phi gives every scenario its own wrong weather forecast as well (planner.py)."""
+        weather_phi gives every scenario its own wrong weather forecast as well (planner.py).  constraints=planner.Constraints(...)
+        ranks the candidates under violation budgets (feasible first, or with a penalty) instead of by return alone."""
         from .planner import Planner
-        return Planner(self, n_candidates, horizon, gamma=gamma, crop=crop, **scenarios)
+        constraints = scenarios.pop("constraints", None)
+        plan = Planner(self, n_candidates, horizon, gamma=gamma, crop=crop, **scenarios)
+        if constraints is not None:
+            plan._constrain(constraints)
+        return plan
 
     def rule_search(self, n_candidates: int, horizon: int, tune, base=None, gamma: float = 1.0, **scenario_kwargs):
         """A gl_gym_amd.planner.RuleSearch for this environment: closed-loop rollouts of n_candidates rule-based controllers per
         environment over `horizon` env-steps on forked copies, and the tuning of the constants named in tune = {name: (lo, hi), ...}
         by the cross-entropy method; the other constants come from `base` (default RuleBasedController()).  The scenario arguments of
         planner() (n_scenarios, n_tail, noise, noise_scale, scenario_seed, weather_sigma, weather_phi) make the tuning robust to crop
-        noise and forecast error.  Needs dt to be a multiple of 450 s (planner.check_rule_dt)."""
+        noise and forecast error; constraints=planner.Constraints(...) tunes under violation budgets.  Needs dt to be a multiple of
+        450 s (planner.check_rule_dt)."""
         from .planner import RuleSearch
         return RuleSearch(self, n_candidates, horizon, tune, base=base, gamma=gamma, **scenario_kwargs)
 
@@ -471,7 +477,9 @@ class TomatoVecEnv:
         """A gl_gym_amd.planner.PolicySearch for this environment: closed-loop rollouts of n_candidates MLP policies (spec: a
         planner.MLPSpec with in_dim = obs_dim) over `horizon` env-steps on forked copies, and gradient-free policy search by the
         cross-entropy method.  share="greenhouse": candidates per greenhouse; "all": every policy runs on all greenhouses and is scored
-        by its mean return.  The scenario arguments of planner() except weather_sigma apply (evaluation and search under crop noise)."""
+        by its mean return.  The scenario arguments of planner() except weather_sigma apply (evaluation and search under crop noise);
+        constraints=planner.Constraints(...) searches under violation budgets (with share="all" a policy's runs are its greenhouses
+        times its scenarios)."""
         from .planner import PolicySearch
         return PolicySearch(self, n_candidates, horizon, spec, share=share, gamma=gamma, **scenario_kwargs)
 

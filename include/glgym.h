@@ -169,7 +169,7 @@ typedef struct {
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
  * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build; glgym_plan_cma_sample,
- * glgym_plan_cma_update */
+ * glgym_plan_cma_update; glgym_plan_constrain */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -843,6 +843,61 @@ typedef struct {
 int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void* stream);
 int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream);
 int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream);
+
+/* ---- violation budgets and chance constraints in candidate ranking (csrc/gl_constr.hpp, csrc/glgym_plan.hip) -------------------
+ * A second scoring stage behind the rollout (and behind glgym_plan_aggregate, if there are scenarios): it turns the candidates'
+ * returns and the accumulated violations of their runs (viol rows 0, 1, 2: CO2, temperature, humidity) into the scores that
+ * glgym_plan_select / _elites / _es_utilities then rank.  Same conventions as above: struct_size first, GLGYM_EINVAL with a
+ * glgym_last_error text before anything is launched, asynchronous on `stream`, no allocation, no host synchronisation (capturable),
+ * plain vector stores, no atomics.  Independent of the handle's dtype.  Opt-in: no other entry point changes.
+ *
+ * Indexing.  P ranking groups, K candidates per group, R = O*S runs per candidate: candidate j = p*K + k owns the children
+ * c = ((p*O + o)*K + k)*S + s, its run r = o*S + s (o-major, then s).  O = 1 is the layout of glgym_plan_rollout_scenarios (S = 1:
+ * no scenarios); P = 1, O = B ranks K policies that each ran on all B greenhouses, at stride K*S.
+ *
+ * Everything is double; products, quotients and sums are rounded separately (no contraction).
+ * Per run r, child c:  d = per_step ? (double)max(n_steps[c], 1) : 1.0;  for i = 0, 1, 2:  e_i = max(0.0, viol[i][c] / d -
+ * budget[i]), except that e_i = +0.0 when budget[i] = +inf (the constraint is off, whatever viol holds: inf - inf never appears) and
+ * when viol[i][c] is not finite under an active budget -- which marks the candidate failed instead;
+ * g_r = ((0.0 + weight[0]*e_0) + weight[1]*e_1) + weight[2]*e_2.  The run violates when g_r > 0.
+ * Per candidate j:  n_viol = the number of violating runs;  feasible = n_viol <= n_allow (n_allow = 0: every run within budget;
+ * n_allow = floor(eps*R): a chance constraint over the sampled futures);  excess G = (sum of the g_r) / (double)R, where the sum has
+ * a fixed, parallel order: lane l of 64 adds the runs with r = l, l + 64, l + 128, ... in ascending r, starting from 0.0 (a lane
+ * without a run keeps 0.0), and the 64 lane sums are then added in lane order 0, 1, ..., 63, starting from 0.0;
+ * failed_out = failed_cand | (a non-finite viol under an active budget) | (ret_cand is not finite), as 0 | 1.
+ * Score.  mode = GLGYM_CONSTRAIN_PENALTY: score = ret_cand - rho*G.  mode = GLGYM_CONSTRAIN_FEASIBLE_FIRST (the constrained
+ * cross-entropy ordering): call a candidate admissible when its failed_out is 0; floor_p = (the smallest ret_cand over group p's
+ * admissible feasible candidates, or 0.0 when it has none) - 1.0; a feasible candidate scores ret_cand, an infeasible one
+ * floor_p - G.  Every feasible candidate thus outranks every infeasible one of its group, feasible ones are ordered by return,
+ * infeasible ones by ascending excess, and the gap between the two classes is at least 1 (up to the rounding of floor_p): argmax,
+ * counting ranks, centred ranks and CMA weights produce the lexicographic order without knowing of it; only an exponentially
+ * weighted mean sees the magnitudes.  In either mode a candidate with failed_out = 1 scores NaN.
+ * n_feasible[p] = the number of admissible feasible candidates of group p. */
+typedef enum { GLGYM_CONSTRAIN_PENALTY = 0, GLGYM_CONSTRAIN_FEASIBLE_FIRST = 1 } glgym_constrain_mode;
+
+typedef struct {
+    int32_t struct_size;
+    int32_t P, O, K, S;          /* all >= 1; P*O*K*S <= INT32_MAX */
+    int32_t ld;                  /* leading dimension of viol (>= P*O*K*S) */
+    int32_t per_step;            /* 0 | 1: budgets per accumulated step, or on the run's totals */
+    int32_t n_allow;             /* 0 .. R */
+    int32_t mode;                /* glgym_constrain_mode */
+    double budget[3];            /* >= 0, or +inf: off; NaN or a negative value is refused */
+    double weight[3];            /* finite, >= 0 */
+    double rho;                  /* finite, >= 0; read in penalty mode only */
+    const double* ret_cand;      /* [P*K] */
+    const uint8_t* failed_cand;  /* [P*K] */
+    const double* viol;          /* SoA [3][ld] */
+    const int32_t* n_steps;      /* [P*O*K*S]; required with per_step */
+    double* score;               /* [P*K] out; must not overlap ret_cand */
+    uint8_t* failed_out;         /* [P*K] out; may be failed_cand */
+    uint8_t* feasible;           /* [P*K] out, or NULL */
+    double* excess;              /* [P*K] out = G, or NULL */
+    int32_t* n_viol;             /* [P*K] out, or NULL */
+    int32_t* n_feasible;         /* [P] out, or NULL */
+} glgym_plan_constrain_args;
+
+int glgym_plan_constrain(glgym_handle h, const glgym_plan_constrain_args* a, void* stream);
 
 /* ---- weather-forecast uncertainty in scenario rollouts (csrc/gl_wscen.hpp, csrc/glgym_plan.hip) ------------------------------
  * A rollout's children step on the true future rows of the weather table: perfect foresight.  glgym_plan_weather gives scenario s of
