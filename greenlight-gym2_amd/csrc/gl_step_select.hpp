@@ -88,10 +88,17 @@ inline bool takes_quad(const StepSelectIn& s)
     return s.f64 || (!s.pipe && !s.crop && (s.layout == 2 || (s.layout == 0 && s.B <= 16 * s.n_simd)));
 }
 
+// the first rule on its own -- the error's text, or null --, for glgym.hip's step_refusal, which decides before anything is launched
+inline const char* step_pipe_error(bool pipe, bool crop, int scheme)
+{
+    return pipe && (crop || scheme != RK4)
+               ? "glgym_step: GLGYM_ODE_PIPE supports neither per-env crop parameters nor schemes other than GLGYM_SCHEME_RK4"
+               : nullptr;
+}
+
 inline StepChoice select_step(const StepSelectIn& s)
 {
-    if (s.pipe && (s.crop || s.scheme != RK4))
-        return {"glgym_step: GLGYM_ODE_PIPE supports neither per-env crop parameters nor schemes other than GLGYM_SCHEME_RK4", {}, 0, 0};
+    if (const char* error = step_pipe_error(s.pipe, s.crop, s.scheme)) return {error, {}, 0, 0};
     const auto blocks = [&](int lanes_per_env) { return (unsigned)(((unsigned long long)lanes_per_env * s.B + WAVE - 1) / WAVE); };
     const bool pair = s.verify && s.ladder_parallel && !s.crop && 8ull * s.B <= (unsigned long long)WAVE * s.n_simd;
     if (takes_quad(s))

@@ -1,6 +1,6 @@
 // glgym.hip -- the integrating gfx950 kernels and the part of the C ABI (include/glgym.h) that launches them.  ONLY what instantiates an
 // integrating kernel lives here: every other kernel and its entry points have a translation unit of their own (glgym_env.hip,
-// glgym_ancillary.hip, glgym_plan.hip, glgym_rng.hip, glgym_bdf.hip), so that an edit over there neither recompiles nor can change
+// glgym_ancillary.hip, glgym_plan.hip, glgym_search.hip, glgym_rng.hip, glgym_bdf.hip), so that an edit over there neither recompiles nor can change
 // the kernels below.  A change to this file owes their instruction-for-instruction comparison (tools/isa_compare.py).
 //
 // Kernels (one lane = one environment; a 64-lane wavefront = one workgroup = 64 environments):
@@ -1420,10 +1420,6 @@ static int launch_step(glgym_handle h, const glgym_step_args* a, const ModelCons
 template <class T>
 static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const RewardConstBase<T>& rw, hipStream_t st)
 {
-    if (h->variant == GLGYM_ODE_PIPE) {
-        g_err = "glgym_step: GLGYM_INTEGRATOR_BDF does not support GLGYM_ODE_PIPE";
-        return GLGYM_EINVAL;
-    }
     glbdf::BdfEnvArgs<T> k;
     k.ld = a->ld;
     k.x = (T*)a->x; k.u = (T*)a->u; k.action = a->action; k.control = (const T*)a->control;
@@ -1439,30 +1435,35 @@ static int launch_step_bdf(glgym_handle h, const glgym_step_args* a, const Rewar
     return GLGYM_OK;
 }
 
+// What glgym_step refuses, all of it, decided on the host before anything is launched: GLGYM_OK, or GLGYM_EINVAL with the text in g_err.
+// step_impl begins with it; the rollouts of glgym_plan.hip call it on the step block they are about to use, before their first prologue
+// (glgym_internal.h).
+int step_refusal(glgym_handle h, const glgym_step_args* a)
+{
+    if (!h || !a) return refuse("glgym_step: null handle / arguments");
+    if (a->struct_size != (int32_t)sizeof(glgym_step_args))       // checked before any pointer member is read
+        return refuse("glgym_step: glgym_step_args.struct_size is " + std::to_string(a->struct_size) + ", this library expects " +
+                      std::to_string(sizeof(glgym_step_args)) + " (ABI " + std::to_string(GLGYM_ABI_VERSION) + "): rebuild against include/glgym.h");
+    if (a->B < 1 || a->ld < a->B || !a->x || !a->u || !a->weather || !a->w_off || !a->timestep ||
+        !a->reward || !a->done || (!a->action) == (!a->control) || a->weather_rows < 1)
+        return refuse("glgym_step: bad arguments (exactly one of action/control, ld >= B, non-null state/outputs)");
+    const bool pipe = h->variant == GLGYM_ODE_PIPE;
+    if (h->step_integrator == GLGYM_INTEGRATOR_BDF)
+        return pipe ? refuse("glgym_step: GLGYM_INTEGRATOR_BDF does not support GLGYM_ODE_PIPE") : (int)GLGYM_OK;
+    if (h->integrator != GLGYM_INTEGRATOR_EXPLICIT)
+        return refuse("glgym_step: GLGYM_INTEGRATOR_BDF is available to glgym_evalF only; set GLGYM_INTEGRATOR_EXPLICIT for env-steps");
+    const char* why = glsel::step_pipe_error(pipe, a->crop_p != nullptr, h->scheme);
+    return why ? refuse(why) : (int)GLGYM_OK;
+}
+
 static int step_impl(glgym_handle h, const glgym_step_args* a, void* stream, const glgym_obs_args* oa, int* fused,
                      const glgym_reset_args* ra = nullptr)
 {
-    if (!h || !a) { g_err = "glgym_step: null handle / arguments"; return GLGYM_EINVAL; }
-    if (a->struct_size != (int32_t)sizeof(glgym_step_args)) {     // checked before any pointer member is read
-        g_err = "glgym_step: glgym_step_args.struct_size is " + std::to_string(a->struct_size) + ", this library expects " +
-                std::to_string(sizeof(glgym_step_args)) + " (ABI " + std::to_string(GLGYM_ABI_VERSION) + "): rebuild against include/glgym.h";
-        return GLGYM_EINVAL;
-    }
-    if (a->B < 1 || a->ld < a->B || !a->x || !a->u || !a->weather || !a->w_off || !a->timestep ||
-        !a->reward || !a->done || (!a->action) == (!a->control) || a->weather_rows < 1) {
-        g_err = "glgym_step: bad arguments (exactly one of action/control, ld >= B, non-null state/outputs)";
-        return GLGYM_EINVAL;
-    }
-    if (h->step_integrator == GLGYM_INTEGRATOR_BDF) {
-        DeviceGuard dev_guard(h);
-        return with_dtype(h->dtype, [&](auto t) { return launch_step_bdf<decltype(t)>(h, a, reward_const(h, t), (hipStream_t)stream); });
-    }
-    if (h->integrator != GLGYM_INTEGRATOR_EXPLICIT) {
-        g_err = "glgym_step: GLGYM_INTEGRATOR_BDF is available to glgym_evalF only; set GLGYM_INTEGRATOR_EXPLICIT for env-steps";
-        return GLGYM_EINVAL;
-    }
+    if (const int rc = step_refusal(h, a)) return rc;
     DeviceGuard dev_guard(h);
     hipStream_t st = (hipStream_t)stream;
+    if (h->step_integrator == GLGYM_INTEGRATOR_BDF)
+        return with_dtype(h->dtype, [&](auto t) { return launch_step_bdf<decltype(t)>(h, a, reward_const(h, t), st); });
     return h->dtype == GLGYM_F32 ? launch_step<float>(h, a, h->mf, h->rf, st, oa, fused, ra)
                                  : launch_step<double>(h, a, h->md, h->rd, st);
 }

@@ -1,13 +1,14 @@
 // glgym_internal.h -- what the C entry points of every translation unit share: the handle, the thread-local error string behind
 // glgym_last_error, HIPCHK, DeviceGuard, the dtype dispatch and the host helpers of the observation / reset argument blocks.  Host code
-// only: nothing in here ends up in a kernel.  (No using-directive for glm:: -- glgym_plan.hip and glgym_rng.hip have NX / NU / NCROP of
-// their own.)
+// only: nothing in here ends up in a kernel.  (No using-directive for glm:: -- glgym_plan.hip, glgym_search.hip and glgym_rng.hip have
+// NX / NU / NCROP of their own.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "glgym.h"
@@ -75,6 +76,26 @@ struct glgym_handle_s {
     double* scratch = nullptr;
     size_t scratch_elems = 0;
 };
+
+// What glgym_step refuses, decided without launching anything (glgym.hip, where glgym_step begins with it): GLGYM_OK, or GLGYM_EINVAL
+// with glgym_step's text in g_err.  The rollouts of glgym_plan.hip ask it before their first prologue.  Not part of the C ABI.
+__attribute__((visibility("hidden"))) int step_refusal(glgym_handle h, const glgym_step_args* a);
+
+// g_err = why, and the GLGYM_EINVAL an entry point returns with it
+static inline int refuse(std::string why)
+{
+    g_err = std::move(why);
+    return GLGYM_EINVAL;
+}
+
+// struct_size of an argument block against this library's; `who` begins the message (the planning and search entry points)
+static inline bool plan_size_ok(const char* who, int32_t got, size_t want)
+{
+    if (got == (int32_t)want) return true;
+    g_err = std::string(who) + ": struct_size is " + std::to_string(got) + ", this library expects " + std::to_string(want) +
+            " (ABI " + std::to_string(GLGYM_ABI_VERSION) + "): rebuild against include/glgym.h";
+    return false;
+}
 
 // The device-pointer entry points launch on the CALLER's stream; HIP wants the calling thread's current device to be the stream's.
 // One process per GPU (the layout this library is built for) never notices; a process that holds handles on several devices does:

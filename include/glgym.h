@@ -435,7 +435,7 @@ int glgym_rng_crop_noise(glgym_handle h, void* crop_p, int B, int ld, double sca
 int glgym_rng_reset_draw(glgym_handle h, int B, int ld, const unsigned char* mask, uint64_t* rng_state, int n_years, int n_days,
                          const int32_t* start_rows, const float* start_days, int32_t* w_off, float* start_day, void* stream);
 
-/* ---- device-side planning: fork, horizon rollouts, selection (csrc/gl_plan.hpp, csrc/glgym_plan.hip) ------------------------
+/* ---- device-side planning: fork, horizon rollouts, selection (csrc/gl_plan.hpp, csrc/glgym_plan.hip; selection: csrc/glgym_search.hip)
  * Sampling-based MPC (random shooting, MPPI) on the device: from the current state of each of P parent environments, K candidate
  * control sequences are simulated over H env-steps on COPIES of the parent (children, C = P * K of them, in caller-owned buffers of
  * their own leading dimension), scored by their discounted return, and the best is picked per parent.  The parents' buffers are only
@@ -537,7 +537,7 @@ int glgym_plan_accumulate(glgym_handle h, const glgym_plan_accumulate_args* a, v
 int glgym_plan_rollout(glgym_handle h, const glgym_plan_rollout_args* a, void* stream);
 int glgym_plan_select(glgym_handle h, const glgym_plan_select_args* a, void* stream);
 
-/* ---- iterated sampling MPC: the cross-entropy method's stages between two rollouts (csrc/gl_cem.hpp, csrc/glgym_plan.hip) ------
+/* ---- iterated sampling MPC: the cross-entropy method's stages between two rollouts (csrc/gl_cem.hpp, csrc/glgym_search.hip) ----
  * One CEM iteration is glgym_plan_sample -> glgym_plan_fork + glgym_plan_rollout -> glgym_plan_elites -> glgym_plan_refit: draw K
  * candidate sequences per parent from a Gaussian per (horizon step, parent, actuator), simulate them, rank each parent's returns,
  * refit mean and spread to the E best.  Same conventions as above: struct_size first, GLGYM_EINVAL before anything is launched,
@@ -603,7 +603,7 @@ int glgym_plan_sample(glgym_handle h, const glgym_plan_sample_args* a, void* str
 int glgym_plan_elites(glgym_handle h, const glgym_plan_elites_args* a, void* stream);
 int glgym_plan_refit(glgym_handle h, const glgym_plan_refit_args* a, void* stream);
 
-/* ---- evolution strategy: mirrored sampling, centred ranks, search-gradient step (csrc/gl_es.hpp, csrc/glgym_plan.hip) -----------
+/* ---- evolution strategy: mirrored sampling, centred ranks, search-gradient step (csrc/gl_es.hpp, csrc/glgym_search.hip) ---------
  * One ES iteration is glgym_plan_es_sample -> a rollout -> glgym_plan_es_utilities -> glgym_plan_es_update.  Same layouts and
  * conventions as the CEM stages above (mean / std [H][P][6] f32, the block [H][P*K][6] f32; struct_size first; every argument is
  * checked, GLGYM_EINVAL with a glgym_last_error text, before the handle is looked at and before anything is launched; asynchronous on
@@ -684,7 +684,7 @@ int glgym_plan_es_sample(glgym_handle h, const glgym_plan_es_sample_args* a, voi
 int glgym_plan_es_utilities(glgym_handle h, const glgym_plan_es_utilities_args* a, void* stream);
 int glgym_plan_es_update(glgym_handle h, const glgym_plan_es_update_args* a, void* stream);
 
-/* ---- CMA-ES with a full covariance matrix over few, strongly interacting components (csrc/gl_cma.hpp, csrc/glgym_plan.hip) ------
+/* ---- CMA-ES with a full covariance matrix over few, strongly interacting components (csrc/gl_cma.hpp, csrc/glgym_search.hip) ----
  * One iteration is glgym_plan_cma_sample -> a rollout -> glgym_plan_elites -> glgym_plan_cma_update.  For the N <= GLGYM_CMA_NMAX
  * searched components of a rule-based controller (glgym_plan_rollout_rule); a policy net's hundreds of weights stay with the
  * separable stages above.  Same layouts and conventions as the ES stages: the block theta [Ht][P*K][6] f32 with Ht = ceil(N / 6),
@@ -772,7 +772,7 @@ typedef struct {
 int glgym_plan_cma_sample(glgym_handle h, const glgym_plan_cma_sample_args* a, void* stream);
 int glgym_plan_cma_update(glgym_handle h, const glgym_plan_cma_update_args* a, void* stream);
 
-/* ---- robust planning: scenario rollouts under crop noise, risk-aware scores (csrc/gl_scen.hpp, csrc/glgym_plan.hip) ----------
+/* ---- robust planning: scenario rollouts under crop noise, risk-aware scores (csrc/gl_scen.hpp, csrc/glgym_plan.hip; scores: csrc/glgym_search.hip)
  * With uncertainty_scale > 0 the environment multiplies the 34 crop parameters p[128..161] by 1 + U(-scale/2, scale/2) at every
  * env-step (glgym_crop_noise).  Here every one of the P*K candidates is simulated under S sampled futures of that block -- children
  * c = (p*K + k)*S + s, C = P*K*S of them -- and scored by a risk measure over its S returns, which glgym_plan_select / _elites /
@@ -844,7 +844,7 @@ int glgym_plan_scenario(glgym_handle h, const glgym_plan_scenario_args* a, void*
 int glgym_plan_rollout_scenarios(glgym_handle h, const glgym_plan_rollout_scenarios_args* a, void* stream);
 int glgym_plan_aggregate(glgym_handle h, const glgym_plan_aggregate_args* a, void* stream);
 
-/* ---- violation budgets and chance constraints in candidate ranking (csrc/gl_constr.hpp, csrc/glgym_plan.hip) -------------------
+/* ---- violation budgets and chance constraints in candidate ranking (csrc/gl_constr.hpp, csrc/glgym_search.hip) -----------------
  * A second scoring stage behind the rollout (and behind glgym_plan_aggregate, if there are scenarios): it turns the candidates'
  * returns and the accumulated violations of their runs (viol rows 0, 1, 2: CO2, temperature, humidity) into the scores that
  * glgym_plan_select / _elites / _es_utilities then rank.  Same conventions as above: struct_size first, GLGYM_EINVAL with a

@@ -1,5 +1,7 @@
 // Host (g++) instantiation of the product's csrc/gl_step_select.hpp -- tests only (tests/test_step_select_host.py): the selection in
 // batches, and the build list expanded into rows.
+#include <cstring>
+
 #include "gl_step_select.hpp"
 
 using namespace glsel;
@@ -23,6 +25,21 @@ void stepselect_batch(int n, const int* in, int* out)
         out[0] = c.error != nullptr;
         put(c.build, out + 1);
         out[9] = (int)c.grid; out[10] = c.fused;
+    }
+}
+
+// the same rows; out: n rows of 3 ints: select_step(..).error is non-null, step_pipe_error(pipe, crop, scheme) is non-null, and the two
+// agree (both null, or the same text)
+void stepselect_pipe_error_batch(int n, const int* in, int* out)
+{
+    for (int r = 0; r < n; ++r, in += 15, out += 3) {
+        const StepSelectIn s{in[0] != 0, in[1], in[2] != 0, in[3] != 0, in[4] != 0, in[5], in[6], in[7], in[8], in[9] != 0, in[10] != 0,
+                             in[11] != 0, in[12], in[13] != 0};
+        const char* sel = select_step(s).error;
+        const char* own = step_pipe_error(s.pipe, s.crop, s.scheme);
+        out[0] = sel != nullptr;
+        out[1] = own != nullptr;
+        out[2] = (sel && own) ? std::strcmp(sel, own) == 0 : sel == own;
     }
 }
 

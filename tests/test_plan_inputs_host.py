@@ -166,7 +166,7 @@ def test_a_subnormal_temperature_gives_nan_and_is_refused(planhost):
     for bad in (I.SMALLEST_SUBNORMAL, float(np.nextafter(edge, 0.0)), 0.0, -1.0, float("nan")):
         with pytest.raises(ValueError):
             _select_temperature(bad)
-    src = (ROOT / "greenlight-gym2_amd" / "csrc" / "glgym_plan.hip").read_text()
+    src = (ROOT / "greenlight-gym2_amd" / "csrc" / "glgym_search.hip").read_text()
     assert "glgym_plan_select: temperature is too small" in src and "2^-1024" in (ROOT / "include" / "glgym.h").read_text()
 
 

@@ -28,6 +28,7 @@ def host(tmp_path_factory):
     lib = C.CDLL(str(so))
     lib.stepselect_batch.argtypes, lib.stepselect_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
     lib.stepselect_builds.argtypes, lib.stepselect_builds.restype = [C.c_void_p, C.c_int], C.c_int
+    lib.stepselect_pipe_error_batch.argtypes, lib.stepselect_pipe_error_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
     lib.stepselect_error_text.restype = C.c_char_p
     lib.evalfselect_batch.argtypes, lib.evalfselect_batch.restype = [C.c_int, C.c_void_p, C.c_void_p], None
     lib.evalfselect_builds.argtypes, lib.evalfselect_builds.restype = [C.c_void_p, C.c_int], C.c_int
@@ -92,6 +93,18 @@ def test_selection_matches_the_documented_rules(selected):
 def test_error_text(host):
     assert host.stepselect_error_text() == (b"glgym_step: GLGYM_ODE_PIPE supports neither per-env crop parameters nor schemes other than "
                                             b"GLGYM_SCHEME_RK4")
+
+
+def test_pipe_rule_on_its_own_is_what_select_step_reports(host):
+    """glsel::step_pipe_error(pipe, crop, scheme) -- what glgym_step's host-side check asks before anything is launched -- against
+    select_step over the full product: one is non-null exactly when the other is, and then the two texts are equal."""
+    rows = inputs()
+    out = np.full((len(rows), 3), -7, dtype=np.int32)
+    host.stepselect_pipe_error_batch(len(rows), rows.ctypes.data, out.ctypes.data)
+    assert np.array_equal(out[:, 0], out[:, 1])
+    assert (out[:, 2] == 1).all()
+    want = (rows[:, 2] == 1) & ((rows[:, 3] == 1) | (rows[:, 1] != RK4))
+    assert np.array_equal(out[:, 1] == 1, want) and 0 < want.sum() < len(rows)
 
 
 def test_build_list_is_the_81_kernels(host):

@@ -7,7 +7,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 csrc = ROOT / "greenlight-gym2_amd" / "csrc"
 s = ""
-for unit in ("glgym", "glgym_env", "glgym_ancillary", "glgym_plan", "glgym_rng", "glgym_bdf"):
+for unit in ("glgym", "glgym_env", "glgym_ancillary", "glgym_plan", "glgym_search", "glgym_rng", "glgym_bdf"):
     out = Path(f"/tmp/{unit}_isa.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-fno-slp-vectorize",
                            "--offload-arch=gfx950", "-std=c++17", f"-I{ROOT / 'include'}", "-S", "--cuda-device-only", "-o", str(out),

@@ -6,7 +6,8 @@
     python tools/lib_bitcompare.py compare /tmp/a.npz /tmp/b.npz
 
 Workloads: the fused step in every kernel layout (fp32 one lane per environment, one- and two-wave builds; fp32 and fp64 four lanes per
-environment), actions and verified raw controls, every scheme; glgym_evalF on raw-control-jump tuples (sequential and two-rungs ladder)."""
+environment), actions and verified raw controls, every scheme; glgym_evalF on raw-control-jump tuples (sequential and two-rungs ladder);
+small seeded planner workloads through every rollout and every search stage (dump_planning)."""
 import sys
 from pathlib import Path
 
@@ -14,6 +15,50 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "greenlight-gym2_amd"))
+
+
+def dump_planning(out, w):
+    """Seeded planner workloads, 4 greenhouses x 16 candidates x 6 steps: Planner.cem with scenarios and weather_sigma, RuleSearch.cem and
+    .cma, PolicySearch.es and .cem, a constrained Planner.cem.  Kept: everything the search returns, and the children's own returns,
+    violations, step counts and flags of its last rollout."""
+    import torch
+    from gl_gym_amd.planner import Constraints, MLPSpec
+    from gl_gym_amd.tomato_env import TomatoVecEnv
+    P, K, H = 4, 16, 6
+    env = TomatoVecEnv(P, weather=w, dtype="float32", season_length=1, start_rows=[0, 96, 480, 1000], seed=5, auto_reset=False)
+    env.reset_tensor()
+    g = torch.Generator().manual_seed(11)
+    for _ in range(3):
+        env.step_tensor((torch.rand(P, 6, generator=g) * 2 - 1).to(env.device), want_obs=True)
+    tune = {"temp_setpoint_day": (16.5, 22.5), "temp_setpoint_night": (13.5, 19.5), "co2_day": (400.0, 1200.0), "rh_max": (75.0, 95.0)}
+    spec = MLPSpec(env.obs_dim, (8,), scale=0.1)
+
+    def keep(tag, res, plan):
+        def walk(prefix, v):
+            if isinstance(v, dict):
+                for k, x in v.items():
+                    walk(f"{prefix}_{k}", x)
+            elif hasattr(v, "cpu"):
+                out[prefix] = v.cpu().numpy()
+        walk(f"plan_{tag}", res)
+        for k in ("ret_t", "viol_T", "n_steps_t", "alive_t", "failed_t"):
+            out[f"plan_{tag}_child_{k}"] = getattr(plan, k).cpu().numpy()
+
+    scen = dict(n_scenarios=3, noise_scale=0.2, n_tail=2, scenario_seed=4)
+    pl = env.planner(K, H, weather_sigma=[20.0, 1.0, 50.0, 10.0, 0.5, 1.0, 0.5], weather_phi=0.6, **scen)
+    keep("cem_wscen", pl.cem(2, 4, carry=2, beta=0.5, seed=3), pl)
+    out["plan_cem_wscen_window"] = pl.weather_window_t.cpu().numpy()
+    rs = env.rule_search(K, H, tune=tune, **scen)
+    keep("rule_cem", rs.cem(2, 4, carry=2, seed=3), rs.plan)
+    rs = env.rule_search(K, H, tune=tune)
+    keep("rule_cma", rs.cma(3, seed=3), rs.plan)
+    ps = env.policy_search(K, H, spec, **scen)
+    keep("policy_es", ps.es(2, lr=0.05, seed=3), ps.plan)
+    ps = env.policy_search(K, H, spec, share="all")
+    keep("policy_cem", ps.cem(2, 4, carry=2, seed=3), ps.plan)
+    pl = env.planner(K, H, constraints=Constraints(co2=50.0, temp=0.5, rh=2.0), **scen)
+    keep("cem_constrained", pl.cem(2, 4, carry=2, seed=3), pl)
+    env.close()
 
 
 def dump(path):
@@ -53,6 +98,7 @@ def dump(path):
             except Exception as e:                   # a failed row raises: record which
                 out[f"evalF_{dtype}_{int(par)}"] = np.array([hash(str(e)) % 1000])
             m.close()
+    dump_planning(out, w)
     np.savez(path, **out)
     print("dumped", len(out), "arrays to", path)
 

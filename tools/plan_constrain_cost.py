@@ -7,7 +7,7 @@ Device events, warmed up, alternating samples; spread = (max - min) / median of 
 (a) glgym_plan_constrain on its own (both kernels, every optional output) at (P, O, K, S) = (64, 1, 1024, 1), (64, 1, 128, 8) and
     (1, 64, 8192, 1) -- share="all" over 64 greenhouses -- on seeded violations with budgets at their median, per step,
     feasibility-first; beside it the same computation written with torch ops in the same process, and the ratio, whichever way it falls.
-(b) Planner.cem and RuleSearch.cem WITHOUT constraints on this build against the parent commit's build on the same inputs: the paths the
+(b) Planner.cem, RuleSearch.cem and PolicySearch.cem WITHOUT constraints on this build against the parent commit's build on the same inputs: the paths the
     stage must leave alone.  --parent-pkg DIR: the greenlight-gym2_amd directory of a checkout of the PARENT commit with its library
     built; both sides then run in child processes of their own.  Without it the report says so and gives no verdict.
     Requirement: ratio <= 1.05.
@@ -41,9 +41,11 @@ def spread(v):
 
 
 def worker(pkg):
-    """Planner.cem and RuleSearch.cem without constraints on the build under pkg; answers "planner" / "rule" on stdin with one sample."""
+    """Planner.cem, RuleSearch.cem and PolicySearch.cem without constraints on the build under pkg; answers "planner" / "rule" / "policy"
+    on stdin with one sample."""
     sys.path.insert(0, str(pkg))
     import torch
+    from gl_gym_amd.planner import MLPSpec
     from gl_gym_amd.tomato_env import TomatoVecEnv
     from gl_gym_amd.utils import synthetic_weather
     env = TomatoVecEnv(CEM_P, weather=synthetic_weather(n_rows=35040), dtype="float32", season_length=10,
@@ -53,7 +55,9 @@ def worker(pkg):
     for _ in range(4):
         env.step_tensor((torch.rand(CEM_P, 6, generator=g) * 2 - 1).to(env.device))
     plan, rule = env.planner(CEM_K, CEM_H), env.rule_search(CEM_K, CEM_H, tune=TUNE)
-    calls = {"planner": lambda: plan.cem(CEM_ITERS, CEM_ELITES, carry=4, beta=0.5, seed=3), "rule": lambda: rule.cem(CEM_ITERS, CEM_ELITES, carry=4, seed=3)}
+    policy = env.policy_search(CEM_K, CEM_H, MLPSpec(env.obs_dim, (16,), scale=0.1))
+    calls = {"planner": lambda: plan.cem(CEM_ITERS, CEM_ELITES, carry=4, beta=0.5, seed=3), "rule": lambda: rule.cem(CEM_ITERS, CEM_ELITES, carry=4, seed=3),
+             "policy": lambda: policy.cem(CEM_ITERS, CEM_ELITES, carry=4, seed=3)}
     for fn in calls.values():
         for _ in range(N_WARM):
             timed(torch, fn, 1)
@@ -164,7 +168,7 @@ def main():
     say(f"(b) constraints=None on this build against {where}, each in a child process; fp32 ls5, {CEM_P} greenhouses x {CEM_K} candidates x "
         f"{CEM_H} steps, cem(n_iter={CEM_ITERS}, n_elite={CEM_ELITES}, carry=4); samples of {CEM_INNER} calls, ms")
     ok = True
-    for what, name in (("planner", "Planner.cem"), ("rule", "RuleSearch.cem")):
+    for what, name in (("planner", "Planner.cem"), ("rule", "RuleSearch.cem"), ("policy", "PolicySearch.cem")):
         new, old = [], []
         for _ in range(N_SAMPLES):
             new.append(sample(kids[0], what))
