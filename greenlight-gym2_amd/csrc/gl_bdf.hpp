@@ -165,7 +165,7 @@ template <class Team> GL_HD bool bdf_lu_factor(const Team& tm, BdfScratch& s, do
 }
 
 // b <- (I - c J)^-1 b on a team of one: permute, forward elimination (unit L), back substitution (U) row by row in ascending column
-// order -- the serial algorithm's order of operations.  (The wavefront's solve, WaveTeam::lu_solve in glgym_bdf.hip, keeps the
+// order -- the serial algorithm's order of operations.  (The wavefront's solve, WaveTeam::lu_solve in gl_bdf_wave.hpp, keeps the
 // forward sweep's order and runs the back substitution as a column sweep in registers.)
 GL_HD void bdf_lu_solve_serial(BdfScratch& s, double* b)
 {

@@ -10,106 +10,16 @@
 #include "glgym_bdf.h"
 
 #include "gl_bdf_env.hpp"
+#include "gl_bdf_wave.hpp"
 
 using namespace glm;
 
 namespace {
 
-constexpr int WAVE = 64;
+using glbdf::WAVE;
 
-__device__ __forceinline__ double bdf_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-// v of lane k (k compile-time after unrolling): two v_readlane, no LDS round trip
-__device__ __forceinline__ double bdf_lane(double v, int k)
-{
-    const long long bits = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, k);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), k);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-struct WaveTeam {
-    static constexpr int width = WAVE;
-    int ln;
-    const ModelConst<double>& m;
-    const CropConst<double>& cr;
-    const StepCoef<double>& s;
-    __device__ int lane() const { return ln; }
-    __device__ double sum(double v) const { return bdf_wave_sum(v); }
-    __device__ void sync() const { __syncthreads(); }
-    // butterfly over (value, index): the largest value, the smallest index among equal values, in every lane
-    __device__ void argmax(double& v, int& i) const
-    {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ov = __shfl_xor(v, o, WAVE);
-            const int oi = __shfl_xor(i, o, WAVE);
-            if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-        }
-    }
-    // (I - c J) w = b: lane i holds w_i in a register; forward sweep in the serial order, back substitution as a column sweep
-    // (w_k = w_k / U_kk final, then lanes i < k take U_ik w_k off).  Rows of lanes >= 28 mirror row 27 and are never stored.
-    __device__ void lu_solve(glbdf::BdfScratch& sh, double* b) const
-    {
-        const int ii = ln < NX ? ln : NX - 1;
-        double w = b[sh.perm[ii]];
-#pragma unroll
-        for (int k = 0; k < NX - 1; ++k) {
-            const double lik = sh.LU[ii * NX + k], wk = bdf_lane(w, k);
-            if (ln > k) w -= lik * wk;
-        }
-#pragma unroll
-        for (int k = NX - 1; k >= 0; --k) {
-            const double uik = sh.LU[ii * NX + k], wk = bdf_lane(w, k) / sh.LU[k * NX + k];
-            if (ln == k) w = wk;
-            else if (ln < k) w -= uik * wk;
-        }
-        if (ln < NX) b[ln] = w;
-        __syncthreads();
-    }
-    __device__ void eval1(const double* x, double* f) const
-    {
-        if (ln == 0) {
-            double xs[NX], k[NX];
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xs[i] = x[i];
-            rhs<double, true, false>(xs, s, m, cr, k);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) f[i] = k[i];
-        }
-        __syncthreads();
-    }
-    // lane j < 28: column j at x + dx_j e_j; lane 28 (need_f0): f0 = rhs(x) -- one call site, one right-hand-side latency
-    __device__ void jac(const double* x, double* f0, bool need_f0, double* J) const
-    {
-        double k[NX], dxj = 1.0;
-        if (ln < NX + (need_f0 ? 1 : 0)) {
-            double xs[NX];
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                const double xi = x[i];
-                if (i == ln) { dxj = 1.4901161193847656e-8 * ::fmax(::fabs(xi), 1.0); xs[i] = xi + dxj; }
-                else xs[i] = xi;
-            }
-            rhs<double, true, false>(xs, s, m, cr, k);
-        }
-        if (need_f0 && ln == NX) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) f0[i] = k[i];
-        }
-        __syncthreads();
-        if (ln < NX) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) J[i * NX + ln] = (k[i] - f0[i]) / dxj;
-        }
-        __syncthreads();
-    }
-};
+// the wavefront team (gl_bdf_wave.hpp) over the model's right-hand side
+using WaveTeam = glbdf::WaveTeam<glbdf::ModelRhs>;
 
 __global__ __launch_bounds__(WAVE) void bdf_row_kernel(const double* __restrict__ x, const double* __restrict__ u,
                                                        const double* __restrict__ d, const double* __restrict__ crop, int nd, double dt,
@@ -138,7 +48,7 @@ __global__ __launch_bounds__(WAVE) void bdf_row_kernel(const double* __restrict_
     if (ln < NU && !__builtin_isfinite(u[(size_t)b * NU + ln])) bad = 1.0;
     if (ln < 7 && !__builtin_isfinite(d[(size_t)b * nd + ln])) bad = 1.0;
     __syncthreads();
-    const WaveTeam tm{ln, sh_m[0], sh_cr[0], sh_s[0]};
+    const WaveTeam tm{ln, {sh_m[0], sh_cr[0], sh_s[0]}};
     int32_t st[glbdf::NSTAT] = {0, 0, 0, 0, 0};
     const int rc = glbdf::bdf_row(tm, sh, sh_m[0], sh_cr[0], sh_s[0], crop ? crop + (size_t)b * NCROP : nullptr, gasR, tCanMin,
                                   u + (size_t)b * NU, d + (size_t)b * nd, bad, dt, rtol, atol, max_steps, st);
@@ -169,7 +79,7 @@ __global__ __launch_bounds__(WAVE) void bdf_env_kernel(glbdf::BdfEnvArgs<T> a, M
         for (int i = ln; i < (int)(sizeof(ModelConst<double>) / 4); i += WAVE) dst[i] = src[i];
     }
     __syncthreads();
-    const WaveTeam tm{ln, sh_m[0], sh_cr[0], sh_s[0]};
+    const WaveTeam tm{ln, {sh_m[0], sh_cr[0], sh_s[0]}};
     const glbdf::BdfEnvResult<T> r = glbdf::bdf_env_row<T>(tm, sh, sh_m[0], sh_cr[0], sh_s[0], rw, a, b);
     if (metrics && ln == 0) {      // GLGYM_NMETRIC order for slots 0..7 (8..13 belong to the explicit ladder), then GLGYM_METRIC_BDF
         float* mrep = metrics + (size_t)(b % GLGYM_METRIC_REPLICAS) * GLGYM_METRIC_STRIDE;
