@@ -117,6 +117,35 @@ struct StepObsResetArgs : StepObsArgs {
     const int* start_rows; const float* start_days; int n_starts;
     unsigned long long seed;
 };
+// registers of the observation epilogue's clamp-free path (step_kernel, OBS builds with default parameters): per pass p the byte offset of
+// element q = lane + 64 p inside a forecast window, and one strip's gathered elements
+constexpr int OBS_FAST_PASSES = 4;          // nf <= 256: Np <= 51 (the default horizon, Np = 48, has nf = 240)
+template <bool ON> struct ObsFastRegs {
+    unsigned toff[OBS_FAST_PASSES];
+    float fv[OBS_FAST_PASSES][OBS_ROWS];
+    int nf, n_full;
+    bool fast;
+};
+template <> struct ObsFastRegs<false> {};
+// all gathers of the strip that starts at lane s0 (wave-uniform), issued back to back: row r's window is a scalar base
+__device__ __forceinline__ void obs_gather_strip(ObsFastRegs<true>& fr, const float* weather, int nd, int base, int s0)
+{
+    const char* rowp[OBS_ROWS];
+#pragma unroll
+    for (int r = 0; r < OBS_ROWS; ++r)
+        rowp[r] = reinterpret_cast<const char*>(weather + (size_t)(__builtin_amdgcn_readlane(base, s0 + r) + 1) * nd);
+#pragma unroll
+    for (int p = 0; p < OBS_FAST_PASSES; ++p) {
+        if (p * WAVE < fr.nf) {                 // wave-uniform
+            // (the offset is made opaque here so that its zero-extension is not hoisted out of the strip loop as a 64-bit value:
+            // scalar base + 32-bit vector offset is one addressing form, base + 64-bit vector a v_lshl_add_u64 per load)
+            unsigned t = fr.toff[p];
+            asm volatile("" : "+v"(t));
+#pragma unroll
+            for (int r = 0; r < OBS_ROWS; ++r) fr.fv[p][r] = *reinterpret_cast<const float*>(rowp[r] + t);
+        }
+    }
+}
 constexpr int GL_SCH_OBS = 8;          // step_kernel's scheme argument: | GL_SCH_OBS = the build with the observation epilogue
 constexpr int GL_SCH_RESET = 16;       // | GL_SCH_RESET (with GL_SCH_OBS): the auto-reset epilogue behind it
 template <int EPI> struct StepObsSel { using type = StepNoObs; };
@@ -349,6 +378,29 @@ __global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelCo
         for (int j = 0; j < 5; ++j) wv[j] = wrow[j];
         const float sday = o.start_day[bb];
         const float uo[NU] = {uBoil, uCo2, a.u[(size_t)2 * a.ld + bb], a.u[(size_t)3 * a.ld + bb], uLamp, a.u[(size_t)5 * a.ld + bb]};
+        // ---- the forecast block of a wavefront none of whose windows touches an end of the table (one ballot; every other wavefront
+        // takes the clamped strips below for all of its rows).  This launch runs ONE wavefront per SIMD: nothing hides an instruction or
+        // a memory round trip of the epilogue, so what does not depend on the row is computed once -- a lane's elements q = lane + 64 p
+        // and their byte offsets (i * nd + c) * 4 inside a window -- a row is a scalar base, a gathered element one load with that
+        // base and no vector address arithmetic, and all of a strip's gathers (OBS_ROWS x OBS_FAST_PASSES per lane) are in flight
+        // together: the first strip's from here, across the core features, the next strip's across the streaming-out of the current one.
+        // Compiled into the default-parameter builds only: in the handle-parameter builds, whose integrator the compiler fits into 256 +
+        // 150-200 registers, this code moved the register allocation of the sub-step loops, and they keep the epilogue they had.
+        ObsFastRegs<DEFAULT_P> fr;
+        if constexpr (DEFAULT_P) {
+            fr.nf = o.moff[5] >= 0 ? 5 * o.Np : 0;
+            fr.n_full = min(WAVE, a.B - b0) / OBS_ROWS;     // wave-uniform
+            fr.fast = fr.nf > 0 && fr.nf <= OBS_FAST_PASSES * WAVE && fr.n_full > 0 &&
+                      __builtin_amdgcn_ballot_w64(base < -1 || base >= a.weather_rows - o.Np) == 0;
+            if (fr.fast) {
+#pragma unroll
+                for (int p = 0; p < OBS_FAST_PASSES; ++p) {  // lanes past nf re-read element nf - 1 and do not write it
+                    const int q = min(lane + p * WAVE, fr.nf - 1), i = q / 5;
+                    fr.toff[p] = (unsigned)(i * a.nd + (q - i * 5)) * 4u;
+                }
+                obs_gather_strip(fr, a.weather, a.nd, base, 0);
+            }
+        }
         float f[OBS_NCORE];
 #pragma unroll
         for (int j = 0; j < OBS_NCORE; ++j) {
@@ -360,7 +412,51 @@ __global__ __launch_bounds__(WAVE, OCC) void step_kernel(StepArgsT<T> a, ModelCo
         const int n_live = min(WAVE, a.B - b0);
         const int nf = o.moff[5] >= 0 ? 5 * o.Np : 0;
         __syncthreads();                                    // the window buffer's last reader (del) is done
-        for (int s0 = 0; s0 < n_live; s0 += OBS_ROWS) {     // wave-uniform
+        int s_begin = 0;
+        if constexpr (DEFAULT_P) if (fr.fast) {
+            // the features that are a loaded value as it stands (controls, weather) have arrived before the strip loop: a wait for
+            // them inside it would, from the second strip on, wait for the stores of the strip before
+#pragma unroll
+            for (int j = 0; j < OBS_NCORE; ++j) asm volatile("" : : "v"(f[j]));
+            // full strips of a clamp-free wavefront: no per-row branch anywhere; the ragged last strip, if any, is left to the loop below
+            for (int s0 = 0; s0 < fr.n_full * OBS_ROWS; s0 += OBS_ROWS) {
+                const int r_me = lane - s0;
+                if (r_me >= 0 && r_me < OBS_ROWS) {
+#pragma unroll
+                    for (int j = 0; j < OBS_NCORE; ++j) {
+                        const int mo = o.moff[obs_core_module(j)];
+                        if (mo >= 0) span[r_me * dim + mo + obs_core_col(j)] = f[j];
+                    }
+                }
+#pragma unroll
+                for (int p = 0; p < OBS_FAST_PASSES; ++p) {
+                    const int q = lane + p * WAVE;
+                    if (q < fr.nf) {
+#pragma unroll
+                        for (int r = 0; r < OBS_ROWS; ++r) span[r * dim + o.moff[5] + q] = fr.fv[p][r];
+                    }
+                }
+                if (s0 + OBS_ROWS < fr.n_full * OBS_ROWS) obs_gather_strip(fr, a.weather, a.nd, base, s0 + OBS_ROWS);     // into the registers just written out
+                __syncthreads();
+                // the span, 16 bytes per lane: OBS_STREAM_DEPTH LDS reads in flight before the stores that consume them
+                constexpr int OBS_STREAM_DEPTH = 8;
+                const int n4 = (OBS_ROWS * dim) >> 2;
+                const v4f* src4 = reinterpret_cast<const v4f*>(span);
+                v4f* dst4 = reinterpret_cast<v4f*>(o.obs + (size_t)(b0 + s0) * dim);
+                int c0 = 0;                                 // wave-uniform
+                for (; c0 + OBS_STREAM_DEPTH * WAVE <= n4; c0 += OBS_STREAM_DEPTH * WAVE) {
+                    v4f t[OBS_STREAM_DEPTH];
+#pragma unroll
+                    for (int k = 0; k < OBS_STREAM_DEPTH; ++k) t[k] = src4[c0 + k * WAVE + lane];
+#pragma unroll
+                    for (int k = 0; k < OBS_STREAM_DEPTH; ++k) __builtin_nontemporal_store(t[k], &dst4[c0 + k * WAVE + lane]);
+                }
+                for (int e = c0 + lane; e < n4; e += WAVE) __builtin_nontemporal_store(src4[e], &dst4[e]);
+                __syncthreads();
+            }
+            s_begin = fr.n_full * OBS_ROWS;
+        }
+        for (int s0 = s_begin; s0 < n_live; s0 += OBS_ROWS) {     // wave-uniform
             const int nrows = min(OBS_ROWS, n_live - s0);
             const int r_me = lane - s0;
             if (r_me >= 0 && r_me < nrows) {
