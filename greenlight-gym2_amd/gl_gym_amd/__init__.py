@@ -4,5 +4,6 @@ the reference's env interface.  Importing the package does not need a GPU; creat
 from ._lib import GlgymError, GlgymOdeError, INFO_KEYS, METRIC_KEYS, LIB_PATH  # noqa: F401
 from .parameters import init_default_params  # noqa: F401
 from .greenlight_model import GreenLight  # noqa: F401
+from .collector import RolloutCollector, TorchHeads  # noqa: F401
 
-__all__ = ["GreenLight", "GlgymError", "GlgymOdeError", "init_default_params", "INFO_KEYS", "METRIC_KEYS", "LIB_PATH"]
+__all__ = ["GreenLight", "RolloutCollector", "TorchHeads", "GlgymError", "GlgymOdeError", "init_default_params", "INFO_KEYS", "METRIC_KEYS", "LIB_PATH"]

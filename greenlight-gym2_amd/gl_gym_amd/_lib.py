@@ -342,6 +342,23 @@ class PlanRolloutPolicyArgs(C.Structure):
                 ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p)]
 
 
+# rollout collection (include/glgym.h glgym_ac_rows / glgym_gae)
+AC_KEY_TAG = 0x41435431                                   # "ACT1": xor-ed into the high word of the noise key
+
+
+class AcRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("in_dim", C.c_int32), ("step", C.c_int32), ("deterministic", C.c_int32),
+                ("value_only", C.c_int32), ("mean_in", C.c_void_p), ("value_in", C.c_void_p), ("log_std", C.c_void_p), ("std", C.c_void_p),
+                ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p), ("obs", C.c_void_p), ("obs_out", C.c_void_p),
+                ("action", C.c_void_p), ("action_env", C.c_void_p), ("eps", C.c_void_p), ("logp", C.c_void_p), ("value", C.c_void_p)]
+
+
+class GaeArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("value", C.c_void_p), ("last_value", C.c_void_p), ("gamma", C.c_double), ("lambda_", C.c_double),
+                ("advantage", C.c_void_p), ("returns", C.c_void_p)]
+
+
 class WeatherArgs(C.Structure):
     _fields_ = [("n_raw", C.c_int32), ("time", C.c_void_p), ("i_glob", C.c_void_p), ("t_out", C.c_void_p),
                 ("rh", C.c_void_p), ("wind", C.c_void_p), ("t_sky", C.c_void_p), ("co2_ppm", C.c_double),
@@ -413,6 +430,8 @@ PROTOTYPES = {
     "glgym_plan_rollout_rule": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutRuleArgs), C.c_void_p]),
     "glgym_policy_rows": (C.c_int, [C.c_void_p, C.POINTER(PolicyRowsArgs), C.c_void_p]),
     "glgym_plan_rollout_policy": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutPolicyArgs), C.c_void_p]),
+    "glgym_ac_rows": (C.c_int, [C.c_void_p, C.POINTER(AcRowsArgs), C.c_void_p]),
+    "glgym_gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),
     "glgym_timer_start": (C.c_int, [C.c_void_p, C.c_void_p]),

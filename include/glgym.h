@@ -169,7 +169,7 @@ typedef struct {
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
  * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build; glgym_plan_cma_sample,
- * glgym_plan_cma_update; glgym_plan_constrain */
+ * glgym_plan_cma_update; glgym_plan_constrain; glgym_ac_rows, glgym_gae */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -1128,6 +1128,80 @@ typedef struct {
 
 int glgym_policy_rows(glgym_handle h, const glgym_policy_rows_args* a, void* stream);
 int glgym_plan_rollout_policy(glgym_handle h, const glgym_plan_rollout_policy_args* a, void* stream);
+
+/* ---- rollout collection: Gaussian sampling stage and GAE (csrc/gl_actor.hpp, csrc/glgym_collect.hip) ----
+ * What an on-policy learner does between two env-steps once its heads have been evaluated -- noise, sample, clip, log-probability,
+ * buffer writes -- and after the last one, the generalised advantage estimate, as two entry points.  The planning section's
+ * conventions hold: struct_size first, every refusal GLGYM_EINVAL with a message of its own before the handle is looked at and before
+ * anything is launched, asynchronous on `stream`, no allocation, no host synchronisation (capturable), plain vector stores, no
+ * atomics.  Opt-in: no other entry point changes.
+ *
+ * Heads.  The six raw means mean_in [B][6] and the value value_in [B] are the caller's: what torch modules of any size produced.
+ * (Heads evaluated inside this call are not part of the library yet.)
+ * Noise.  D = draw_index + *draw_base (draw_base NULL: 0).  Row b at step `step`: Philox4x32-10 with counter (b, 2 step + blk, lo32(D),
+ * hi32(D)), blk = 0 | 1, key (lo32(seed), hi32(seed) ^ 0x41435431); with the eight words r0..r7, u = (r + 0.5) * 2^-32 and three
+ * Box-Muller pairs in double from r0..r5 as glgym_plan_sample's: sqrt(-2 log u0) * cos(2 pi u1), ... * sin(2 pi u1); e_j = (float) of
+ * them.  Row b's noise does not depend on B.  deterministic = 1: e_j = 0, no draw.
+ * Sample, float32, every operation rounded on its own:
+ *   a_j    = mean_j + std_j * e_j                                            -> action
+ *   env_j  = fminf(fmaxf(a_j, -1), 1), a NaN reads as -1                     -> action_env, what glgym_step's action path takes
+ *   logp   = s after s = 0 and, j ascending, s = s + (((-0.5f * e_j) * e_j - log_std_j) - 0.9189385f)
+ * log_std [6] and std [6] are both the caller's device vectors (std = exp(log_std)): the kernel has no transcendental but the normals'.
+ * value = value_in, copied into the buffer slot; obs_out, if given, is a copy of obs [B][in_dim] (the slot of the observation).
+ * value_only = 1: only `value` is written (the bootstrap value after the last step); nothing else is looked at but value_in.
+ * Kernel: one lane per row, 256 per block, no LDS, no barrier; the observation copy is a block's own 256 rows, one contiguous span.
+ * Nothing outside the named outputs is written.
+ * Refused: B < 1 or > 2^31 - 256, step < 0, a flag that is not 0 | 1, a NULL value_in or value; without value_only a NULL mean_in,
+ * log_std, std, action, action_env or logp, and with obs_out an in_dim outside 1 .. 1024, a NULL obs, obs_out == obs or overlapping it. */
+typedef struct {
+    int32_t struct_size;
+    int32_t B;                   /* rows */
+    int32_t in_dim;              /* columns of obs / obs_out; looked at only with obs_out */
+    int32_t step;                /* >= 0: the step of the rollout, second word of the counter */
+    int32_t deterministic;       /* 0 | 1 */
+    int32_t value_only;          /* 0 | 1 */
+    const float* mean_in;        /* [B][6] f32 */
+    const float* value_in;       /* [B] f32 */
+    const float* log_std;        /* [6] f32 */
+    const float* std;            /* [6] f32: exp(log_std) */
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    const float* obs;            /* [B][in_dim] f32, or NULL without obs_out */
+    float* obs_out;              /* [B][in_dim] f32 out, or NULL */
+    float* action;               /* [B][6] f32 out: a */
+    float* action_env;           /* [B][6] f32 out: a clipped to [-1, 1] */
+    float* eps;                  /* [B][6] f32 out: e, or NULL */
+    float* logp;                 /* [B] f32 out */
+    float* value;                /* [B] f32 out */
+} glgym_ac_rows_args;
+
+/* GAE(lambda) over a rollout of T steps of B environments, float32, gamma and lambda cast to float once and gl = gamma * lambda one
+ * float32 product; per environment, adv = 0, then for t = T-1 .. 0:
+ *   nnt    = 1 - (done[t] != 0);  nv = t == T-1 ? last_value : value[t+1]
+ *   delta  = (reward[t] + (gamma * nv) * nnt) - value[t]
+ *   adv    = delta + (gl * nnt) * adv                      -> advantage[t]
+ *   returns[t] = adv + value[t]
+ * every product and sum rounded on its own, left to right inside the brackets -- stable_baselines3's compute_returns_and_advantage with
+ * episode_starts[t+1] == done[t].  One lane per environment, 256 per block, every access coalesced along b.
+ * Refused: T < 1, B < 1, gamma or lambda outside [0, 1] or not finite, a NULL pointer, an output that overlaps an input or the other
+ * output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t T;
+    int32_t B;
+    const float* reward;         /* [T][B] f32 */
+    const uint8_t* done;         /* [T][B] */
+    const float* value;          /* [T][B] f32 */
+    const float* last_value;     /* [B] f32: the value of the observation after step T-1 */
+    double gamma;
+    double lambda;
+    float* advantage;            /* [T][B] f32 out */
+    float* returns;              /* [T][B] f32 out */
+} glgym_gae_args;
+
+int glgym_ac_rows(glgym_handle h, const glgym_ac_rows_args* a, void* stream);
+int glgym_gae(glgym_handle h, const glgym_gae_args* a, void* stream);
 
 /* ---- on-device VecNormalize ---------------------------------------------------------------------
  * Replaces stable_baselines3.common.vec_env.VecNormalize (3rd party, pinned ==2.6.0 in the reference's requirements.txt)
