@@ -359,6 +359,30 @@ class GaeArgs(C.Structure):
                 ("advantage", C.c_void_p), ("returns", C.c_void_p)]
 
 
+# PPO update (include/glgym.h glgym_ppo_batch / glgym_ppo_loss)
+PPO_KEY_TAG = 0x50524D31                                  # "PRM1": xor-ed into the high word of the permutation's key
+PPO_MAX_BLOCKS, PPO_N_SUM, PPO_N_ADV = 1024, 11, 2
+PPO_BATCH_WS_BYTES, PPO_LOSS_WS_BYTES = PPO_MAX_BLOCKS * PPO_N_ADV * 8, PPO_MAX_BLOCKS * PPO_N_SUM * 8
+PPO_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "max_ratio", "n")
+
+
+class PpoBatchArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("offset", C.c_int32), ("in_dim", C.c_int32),
+                ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p), ("obs", C.c_void_p), ("action", C.c_void_p),
+                ("logp", C.c_void_p), ("advantage", C.c_void_p), ("returns", C.c_void_p), ("value", C.c_void_p), ("mb_obs", C.c_void_p),
+                ("mb_action", C.c_void_p), ("mb_logp", C.c_void_p), ("mb_adv", C.c_void_p), ("mb_ret", C.c_void_p), ("mb_value", C.c_void_p),
+                ("mb_index", C.c_void_p), ("adv_stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class PpoLossArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("mean", C.c_void_p), ("value", C.c_void_p), ("log_std", C.c_void_p),
+                ("inv_std", C.c_void_p), ("mb_action", C.c_void_p), ("mb_logp", C.c_void_p), ("mb_adv", C.c_void_p), ("mb_ret", C.c_void_p),
+                ("mb_value", C.c_void_p), ("adv_stats", C.c_void_p), ("clip_range", C.c_double), ("clip_range_vf", C.c_double),
+                ("vf_coef", C.c_double), ("ent_coef", C.c_double), ("grad_mean", C.c_void_p), ("grad_value", C.c_void_p),
+                ("grad_log_std", C.c_void_p), ("stats", C.c_void_p), ("ratio_out", C.c_void_p), ("logp_out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class WeatherArgs(C.Structure):
     _fields_ = [("n_raw", C.c_int32), ("time", C.c_void_p), ("i_glob", C.c_void_p), ("t_out", C.c_void_p),
                 ("rh", C.c_void_p), ("wind", C.c_void_p), ("t_sky", C.c_void_p), ("co2_ppm", C.c_double),
@@ -432,6 +456,8 @@ PROTOTYPES = {
     "glgym_plan_rollout_policy": (C.c_int, [C.c_void_p, C.POINTER(PlanRolloutPolicyArgs), C.c_void_p]),
     "glgym_ac_rows": (C.c_int, [C.c_void_p, C.POINTER(AcRowsArgs), C.c_void_p]),
     "glgym_gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs), C.c_void_p]),
+    "glgym_ppo_batch": (C.c_int, [C.c_void_p, C.POINTER(PpoBatchArgs), C.c_void_p]),
+    "glgym_ppo_loss": (C.c_int, [C.c_void_p, C.POINTER(PpoLossArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),
     "glgym_timer_start": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -2,7 +2,7 @@
 OnPolicyAlgorithm.collect_rollouts does between two optimiser phases -- observation -> stochastic policy and value -> env-step ->
 buffer, then GAE(lambda).  The two heads are torch modules (TorchHeads); everything behind them -- the action noise, the sample, the
 clip, the log-probability, the buffer writes -- is one library launch per step, and the advantages are one launch per rollout.  The
-buffer, the noise and the advantages never leave the device; the optimiser step is the caller's, in torch.
+buffer, the noise and the advantages never leave the device; the optimiser phase over the buffer is gl_gym_amd.ppo.PPO, or the caller's.
 
     heads = TorchHeads(pi_module, vf_module, log_std)   # the modules the optimiser trains: nothing to copy back after a step
     col = RolloutCollector(env, 64, heads, gamma=0.9631)

@@ -169,7 +169,7 @@ typedef struct {
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
  * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build; glgym_plan_cma_sample,
- * glgym_plan_cma_update; glgym_plan_constrain; glgym_ac_rows, glgym_gae */
+ * glgym_plan_cma_update; glgym_plan_constrain; glgym_ac_rows, glgym_gae; glgym_ppo_batch, glgym_ppo_loss */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -1202,6 +1202,114 @@ typedef struct {
 
 int glgym_ac_rows(glgym_handle h, const glgym_ac_rows_args* a, void* stream);
 int glgym_gae(glgym_handle h, const glgym_gae_args* a, void* stream);
+
+/* ---- PPO update: seeded minibatches and the clipped-surrogate loss (csrc/gl_ppo.hpp, csrc/glgym_ppo.hip) ----
+ * The other half of the on-policy loop: what stable_baselines3's PPO.train does around the two heads -- the shuffle, the minibatch
+ * gathers, the advantage normalisation, the loss with its gradients with respect to the heads' outputs -- as two entry points.  The heads
+ * themselves, their backward pass and the optimiser stay the caller's, in torch.  The planning section's conventions hold: struct_size
+ * first, every refusal GLGYM_EINVAL with a message of its own before the handle is looked at and before anything is launched,
+ * asynchronous on `stream`, no allocation, no host synchronisation (capturable), plain vector stores, no atomics.  Opt-in: no other
+ * entry point changes.
+ *
+ * Permutation.  D = draw_index + *draw_base (draw_base NULL: 0).  Position p in [0, N) -> transition perm(p) in [0, N), computed per
+ * index, never stored: w = the smallest even bit count >= 2 with 2^w >= N, half = w / 2, mask = 2^half - 1.  P(x) on [0, 2^w): L = x >> half,
+ * R = x & mask; four rounds r = 0..3 of (L, R) = (R, L ^ (F(r, R) & mask)); P = (L << half) | R, where F(r, R) is word 0 of Philox4x32-10
+ * with counter (R, r, lo32(D), hi32(D)) and key (lo32(seed), hi32(seed) ^ 0x50524d31).  perm(p): y = P(p); while y >= N: y = P(y).  It
+ * depends on (seed, D, N) only -- not on M, offset or the launch.
+ * Reductions (both entry points).  Rows are cut into chunks of 256; nb = min(ceil(M / 256), 1024) blocks of 256 lanes; block b takes
+ * chunks b, b + nb, ...; lane t takes row 256 chunk + t of each, ascending, and adds its terms in double from 0.  The 64 lanes of a
+ * wavefront combine by butterfly (xor 32, 16, .. 1), the four wavefronts of a block in index order, the blocks' partials go to
+ * `workspace` and a finishing launch of the same call adds them in block order.  A function of M alone.
+ *
+ * glgym_ppo_batch: minibatch positions [offset, offset + M) of the permutation, gathered from flat [N] sources (a collector's buffer
+ * viewed as [T*B]).  Row m of every output is row perm(offset + m) of its source, bit for bit; mb_index, if given, is perm(offset + m).
+ * A block's output rows are one contiguous span written with lane stride 1; a row's permutation is computed once and shared.
+ * adv_stats, if given: [0] = S1 / M and [1] = sqrt(max(0, (S2 - (S1 * S1) / M) / (M - 1))) of the minibatch's advantages, S1 = sum a,
+ * S2 = sum a * a in double by the reduction above, every operation rounded on its own.  workspace: [1024][2] doubles = 16 384 bytes,
+ * needed with adv_stats only.
+ * Refused: N or M < 1, N > 2^31 - 256, offset < 0 or offset + M > N, in_dim outside 1 .. 1024, a NULL source or output other than
+ * mb_index / adv_stats, adv_stats with M < 2 or with a NULL or undersized workspace, an output that overlaps a source or another output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t N;                   /* transitions in the sources */
+    int32_t M;                   /* rows of this minibatch */
+    int32_t offset;              /* first position of the permutation */
+    int32_t in_dim;              /* columns of obs */
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    const float* obs;            /* [N][in_dim] f32 */
+    const float* action;         /* [N][6] f32 */
+    const float* logp;           /* [N] f32 */
+    const float* advantage;      /* [N] f32 */
+    const float* returns;        /* [N] f32 */
+    const float* value;          /* [N] f32 */
+    float* mb_obs;               /* [M][in_dim] f32 out */
+    float* mb_action;            /* [M][6] f32 out */
+    float* mb_logp;              /* [M] f32 out */
+    float* mb_adv;               /* [M] f32 out */
+    float* mb_ret;               /* [M] f32 out */
+    float* mb_value;             /* [M] f32 out */
+    int32_t* mb_index;           /* [M] i32 out, or NULL */
+    double* adv_stats;           /* [2] out: mean, unbiased standard deviation of mb_adv, or NULL */
+    double* workspace;           /* [1024][2] doubles, or NULL without adv_stats */
+    int64_t workspace_bytes;
+} glgym_ppo_batch_args;
+
+/* glgym_ppo_loss: the clipped-surrogate loss of stable_baselines3's PPO.train on the heads' outputs of one minibatch, forward and
+ * backward in one call.  float32, every operation rounded on its own, in this order (c = clip_range, cv = clip_range_vf,
+ * w = (float)(1.0 / M), the coefficients cast to float once); per row:
+ *   z_j    = (a_j - mean_j) * inv_std_j                          inv_std = exp(-log_std) is the caller's, as std is glgym_ac_rows'
+ *   logp   = s after s = 0 and, j ascending, s = s + (((-0.5f * z_j) * z_j - log_std_j) - 0.9189385f)          -> logp_out
+ *   d      = logp - old_logp;  ratio = (float) exp((double) d)                                                   -> ratio_out
+ *   A      = adv, or with adv_stats (adv - (float) adv_stats[0]) / ((float) adv_stats[1] + 1e-8f)
+ *   s1     = ratio * A;  rc = fminf(fmaxf(ratio, 1 - c), 1 + c);  s2 = rc * A;  surrogate = fminf(s1, s2)
+ *   q      = s1 <= s2 ? (-w) * s1 : 0          (what the backward passes of min and clamp add up to, the tie inside the clip range included)
+ *   grad_mean_j = q * (z_j * inv_std_j);  the row's term for log_std_j = q * (z_j * z_j - 1)
+ *   vp     = value, or with cv > 0 old_v + fminf(fmaxf(value - old_v, -cv), cv);  value term = (ret - vp) * (ret - vp)
+ *   grad_value  = ((vf_coef * 2) * w) * (vp - ret), or 0 where value - old_v lies outside [-cv, cv]
+ *   kl term = (ratio - 1) - d;  clip term = |ratio - 1| > c
+ * The rows' terms are added in double by the reduction above (the largest ratio with max in place of +, a NaN winning), then
+ *   policy_loss = -(sum surrogate / M);  value_loss = sum value term / M
+ *   entropy_loss = -e after e = 0 and, j ascending, e = e + ((0.5f + 0.9189385f) + log_std_j)      (float32)
+ *   stats = { (policy_loss + ent_coef * entropy_loss) + vf_coef * value_loss, policy_loss, value_loss, entropy_loss, sum kl / M,
+ *             sum clip / M, max ratio, M }                                                          (double)
+ *   grad_log_std_j = (float)(sum of the rows' terms) - ent_coef                                     (float32)
+ * A NaN stays in its row: its gradients, logp, ratio and kl are NaN and so are the sums they enter; fminf / fmaxf hand on their other
+ * operand, so the surrogate of a row whose ratio is NaN reads (1 - c) * A.  Nothing traps; nothing outside the named outputs is written.
+ * Kernel: one lane per row, 256 per block, LDS for combining the wavefronts only.  workspace: [1024][11] doubles = 90 112 bytes.
+ * Refused: M < 1 or > 2^31 - 256, clip_range not > 0 or not finite, a coefficient or clip_range_vf that is not finite, clip_range_vf > 0
+ * without mb_value, a NULL pointer other than adv_stats / mb_value / ratio_out / logp_out, an undersized workspace, an output that
+ * overlaps an input or another output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t M;
+    const float* mean;           /* [M][6] f32: the policy head's output */
+    const float* value;          /* [M] f32: the value head's output */
+    const float* log_std;        /* [6] f32 */
+    const float* inv_std;        /* [6] f32: exp(-log_std) */
+    const float* mb_action;      /* [M][6] f32 */
+    const float* mb_logp;        /* [M] f32: old_logp */
+    const float* mb_adv;         /* [M] f32 */
+    const float* mb_ret;         /* [M] f32 */
+    const float* mb_value;       /* [M] f32: old_v, or NULL with clip_range_vf <= 0 */
+    const double* adv_stats;     /* [2]: glgym_ppo_batch's, or NULL: no normalisation */
+    double clip_range;           /* > 0 */
+    double clip_range_vf;        /* <= 0: off */
+    double vf_coef;
+    double ent_coef;
+    float* grad_mean;            /* [M][6] f32 out */
+    float* grad_value;           /* [M] f32 out */
+    float* grad_log_std;         /* [6] f32 out */
+    double* stats;               /* [8] out */
+    float* ratio_out;            /* [M] f32 out, or NULL */
+    float* logp_out;             /* [M] f32 out, or NULL */
+    double* workspace;           /* [1024][11] doubles */
+    int64_t workspace_bytes;
+} glgym_ppo_loss_args;
+
+int glgym_ppo_batch(glgym_handle h, const glgym_ppo_batch_args* a, void* stream);
+int glgym_ppo_loss(glgym_handle h, const glgym_ppo_loss_args* a, void* stream);
 
 /* ---- on-device VecNormalize ---------------------------------------------------------------------
  * Replaces stable_baselines3.common.vec_env.VecNormalize (3rd party, pinned ==2.6.0 in the reference's requirements.txt)
