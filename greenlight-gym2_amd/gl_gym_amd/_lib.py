@@ -383,6 +383,51 @@ class PpoLossArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+# soft actor-critic (include/glgym.h glgym_sac_rows / glgym_sac_rows_grad / glgym_sac_batch / glgym_sac_loss / glgym_polyak)
+SAC_KEY_TAG, SAC_SAMPLE_TAG = 0x53414331, 0x534D5031      # "SAC1", "SMP1": xor-ed into the high word of the noise and the sampling key
+SAC_N_SUM, SAC_MAX_TENSORS = 5, 64
+SAC_LOSS_WS_BYTES = PPO_MAX_BLOCKS * SAC_N_SUM * 8
+SAC_CRITIC, SAC_ACTOR = 0, 1
+SAC_CRITIC_STATS = ("critic_loss", "q1_mse", "q2_mse", "q1_mean", "q2_mean", "target_mean", "alpha", "n")
+SAC_ACTOR_STATS = ("actor_loss", "ent_coef_loss", "grad_log_alpha", "logp_mean", "alpha", "log_alpha", "unused", "n")
+# one row of SAC.update's stats_t
+SAC_STATS = ("critic_loss", "actor_loss", "ent_coef_loss", "alpha", "logp_mean", "q1_mean", "target_mean", "n")
+
+
+class SacRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("in_dim", C.c_int32), ("step", C.c_int32), ("deterministic", C.c_int32),
+                ("uniform", C.c_int32), ("row0", C.c_int64), ("mean_in", C.c_void_p), ("log_std_in", C.c_void_p), ("seed", C.c_uint64),
+                ("draw_index", C.c_uint64), ("draw_base", C.c_void_p), ("action_noise_sigma", C.c_double), ("obs", C.c_void_p),
+                ("obs_out", C.c_void_p), ("action", C.c_void_p), ("action_env", C.c_void_p), ("action_slot", C.c_void_p), ("logp", C.c_void_p),
+                ("eps", C.c_void_p), ("eps2", C.c_void_p), ("std", C.c_void_p), ("tanh", C.c_void_p), ("corr", C.c_void_p)]
+
+
+class SacRowsGradArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("grad_action", C.c_void_p), ("grad_logp", C.c_void_p), ("eps", C.c_void_p),
+                ("std", C.c_void_p), ("tanh", C.c_void_p), ("log_std_in", C.c_void_p), ("grad_mean", C.c_void_p), ("grad_log_std", C.c_void_p)]
+
+
+class SacBatchArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("in_dim", C.c_int32), ("M", C.c_int32), ("head", C.c_int32),
+                ("n_valid", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("draw_index", C.c_uint64), ("draw_base", C.c_void_p),
+                ("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("mb_obs", C.c_void_p),
+                ("mb_next_obs", C.c_void_p), ("mb_action", C.c_void_p), ("mb_reward", C.c_void_p), ("mb_done", C.c_void_p),
+                ("index_out", C.c_void_p)]
+
+
+class SacLossArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("stage", C.c_int32), ("reserved", C.c_int32), ("q1", C.c_void_p),
+                ("q2", C.c_void_p), ("logp", C.c_void_p), ("q1_next", C.c_void_p), ("q2_next", C.c_void_p), ("reward", C.c_void_p),
+                ("done", C.c_void_p), ("alpha", C.c_void_p), ("log_alpha", C.c_void_p), ("gamma", C.c_double), ("target_entropy", C.c_double),
+                ("grad_q1", C.c_void_p), ("grad_q2", C.c_void_p), ("grad_logp", C.c_void_p), ("target_out", C.c_void_p),
+                ("grad_log_alpha", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class PolyakArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n", C.c_int32), ("dst", C.c_void_p), ("src", C.c_void_p), ("count", C.c_void_p),
+                ("max_count", C.c_int64), ("tau", C.c_double)]
+
+
 class WeatherArgs(C.Structure):
     _fields_ = [("n_raw", C.c_int32), ("time", C.c_void_p), ("i_glob", C.c_void_p), ("t_out", C.c_void_p),
                 ("rh", C.c_void_p), ("wind", C.c_void_p), ("t_sky", C.c_void_p), ("co2_ppm", C.c_double),
@@ -458,6 +503,11 @@ PROTOTYPES = {
     "glgym_gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs), C.c_void_p]),
     "glgym_ppo_batch": (C.c_int, [C.c_void_p, C.POINTER(PpoBatchArgs), C.c_void_p]),
     "glgym_ppo_loss": (C.c_int, [C.c_void_p, C.POINTER(PpoLossArgs), C.c_void_p]),
+    "glgym_sac_rows": (C.c_int, [C.c_void_p, C.POINTER(SacRowsArgs), C.c_void_p]),
+    "glgym_sac_rows_grad": (C.c_int, [C.c_void_p, C.POINTER(SacRowsGradArgs), C.c_void_p]),
+    "glgym_sac_batch": (C.c_int, [C.c_void_p, C.POINTER(SacBatchArgs), C.c_void_p]),
+    "glgym_sac_loss": (C.c_int, [C.c_void_p, C.POINTER(SacLossArgs), C.c_void_p]),
+    "glgym_polyak": (C.c_int, [C.c_void_p, C.POINTER(PolyakArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),
     "glgym_timer_start": (C.c_int, [C.c_void_p, C.c_void_p]),

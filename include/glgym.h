@@ -169,7 +169,8 @@ typedef struct {
  * glgym_plan_sample, glgym_plan_elites, glgym_plan_refit; glgym_plan_scenario, glgym_plan_rollout_scenarios, glgym_plan_aggregate;
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
  * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build; glgym_plan_cma_sample,
- * glgym_plan_cma_update; glgym_plan_constrain; glgym_ac_rows, glgym_gae; glgym_ppo_batch, glgym_ppo_loss */
+ * glgym_plan_cma_update; glgym_plan_constrain; glgym_ac_rows, glgym_gae; glgym_ppo_batch, glgym_ppo_loss; glgym_sac_rows,
+ * glgym_sac_rows_grad, glgym_sac_batch, glgym_sac_loss, glgym_polyak */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -1310,6 +1311,190 @@ typedef struct {
 
 int glgym_ppo_batch(glgym_handle h, const glgym_ppo_batch_args* a, void* stream);
 int glgym_ppo_loss(glgym_handle h, const glgym_ppo_loss_args* a, void* stream);
+
+/* ---- soft actor-critic: replay ring, squashed actor, loss stage, Polyak update (csrc/gl_sac.hpp, csrc/glgym_sac.hip) ----
+ * The off-policy twin of the two sections above: what stable_baselines3's SAC does between the networks' outputs and their gradients, as
+ * five entry points.  The actor, the two critics, the two target critics, autograd through them and the optimisers stay the caller's, in
+ * torch.  The planning section's conventions hold: struct_size first, every refusal GLGYM_EINVAL with a message of its own before the
+ * handle is looked at and before anything is launched, asynchronous on `stream`, no allocation, no host synchronisation (capturable),
+ * plain vector stores, no atomics.  Opt-in: no other entry point changes.  Reductions are those of the PPO section: chunks of 256 rows,
+ * nb = min(ceil(M / 256), 1024) blocks, lane / butterfly / wavefronts in index order / blocks in block order, in double, through
+ * `workspace` and a finishing launch -- a function of M alone.
+ *
+ * glgym_sac_rows: the tanh-squashed Gaussian with a state-dependent deviation, forward.  mean_in [M][6] and log_std_in [M][6] are the
+ * actor's two outputs.
+ * Noise.  D = draw_index + *draw_base (draw_base NULL: 0).  Row r has the key k = (uint32)(row0 + r): Philox4x32-10 with counter
+ * (k, 4 step + blk, lo32(D), hi32(D)), key (lo32(seed), hi32(seed) ^ 0x53414331 "SAC1").  blk = 0 | 1 give eight words and e_0..e_5 by
+ * three Box-Muller pairs in double from words 0..5, each rounded once to float32, as glgym_ac_rows; blk = 2 | 3 give e2_0..e2_5 the same
+ * way.  A row's noise depends on neither M nor any other row.
+ * Per actuator j, float32, every operation rounded on its own, in this order:
+ *   ls   = fminf(fmaxf(log_std_j, -20), 2)
+ *   std  = (float) exp((double) ls)                                                     -> std
+ *   u    = mean_j + std * e_j                                                           (e -> eps, e2 -> eps2)
+ *   a    = (float) tanh((double) u)                                                     -> action, tanh
+ *   c    = (1 - a * a) + 1e-6f
+ *   l    = (float) log((double) c)                                                      -> corr
+ *   logp = s after s = 0; j ascending: s = s + (((-0.5f * e_j) * e_j - ls_j) - 0.9189385f); then j ascending: s = s - l_j     -> logp
+ *   env  = fminf(fmaxf(a, -1), 1); with action_noise_sigma > 0: fminf(fmaxf(a + sigma * e2_j, -1), 1)      -> action_env, action_slot
+ * A NaN reads as -1 in env, whatever its source.  deterministic = 1: e_j = 0 (e2 is still drawn with sigma > 0).  uniform = 1 (the
+ * learning_starts warm-up): a_j = (float)(2.0 * (((double) r_j + 0.5) * 2^-32) - 1.0) from words r_0..r_5 of blk 0 | 1, env_j its clip;
+ * mean_in and log_std_in are not looked at and only action, action_env, action_slot and obs_out are written.
+ * Every output is optional; at least one must be given.  eps2 and corr are diagnostic outputs: they exist so that a test can hand the
+ * device's own noise and log term to a host build, nothing in the library reads them and callers should not depend on them.  obs_out is a copy of obs [M][in_dim].  Kernel: one lane per row, 256 per block,
+ * no LDS, no barrier.  Nothing outside the named outputs is written.
+ * Refused: M < 1 or > 2^31 - 256, step outside 0 .. 2^30 - 1, row0 < 0 or row0 + M > 2^32, a flag that is not 0 | 1, both flags set,
+ * action_noise_sigma negative or not finite, no output at all, without uniform a NULL mean_in or log_std_in, with uniform a logp, eps,
+ * eps2, std, tanh or corr output, with obs_out an in_dim outside 1 .. 1024, a NULL obs, obs_out overlapping obs. */
+typedef struct {
+    int32_t struct_size;
+    int32_t M;                   /* rows */
+    int32_t in_dim;              /* columns of obs / obs_out; looked at only with obs_out */
+    int32_t step;                /* 0 .. 2^30 - 1: second word of the counter is 4 step + blk */
+    int32_t deterministic;       /* 0 | 1 */
+    int32_t uniform;             /* 0 | 1 */
+    int64_t row0;                /* the noise of row r is keyed by row0 + r */
+    const float* mean_in;        /* [M][6] f32 */
+    const float* log_std_in;     /* [M][6] f32 */
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    double action_noise_sigma;   /* 0: off */
+    const float* obs;            /* [M][in_dim] f32, or NULL without obs_out */
+    float* obs_out;              /* [M][in_dim] f32 out, or NULL */
+    float* action;               /* [M][6] f32 out: a, or NULL */
+    float* action_env;           /* [M][6] f32 out: env, or NULL */
+    float* action_slot;          /* [M][6] f32 out: env once more (a replay slot), or NULL */
+    float* logp;                 /* [M] f32 out, or NULL */
+    float* eps;                  /* [M][6] f32 out: e, or NULL */
+    float* eps2;                 /* [M][6] f32 out, DIAGNOSTIC (tests; may change): e2 (0 without action_noise_sigma > 0), or NULL */
+    float* std;                  /* [M][6] f32 out, or NULL */
+    float* tanh;                 /* [M][6] f32 out: a, or NULL */
+    float* corr;                 /* [M][6] f32 out, DIAGNOSTIC (tests; may change): l, or NULL */
+} glgym_sac_rows_args;
+
+/* glgym_sac_rows_grad: the reparameterised backward pass of glgym_sac_rows from what it saved.  Per element, float32, every operation
+ * rounded on its own, in this order (ga = grad_action_j, gl = grad_logp of the row, a = tanh_j, e = eps_j):
+ *   g  = 1 - a * a
+ *   gu = (ga * g) + (gl * (((2 * a) * g) / (g + 1e-6f)))                               -> grad_mean
+ *   grad_log_std = ((gu * (std * e)) - gl) where -20 <= log_std_in_j <= 2, else 0 (a NaN log_std_in: 0)
+ * One lane per row.  Refused: M < 1 or > 2^31 - 256, a NULL pointer, an output that overlaps an input or the other output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t M;
+    const float* grad_action;    /* [M][6] f32 */
+    const float* grad_logp;      /* [M] f32 */
+    const float* eps;            /* [M][6] f32 */
+    const float* std;            /* [M][6] f32 */
+    const float* tanh;           /* [M][6] f32 */
+    const float* log_std_in;     /* [M][6] f32 */
+    float* grad_mean;            /* [M][6] f32 out */
+    float* grad_log_std;         /* [M][6] f32 out */
+} glgym_sac_rows_grad_args;
+
+/* glgym_sac_batch: M transitions drawn with replacement from a replay ring of S slots of B environments, slot-major: obs [S][B][in_dim],
+ * action [S][B][6], reward [S][B], done [S][B] (uint8).  An observation is stored once: the next observation of slot s is the observation
+ * of slot (s + 1) mod S.  head is the oldest valid slot and n_valid the number of slots, counted from head, whose successor observation
+ * has been written (1 <= n_valid <= S - 1).
+ * Position p in [0, M) of draw D = draw_index + *draw_base: Philox4x32-10 with counter (p, 0, lo32(D), hi32(D)) and key (lo32(seed),
+ * hi32(seed) ^ 0x534d5031 "SMP1"); w = word0 * 2^32 + word1; idx = floor(w * n / 2^64) with n = n_valid * B (its bias is at most
+ * n / 2^64); slot = (head + idx / B) mod S, b = idx mod B.  Row p of mb_obs, mb_action, mb_reward, mb_done is row (slot, b) of its source,
+ * row p of mb_next_obs is row ((slot + 1) mod S, b) of obs, bit for bit; index_out, if given, is slot * B + b.  It depends on (seed, D, S,
+ * B, head, n_valid) and p only.  A block's output rows are one contiguous span written with lane stride 1; the row indices are staged in LDS.
+ * Refused: S < 2, B < 1, S * B > 2^31 - 1, M < 1 or > 2^31 - 256, in_dim outside 1 .. 1024, head outside 0 .. S - 1, n_valid < 1,
+ * n_valid > S - 1 (a slot without a successor), a NULL pointer other than index_out / draw_base, an output that overlaps a source or
+ * another output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t S;                   /* slots of the ring */
+    int32_t B;                   /* environments per slot */
+    int32_t in_dim;              /* columns of obs */
+    int32_t M;                   /* rows of the minibatch */
+    int32_t head;                /* oldest valid slot */
+    int32_t n_valid;             /* slots with a written successor observation */
+    int32_t reserved;            /* 0 */
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    const float* obs;            /* [S][B][in_dim] f32 */
+    const float* action;         /* [S][B][6] f32 */
+    const float* reward;         /* [S][B] f32 */
+    const uint8_t* done;         /* [S][B] */
+    float* mb_obs;               /* [M][in_dim] f32 out */
+    float* mb_next_obs;          /* [M][in_dim] f32 out */
+    float* mb_action;            /* [M][6] f32 out */
+    float* mb_reward;            /* [M] f32 out */
+    uint8_t* mb_done;            /* [M] out */
+    int64_t* index_out;          /* [M] i64 out, or NULL */
+} glgym_sac_batch_args;
+
+/* glgym_sac_loss: the critic stage (stage = 0) or the actor stage (stage = 1) of stable_baselines3's SAC.train, forward and backward in
+ * one call.  alpha [1] is a device float the caller forms as exp(log_alpha) (as std is the caller's in glgym_ac_rows); w = (float)(1.0 / M);
+ * gamma and target_entropy are cast to float once.  float32, every operation rounded on its own, in this order; per row:
+ * Critic stage (q1, q2: the critics on (obs, action); q1_next, q2_next: the target critics on (next_obs, next action); logp: the next
+ * action's log-probability):
+ *   m  = fminf(q1_next, q2_next)
+ *   y  = reward + (((1 - done) * gamma) * (m - (alpha * logp)))                        -> target_out      (done != 0 reads as 1)
+ *   grad_q1 = w * (q1 - y);  grad_q2 = w * (q2 - y)
+ *   sums in double of (q1 - y) * (q1 - y), (q2 - y) * (q2 - y), q1, q2, y  =: S1, S2, Q1, Q2, Y
+ *   stats = { (0.5 * (S1 + S2)) / M, S1 / M, S2 / M, Q1 / M, Q2 / M, Y / M, alpha, M }
+ * Actor stage (q1, q2: the critics on (obs, the policy's action); logp: that action's log-probability):
+ *   grad_logp = w * alpha;  grad_q1 = q1 <= q2 ? -w : 0;  grad_q2 = q1 <= q2 ? 0 : -w
+ *   sums in double of (alpha * logp) - fminf(q1, q2), logp + target_entropy, logp  =: A, E, P
+ *   stats = { A / M, -(log_alpha * (E / M)), -(E / M), P / M, alpha, log_alpha, 0, M };  grad_log_alpha = (float)(-(E / M))
+ * stats[1] is the entropy coefficient's loss -(log_alpha) * mean(logp + target_entropy) and stats[2] its gradient.
+ * NaN: fminf hands on its other operand, so a NaN q1_next alone leaves the target finite; a NaN in both, in logp, reward or alpha gives a NaN
+ * y, NaN gradients of that row and NaN sums they enter.  In the actor stage a NaN q1 fails q1 <= q2: the row's gradient goes to q2, and
+ * the loss term is alpha logp - q2.  Nothing traps; nothing outside the named outputs is written.
+ * Kernel: one lane per row, 256 per block, LDS for combining the wavefronts only.  workspace: [1024][5] doubles = 40 960 bytes.
+ * Refused: M < 1 or > 2^31 - 256, a stage other than 0 | 1, gamma outside [0, 1] or target_entropy not finite, a NULL q1, q2, logp,
+ * alpha, grad_q1, grad_q2, stats or workspace, in the critic stage a NULL q1_next, q2_next, reward or done, in the actor stage a NULL
+ * log_alpha or grad_logp, an undersized workspace, an output that overlaps an input or another output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t M;
+    int32_t stage;               /* 0: critic, 1: actor */
+    int32_t reserved;            /* 0 */
+    const float* q1;             /* [M] f32 */
+    const float* q2;             /* [M] f32 */
+    const float* logp;           /* [M] f32 */
+    const float* q1_next;        /* [M] f32, critic stage */
+    const float* q2_next;        /* [M] f32, critic stage */
+    const float* reward;         /* [M] f32, critic stage */
+    const uint8_t* done;         /* [M], critic stage */
+    const float* alpha;          /* [1] f32 device: exp(log_alpha) */
+    const float* log_alpha;      /* [1] f32 device, actor stage */
+    double gamma;                /* critic stage */
+    double target_entropy;       /* actor stage */
+    float* grad_q1;              /* [M] f32 out */
+    float* grad_q2;              /* [M] f32 out */
+    float* grad_logp;            /* [M] f32 out, actor stage */
+    float* target_out;           /* [M] f32 out, critic stage, or NULL */
+    float* grad_log_alpha;       /* [1] f32 out, actor stage, or NULL */
+    double* stats;               /* [8] out */
+    double* workspace;           /* [1024][5] doubles */
+    int64_t workspace_bytes;
+} glgym_sac_loss_args;
+
+/* glgym_polyak: t = ((1 - tau) * t) + (tau * s) over a table of n <= 64 tensors in one launch, float32, 1 - tau one float32 difference of
+ * (float) tau formed once, the two products rounded separately.  dst [n], src [n] (device arrays of device pointers) and count [n] (device
+ * int64 element counts) are uploaded once by the caller; max_count, the largest count, only sizes the grid (the kernel strides over it:
+ * a smaller value is slower, never wrong).  Every element is a dword access, so a tensor needs 4-byte alignment only; a tensor of 0
+ * elements is skipped.  Refused: n outside 1 .. 64, a NULL table, tau outside [0, 1] or not finite, max_count < 0. */
+typedef struct {
+    int32_t struct_size;
+    int32_t n;
+    float* const* dst;           /* [n] device: the target tensors t */
+    const float* const* src;     /* [n] device: the source tensors s */
+    const int64_t* count;        /* [n] device: elements of each */
+    int64_t max_count;
+    double tau;
+} glgym_polyak_args;
+
+int glgym_sac_rows(glgym_handle h, const glgym_sac_rows_args* a, void* stream);
+int glgym_sac_rows_grad(glgym_handle h, const glgym_sac_rows_grad_args* a, void* stream);
+int glgym_sac_batch(glgym_handle h, const glgym_sac_batch_args* a, void* stream);
+int glgym_sac_loss(glgym_handle h, const glgym_sac_loss_args* a, void* stream);
+int glgym_polyak(glgym_handle h, const glgym_polyak_args* a, void* stream);
 
 /* ---- on-device VecNormalize ---------------------------------------------------------------------
  * Replaces stable_baselines3.common.vec_env.VecNormalize (3rd party, pinned ==2.6.0 in the reference's requirements.txt)
