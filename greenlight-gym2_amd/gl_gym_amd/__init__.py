@@ -7,5 +7,6 @@ from .greenlight_model import GreenLight  # noqa: F401
 from .collector import RolloutCollector, TorchHeads  # noqa: F401
 from .ppo import PPO, PpoLossBuffers, ppo_loss  # noqa: F401
 from .sac import SAC, ReplayCollector, SquashedBuffers, squashed_sample  # noqa: F401
+from .recurrent_ppo import RecurrentCollector, RecurrentHeads, RecurrentPPO, lstm_cell  # noqa: F401
 
-__all__ = ["GreenLight", "RolloutCollector", "TorchHeads", "PPO", "PpoLossBuffers", "ppo_loss", "SAC", "ReplayCollector", "SquashedBuffers", "squashed_sample", "GlgymError", "GlgymOdeError", "init_default_params", "INFO_KEYS", "METRIC_KEYS", "LIB_PATH"]
+__all__ = ["GreenLight", "RolloutCollector", "TorchHeads", "PPO", "PpoLossBuffers", "ppo_loss", "SAC", "ReplayCollector", "SquashedBuffers", "squashed_sample", "RecurrentCollector", "RecurrentHeads", "RecurrentPPO", "lstm_cell", "GlgymError", "GlgymOdeError", "init_default_params", "INFO_KEYS", "METRIC_KEYS", "LIB_PATH"]

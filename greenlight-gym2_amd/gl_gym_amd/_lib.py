@@ -428,6 +428,31 @@ class PolyakArgs(C.Structure):
                 ("max_count", C.c_int64), ("tau", C.c_double)]
 
 
+# recurrent PPO (include/glgym.h glgym_lstm_cell / glgym_lstm_cell_grad / glgym_seq_batch)
+LSTM_MAX_H, LSTM_MAX_BLOCKS, LSTM_N_ACT, SEQ_MAX_STATE = 1024, 2048, 5, 4
+SEQ_BATCH_WS_BYTES = PPO_BATCH_WS_BYTES
+
+
+class LstmCellArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("H", C.c_int32), ("gx", C.c_void_p), ("gh", C.c_void_p), ("c_prev", C.c_void_p),
+                ("start", C.c_void_p), ("h", C.c_void_p), ("c", C.c_void_p), ("act", C.c_void_p)]
+
+
+class LstmCellGradArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("M", C.c_int32), ("H", C.c_int32), ("dh", C.c_void_p), ("dc", C.c_void_p), ("act", C.c_void_p),
+                ("c_prev", C.c_void_p), ("start", C.c_void_p), ("d_gx", C.c_void_p), ("d_gh", C.c_void_p), ("d_c_prev", C.c_void_p)]
+
+
+class SeqBatchArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("S", C.c_int32), ("offset", C.c_int32),
+                ("in_dim", C.c_int32), ("n_state", C.c_int32), ("state_dim", C.c_int32 * 4), ("seed", C.c_uint64), ("draw_index", C.c_uint64),
+                ("draw_base", C.c_void_p), ("obs", C.c_void_p), ("action", C.c_void_p), ("logp", C.c_void_p), ("advantage", C.c_void_p),
+                ("returns", C.c_void_p), ("value", C.c_void_p), ("episode_starts", C.c_void_p), ("state_src", C.c_void_p * 4),
+                ("mb_obs", C.c_void_p), ("mb_action", C.c_void_p), ("mb_logp", C.c_void_p), ("mb_adv", C.c_void_p), ("mb_ret", C.c_void_p),
+                ("mb_value", C.c_void_p), ("mb_start", C.c_void_p), ("state_out", C.c_void_p * 4), ("mb_index", C.c_void_p),
+                ("adv_stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class WeatherArgs(C.Structure):
     _fields_ = [("n_raw", C.c_int32), ("time", C.c_void_p), ("i_glob", C.c_void_p), ("t_out", C.c_void_p),
                 ("rh", C.c_void_p), ("wind", C.c_void_p), ("t_sky", C.c_void_p), ("co2_ppm", C.c_double),
@@ -508,6 +533,9 @@ PROTOTYPES = {
     "glgym_sac_batch": (C.c_int, [C.c_void_p, C.POINTER(SacBatchArgs), C.c_void_p]),
     "glgym_sac_loss": (C.c_int, [C.c_void_p, C.POINTER(SacLossArgs), C.c_void_p]),
     "glgym_polyak": (C.c_int, [C.c_void_p, C.POINTER(PolyakArgs), C.c_void_p]),
+    "glgym_lstm_cell": (C.c_int, [C.c_void_p, C.POINTER(LstmCellArgs), C.c_void_p]),
+    "glgym_lstm_cell_grad": (C.c_int, [C.c_void_p, C.POINTER(LstmCellGradArgs), C.c_void_p]),
+    "glgym_seq_batch": (C.c_int, [C.c_void_p, C.POINTER(SeqBatchArgs), C.c_void_p]),
     "glgym_vecnorm": (C.c_int, [C.c_void_p, C.POINTER(VecNormArgs), C.c_void_p]),
     "glgym_weather": (C.c_int, [C.c_void_p, C.POINTER(WeatherArgs), C.c_void_p]),
     "glgym_timer_start": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -112,7 +112,8 @@ class PPO:
     update(): for every epoch, for every minibatch: glgym_ppo_batch (gather + advantage statistics) -> the heads in torch with grad ->
     ppo_loss -> backward -> clip_grad_norm_ -> optimizer.step; then the draw word + 1.  Returns stats_t [n_epochs, n_minibatches, 8]
     (PPO.STATS; float64, on the device).  Never synchronises; everything of its own is allocated in the constructor.
-    Out of scope, refused: target_kl (a host decision per minibatch), learning-rate and clip schedules, recurrent policies."""
+    Out of scope, refused: target_kl (a host decision per minibatch), learning-rate and clip schedules.  Recurrent policies: gl_gym_amd.recurrent_ppo
+    (RecurrentCollector, RecurrentPPO)."""
 
     STATS = L.PPO_STATS
 

@@ -243,7 +243,8 @@ class SAC:
     glgym_sac_loss (actor stage), backward through the critics into squashed_sample (the critics' gradients are discarded), actor step,
     then the entropy coefficient's own Adam step on the gradient the same launch left -> glgym_polyak every target_update_interval steps
     -> the draw word + 1.  Returns stats_t [gradient_steps, 8] (SAC.STATS; float64, on the device).  Never synchronises.
-    Out of scope, refused: use_sde, n_critics != 2, learning-rate schedules, recurrent policies, prioritised replay."""
+    Out of scope, refused: use_sde, n_critics != 2, learning-rate schedules, recurrent policies (the on-policy recurrent agent is
+    gl_gym_amd.recurrent_ppo), prioritised replay."""
 
     STATS = L.SAC_STATS
 

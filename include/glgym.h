@@ -170,7 +170,7 @@ typedef struct {
  * glgym_plan_weather; glgym_rule_rows, glgym_plan_rollout_rule; glgym_policy_rows, glgym_plan_rollout_policy; glgym_plan_es_sample,
  * glgym_plan_es_utilities, glgym_plan_es_update; glgym_last_step_build; glgym_last_evalf_build; glgym_plan_cma_sample,
  * glgym_plan_cma_update; glgym_plan_constrain; glgym_ac_rows, glgym_gae; glgym_ppo_batch, glgym_ppo_loss; glgym_sac_rows,
- * glgym_sac_rows_grad, glgym_sac_batch, glgym_sac_loss, glgym_polyak */
+ * glgym_sac_rows_grad, glgym_sac_batch, glgym_sac_loss, glgym_polyak; glgym_lstm_cell, glgym_lstm_cell_grad, glgym_seq_batch */
 #define GLGYM_ABI_VERSION 7
 
 /* Device-pointer arguments of one batched env-step.  Exactly one of `action` / `control` is non-null. */
@@ -1495,6 +1495,122 @@ int glgym_sac_rows_grad(glgym_handle h, const glgym_sac_rows_grad_args* a, void*
 int glgym_sac_batch(glgym_handle h, const glgym_sac_batch_args* a, void* stream);
 int glgym_sac_loss(glgym_handle h, const glgym_sac_loss_args* a, void* stream);
 int glgym_polyak(glgym_handle h, const glgym_polyak_args* a, void* stream);
+
+/* ---- recurrent PPO: fused LSTM cell and sequence minibatches (csrc/gl_lstm.hpp, csrc/glgym_rppo.hip) ----
+ * What a recurrent policy (sb3-contrib's RecurrentPPO with MlpLstmPolicy) adds to the two on-policy sections above: the part of an LSTM
+ * step that lies between torch's two gate products and the new state, its backward pass, and minibatches of whole sequences for truncated
+ * back-propagation through time.  The products x W_ih^T + b and h W_hh^T, autograd through them, the heads and the optimiser stay the
+ * caller's, in torch.  The planning section's conventions hold: struct_size first, every refusal GLGYM_EINVAL with a message of its own
+ * before the handle is looked at and before anything is launched, asynchronous on `stream`, no allocation, no host synchronisation
+ * (capturable), plain vector stores, no atomics, an output that overlaps an input or another output is refused.  Opt-in: no other entry
+ * point changes.
+ *
+ * glgym_lstm_cell: one LSTM step on the gate pre-activations of M rows with hidden size H, gates in torch's order i, f, g, o:
+ * gx [M][4H] is the input product with whatever bias the caller's addmm folded in (b_ih + b_hh), gh [M][4H] is h_prev W_hh^T without a
+ * bias.  float32, every operation rounded on its own, in this order, per (row, unit j) (x_k = x[row][k H + j]):
+ *   keep = start == NULL || start[row] == 0
+ *   a_k  = keep ? gx_k + gh_k : gx_k                 k = i, f, g, o
+ *   c0   = keep ? c_prev : 0
+ *   i = (float)(1 / (1 + exp(-(double) a_i))), likewise f and o;  g = (float) tanh((double) a_g)
+ *   c = f * c0 + i * g          (two products and one sum, not contracted)
+ *   tc = (float) tanh((double) c);  h = o * tc
+ * act, if given, is [M][5H] holding i, f, g, o, tc: what glgym_lstm_cell_grad reads (NULL while collecting).
+ * The reset is a SELECT, not sb3-contrib's multiplication of the state by 1 - episode_start.  For finite states the two give the same
+ * numbers; with the select a NaN or an infinity in the state of an episode that has ended cannot enter the next one (0 * NaN is NaN).
+ * The mask commutes with the product -- (m h) W = m (h W) for a row scalar m in {0, 1} -- so gh may be computed from the unmasked h_prev
+ * and no masking launch is needed in front of it.
+ * Kernel: one lane per (row, unit), consecutive lanes on consecutive units of each gate plane; where H % 4 == 0 and every buffer is
+ * 16-byte aligned a lane takes four units with one 16-byte access per plane.  No LDS, no barrier, no scratch; at most 2048 blocks of 256,
+ * striding.  44 bytes per (row, unit) without act, 64 with it.
+ * Refused: M < 1, H outside 1 .. 1024, M * 4 H above 2^31 - 1, a NULL pointer other than start / act, an overlap. */
+typedef struct {
+    int32_t struct_size;
+    int32_t M;                   /* rows */
+    int32_t H;                   /* hidden size */
+    const float* gx;             /* [M][4H] f32: x W_ih^T + b_ih + b_hh */
+    const float* gh;             /* [M][4H] f32: h_prev W_hh^T */
+    const float* c_prev;         /* [M][H] f32 */
+    const uint8_t* start;        /* [M]: non-zero = the row begins an episode, or NULL: none does */
+    float* h;                    /* [M][H] f32 out */
+    float* c;                    /* [M][H] f32 out */
+    float* act;                  /* [M][5H] f32 out: i, f, g, o, tc, or NULL */
+} glgym_lstm_cell_args;
+
+/* glgym_lstm_cell_grad: the backward pass of glgym_lstm_cell from what it saved.  dh [M][H] is the gradient arriving at h, dc [M][H] the
+ * one arriving at c from the step after (NULL: 0).  float32, every operation rounded on its own, in this order, per (row, unit), with keep
+ * and c0 as above:
+ *   do   = dh * tc
+ *   dct  = dc + (dh * o) * (1 - tc * tc)
+ *   da_i = (dct * g) * (i * (1 - i));  da_f = (dct * c0) * (f * (1 - f));  da_g = (dct * i) * (1 - g * g);  da_o = do * (o * (1 - o))
+ *   d_gx = da;  d_gh = keep ? da : 0;  d_c_prev = keep ? dct * f : 0
+ * No transcendental, no reduction (the bias gradients are the addmm's own).  The kernel is shaped as glgym_lstm_cell's.
+ * Refused: as glgym_lstm_cell, the optional pointers being start and dc. */
+typedef struct {
+    int32_t struct_size;
+    int32_t M;
+    int32_t H;
+    const float* dh;             /* [M][H] f32 */
+    const float* dc;             /* [M][H] f32, or NULL: 0 */
+    const float* act;            /* [M][5H] f32: glgym_lstm_cell's */
+    const float* c_prev;         /* [M][H] f32 */
+    const uint8_t* start;        /* [M], or NULL */
+    float* d_gx;                 /* [M][4H] f32 out */
+    float* d_gh;                 /* [M][4H] f32 out */
+    float* d_c_prev;             /* [M][H] f32 out */
+} glgym_lstm_cell_grad_args;
+
+/* glgym_seq_batch: a minibatch of S whole sequences of L steps from a collector's [T][B] buffer, T % L == 0.  Sequence q in
+ * [0, (T / L) B) is chunk q / B of environment q % B, i.e. buffer rows ((q / B) L + l) B + q % B for l = 0 .. L - 1.  The minibatch is
+ * positions [offset, offset + S) of glgym_ppo_batch's permutation with N = (T / L) B (the same function, key tag and draw word): with L = 1
+ * the call gathers what glgym_ppo_batch gathers.  The outputs are time-major: row (l, s) = l S + s of each is the source row of step l of
+ * sequence perm(offset + s), bit for bit; mb_start is gathered from episode_starts (uint8); mb_index [S], if given, is perm(offset + s).
+ * For i < n_state <= 4, state_src[i] is [T / L][B][state_dim[i]] (a recurrent state stored at the first step of every chunk) and
+ * state_out[i] [S][state_dim[i]] its row perm(offset + s).
+ * No padding: a sequence is not split where an episode starts inside it, glgym_lstm_cell's start select does there what a per-step loop
+ * over the episode starts does.
+ * adv_stats, if given: mean and unbiased standard deviation of the L S gathered advantages in flattened (l, s) order, by the reduction
+ * and the formula stated for glgym_ppo_batch with M = L S.  workspace: [1024][2] doubles = 16 384 bytes, needed with adv_stats only.
+ * Refused: T, B, S or L < 1, T % L != 0, T B > 2^31 - 256, offset < 0 or offset + S > (T / L) B, in_dim outside 1 .. 1024, n_state outside
+ * 0 .. 4, a state dimension outside 1 .. 1024, a NULL source or output other than mb_index / adv_stats, adv_stats with L S < 2 or with a
+ * NULL or undersized workspace, an output that overlaps a source or another output. */
+typedef struct {
+    int32_t struct_size;
+    int32_t T;                   /* steps of the buffer */
+    int32_t B;                   /* environments */
+    int32_t L;                   /* steps of a sequence */
+    int32_t S;                   /* sequences of this minibatch */
+    int32_t offset;              /* first position of the permutation */
+    int32_t in_dim;              /* columns of obs */
+    int32_t n_state;             /* 0 .. 4 */
+    int32_t state_dim[4];
+    uint64_t seed;
+    uint64_t draw_index;
+    const uint64_t* draw_base;   /* device word added to draw_index, or NULL */
+    const float* obs;            /* [T][B][in_dim] f32 */
+    const float* action;         /* [T][B][6] f32 */
+    const float* logp;           /* [T][B] f32 */
+    const float* advantage;      /* [T][B] f32 */
+    const float* returns;        /* [T][B] f32 */
+    const float* value;          /* [T][B] f32 */
+    const uint8_t* episode_starts; /* [T][B] */
+    const float* state_src[4];   /* [T/L][B][state_dim[i]] f32 */
+    float* mb_obs;               /* [L][S][in_dim] f32 out */
+    float* mb_action;            /* [L][S][6] f32 out */
+    float* mb_logp;              /* [L][S] f32 out */
+    float* mb_adv;               /* [L][S] f32 out */
+    float* mb_ret;               /* [L][S] f32 out */
+    float* mb_value;             /* [L][S] f32 out */
+    uint8_t* mb_start;           /* [L][S] out */
+    float* state_out[4];         /* [S][state_dim[i]] f32 out */
+    int32_t* mb_index;           /* [S] i32 out, or NULL */
+    double* adv_stats;           /* [2] out: mean, unbiased standard deviation of mb_adv, or NULL */
+    double* workspace;           /* [1024][2] doubles, or NULL without adv_stats */
+    int64_t workspace_bytes;
+} glgym_seq_batch_args;
+
+int glgym_lstm_cell(glgym_handle h, const glgym_lstm_cell_args* a, void* stream);
+int glgym_lstm_cell_grad(glgym_handle h, const glgym_lstm_cell_grad_args* a, void* stream);
+int glgym_seq_batch(glgym_handle h, const glgym_seq_batch_args* a, void* stream);
 
 /* ---- on-device VecNormalize ---------------------------------------------------------------------
  * Replaces stable_baselines3.common.vec_env.VecNormalize (3rd party, pinned ==2.6.0 in the reference's requirements.txt)
